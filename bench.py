@@ -10,7 +10,8 @@ Workload: STL10-shaped 96x96, ClusterNet5g, output_k 70, 5 sub-heads, 660 pairs 
 pair, weak scaling (660 pairs per rank), RCCL all-reduce of the raw joint P (inside
 IID_loss) and of the parameter gradients.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0), the metric's record; `--full` adds `roofline`, `cpu_baseline` and the other
+measurements after the timed region, `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -61,8 +62,9 @@ def _free_port():
 def self_launch(args):
   """`python bench.py --gpus N` (N > 1) outside a launcher: become N ranks -- the reference's counterpart is one line
   that just works (torch.nn.DataParallel over the visible devices: cluster_sobel.py:146, segmentation_twohead.py:173).
-  Re-executes this command under `python -m torch.distributed.run --nproc-per-node N` (one process per GPU, RCCL); exits
-  non-zero with a message when the box has fewer than N devices -- never a silent 1-rank run."""
+  Runs this command under `python -m torch.distributed.run --nproc-per-node N` (one process per GPU, RCCL) as a child
+  process and exits with its return code (this process has already opened the device, so it must not replace its own
+  image with exec); exits non-zero with a message when the box has fewer than N devices -- never a silent 1-rank run."""
   backend = os.environ.get("IIC_DIST_BACKEND", "nccl")
   ndev = torch.cuda.device_count() if torch.cuda.is_available() else 0
   if ndev < args.gpus and backend == "nccl":
@@ -77,7 +79,9 @@ def self_launch(args):
          "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
   sys.stderr.write("bench.py: --gpus %d without a launcher environment: %s\n" % (args.gpus, " ".join(cmd)))
   sys.stderr.flush()
-  os.execv(sys.executable, cmd)
+  import subprocess
+  rc = subprocess.run(cmd).returncode
+  sys.exit(rc if rc >= 0 else 128 - rc)      # (killed by signal s: the shell's 128 + s)
 
 
 class Ranks(object):
@@ -495,6 +499,38 @@ def reference_api_rate(cfg, dev, imgs, imgs_tf, pairs, steps, auto_branch=False,
   return {"paired_images_per_sec": pairs / dt, "ms_per_step": 1e3 * dt, "final_loss": v, "what": what}
 
 
+DUMP_SAMPLE = 4 << 20       # float32 elements per sampled array (16 MB): params + grads + buffers + loss < 64 MB
+
+
+def dump_outputs(out_dir, loss, net):
+  """--dump-outputs DIR: what the timed path handed back in its LAST step, written right after the timed region (before
+  any --full measurement runs more steps), rank 0 only:
+    loss.npy      float64 [1]   the step's loss (the last head's for the two-head configs)
+    params.npy    float32       the parameters after the optimiser step  } all parameters flattened in named_parameters()
+    grads.npy     float32       the step's gradients (p.grad + what a     } order; above DUMP_SAMPLE elements, the same
+                                side branch accumulated: iic_amd.ops)     } fixed seeded sample of positions for both
+    buffers.npy   float32       the BatchNorm running statistics (every floating buffer, flattened, in full)
+  Inputs, initial weights and sample positions are all seeded: the same arguments give the same arrays to compare."""
+  import numpy as np
+  from iic_amd import ops
+  torch.cuda.synchronize()
+  params = [p for _, p in net.named_parameters()]
+  flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+  flat_g = torch.cat([(sum(ops.branch_grads(p), p.grad if p.grad is not None else torch.zeros_like(p))).detach()
+                      .reshape(-1).float() for p in params])
+  if flat_p.numel() > DUMP_SAMPLE:
+    rng = np.random.default_rng(20260101)
+    idx = torch.from_numpy(np.unique(rng.integers(0, flat_p.numel(), DUMP_SAMPLE))).to(flat_p.device)
+    flat_p, flat_g = flat_p[idx], flat_g[idx]
+  bufs = [b.detach().reshape(-1).float() for _, b in net.named_buffers() if b.dtype.is_floating_point]
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss.detach())], dtype=np.float64))
+  np.save(os.path.join(out_dir, "params.npy"), flat_p.float().cpu().numpy())
+  np.save(os.path.join(out_dir, "grads.npy"), flat_g.cpu().numpy())
+  np.save(os.path.join(out_dir, "buffers.npy"),
+          torch.cat(bufs).cpu().numpy() if bufs else np.zeros(0, dtype=np.float32))
+
+
 SEG_CONFIGS = {
   # BASELINE.json configs[3]: Potsdam-3 200x200 SegmentationNet10aTwoHead, batch 75, in_ch 4,
   # k_A 24 / k_B 3 (commands.txt:83); BASELINE asks T = 1, the reference's own setting is T = 10
@@ -582,10 +618,12 @@ def bench_segmentation(args):
     last = step()
   rk.fence()
   dt = rk.max_over_ranks(time.perf_counter() - t0) / args.steps
-  # kernel-level rooflines: HIP events around the contraction and around every conv launch, in extra
+  if args.dump_outputs and rk.rank == 0:
+    dump_outputs(args.dump_outputs, last, net)
+  # kernel-level rooflines (--full): HIP events around the contraction and around every conv launch, in extra
   # ONE-stream steps after the timed region (with two streams an event pair also spans whatever the
   # other view has in flight, and the event records cost GPU bubbles)
-  n_inst = 0 if args.no_roofline else min(args.steps, 2)
+  n_inst = min(args.steps, 2) if args.full and not args.no_roofline else 0
   streams_timed = 2 if two_streams[0] else 1
   two_streams[0] = False
   conv = ConvTimer()
@@ -748,7 +786,9 @@ def bench_6c(args):
   t_enq = time.perf_counter() - t0
   rk.fence()
   dt = rk.max_over_ranks(time.perf_counter() - t0) / args.steps
-  n_inst = 0 if args.no_roofline else min(args.steps, 3)
+  if args.dump_outputs and rk.rank == 0:
+    dump_outputs(args.dump_outputs, last, net)
+  n_inst = min(args.steps, 3) if args.full and not args.no_roofline else 0
   conv = ConvTimer()
   conv.install()
   for _ in range(n_inst):
@@ -797,12 +837,12 @@ def secondary_configs():
   import subprocess
   res = {}
   for name, extra in SECONDARY:
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", name] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--full"] + extra
     try:
       r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
       d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
       e = {"value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"],
-           "workload": d["config"]["workload"], "command": "python bench.py --config %s %s" % (name, " ".join(extra))}
+           "workload": d["config"]["workload"], "command": "python bench.py --config %s --full %s" % (name, " ".join(extra))}
       for k in ("roofline", "roofline_conv"):
         if k in d:
           e[k] = {q: d[k].get(q) for q in ("bound", "kernel", "achieved", "peak", "unit", "frac", "kernel_ms_per_step",
@@ -820,8 +860,17 @@ def main():
                        "measurements of the segmentation configs with their own roofline object")
   ap.add_argument("--T", type=int, default=None, help="half_T_side_dense override for the segmentation configs")
   ap.add_argument("--gpus", type=int, default=1)
-  ap.add_argument("--steps", type=int, default=10)
-  ap.add_argument("--warmup", type=int, default=3)
+  ap.add_argument("--steps", type=int, default=None,
+                  help="timed steps (default 10; 3 for the segmentation configs)")
+  ap.add_argument("--warmup", type=int, default=None,
+                  help="untimed steps before them (default 3; 1 for the segmentation configs)")
+  ap.add_argument("--full", action="store_true",
+                  help="also the measurements beyond the headline, each after the timed region: the roofline's "
+                       "instrumented steps, the replica-dedup and reference-API rates, the other BASELINE.json configs, "
+                       "the CPU baselines (the --no-* switches below still drop single ones); off: set up, warm up, "
+                       "time --steps steps, print the record")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step computed to DIR/*.npy (bench.dump_outputs)")
   ap.add_argument("--pairs", type=int, default=PAIRS_PER_GPU, help="pairs per GPU (default 660)")
   ap.add_argument("--lr", type=float, default=1e-4,
                   help="Adam learning rate (timing ablations that produce wrong gradients use 0 to keep the weights sane)")
@@ -843,21 +892,26 @@ def main():
                   help="N > 1: keep the GLOBAL batch at --pairs (default 660, the reference's batch_sz) and give "
                        "every rank pairs/N of it, instead of --pairs per rank (weak scaling, the default)")
   ap.add_argument("--no-secondary", action="store_true",
-                  help="skip the other BASELINE.json configs (mnist6c, cifar6c, potsdam3 T=1, coco3), which the default "
-                       "N=1 run measures in sub-processes after the headline and reports under `secondary`")
+                  help="skip the other BASELINE.json configs (mnist6c, cifar6c, potsdam3 T=1, coco3), which an N=1 "
+                       "--full run measures in sub-processes after the headline and reports under `secondary`")
   ap.add_argument("--with-augment", action="store_true",
                   help="also build every step's batch inside the timed region with the GPU paired "
                        "augmentation (iic_amd.augment, SURVEY 8f rank 1) from a resident uint8 "
                        "dataset, as cluster_sobel.py:205-232 does from its dataloaders; the default "
                        "(off) is the metric's own timed region, which excludes data loading")
   args = ap.parse_args()
+  seg = args.config in SEG_CONFIGS
+  if args.steps is None:
+    args.steps = 3 if seg else 10
+  if args.warmup is None:
+    args.warmup = 1 if seg else 3
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be >= 1 and --warmup >= 0")
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     self_launch(args)          # (does not return)
   if args.config in C6_CONFIGS:
     return bench_6c(args)
-  if args.config != "stl10_5g":
-    if args.steps == 10 and args.warmup == 3:
-      args.steps, args.warmup = 3, 1
+  if seg:
     return bench_segmentation(args)
 
   rk = Ranks(args)
@@ -1025,11 +1079,14 @@ def main():
   c_enq = time.thread_time() - c0
   fence()
   dt = time.perf_counter() - t0
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, last, net)
+  # Everything from here to the record is --full only (the plain run's record is the timed region alone).
   # Roofline of the conv kernels: HIP events around every conv launch, on the launch stream, in
   # extra steps run right AFTER the timed region.  (Inside the timed region the 316 event pairs
   # per step cost ~6 ms/step of GPU bubbles -- measured -- and would distort `value`.)
   timer = None
-  if not args.no_roofline:          # every rank runs the extra steps (they contain collectives)
+  if args.full and not args.no_roofline:          # every rank runs the extra steps (they contain collectives)
     if rank == 0:
       timer = ConvTimer()
       timer.install()
@@ -1058,7 +1115,8 @@ def main():
   # statistics are replication-invariant).  Same losses and gradients (tests: test_replica_dedup_fp32_mode_vs_reference_
   # golden), a third of that view's conv work.  The metric's `value` keeps the reference's redundant forward.
   dedup = None
-  if not dist_on and use_branch and use_graph and aug is None and not args.no_reference_api and args.pairs % 3 == 0:
+  if (args.full and not dist_on and use_branch and use_graph and aug is None and not args.no_reference_api
+      and args.pairs % 3 == 0):
     try:
       from iic_amd.archs import cluster as _cl
       from iic_amd.graph import CapturedPairStep
@@ -1081,7 +1139,7 @@ def main():
     except Exception as e:      # noqa: BLE001  (a secondary measurement never takes the headline down)
       dedup = {"error": "%s: %s" % (type(e).__name__, e)}
   ref_api = None
-  if not dist_on and not args.no_reference_api:
+  if args.full and not dist_on and not args.no_reference_api:
     ref_api = reference_api_rate(cfg, dev, imgs, imgs_tf, args.pairs, args.steps)
     # (rounds 3-4 also measured an eager two-stream variant; round 5 removed that mode: iic_amd/ops.py)
     ref_api["graphed"] = reference_api_rate(cfg, dev, imgs, imgs_tf, args.pairs, args.steps, auto_branch=True,
@@ -1160,9 +1218,9 @@ def main():
     if dist_on:
       out["config"]["data_parallel"] = dp_report
       out["config"]["data_parallel"]["streams_after_collectives"] = stream_check
-    if not dist_on and not args.no_secondary and args.pairs == PAIRS_PER_GPU:
+    if args.full and not dist_on and not args.no_secondary and args.pairs == PAIRS_PER_GPU:
       out["secondary"] = secondary_configs()
-    if not dist_on and not args.no_cpu_baseline:
+    if args.full and not dist_on and not args.no_cpu_baseline:
       out["cpu_baseline"] = cpu_baseline()
       out["cpu_baseline"]["configs0_mnist"] = cpu_baseline_mnist()
     # wall time of this whole invocation (imports, captures, the timed region, the reference-API / secondary / CPU legs)
