@@ -53,15 +53,12 @@ struct bd_blk {
 #ifndef BD_STORE_UB
 #define BD_STORE_UB 8      // rows per thread whose epilogue loads are in flight together (16 per tile)
 #endif
-#ifndef BD_RELOAD_NB
-#define BD_RELOAD_NB 4     // 16-B patch pieces in flight per thread at a chunk boundary (8 spills)
-#endif
 
 // ABL: timing-ablation build (tools/conv_perf.py --ablate; results are WRONG by design):
 //   1 = no patch reload at chunk boundaries, 2 = B fragments always from the same address
 //   (L2-hot), 4 = no epilogue, 8 = no chunk-boundary barriers either, 16 = no A-fragment LDS reads,
 //   32 = no global stores of the tile, 64 = no BatchNorm statistics.
-// DMA: the patch is fetched by LDS-DMA (global_load_lds_dwordx4: no staging VGPRs, every piece of
+// The patch is fetched by LDS-DMA (global_load_lds_dwordx4: no staging VGPRs, every piece of
 // a chunk in flight at once instead of 4-piece batches that each wait a full memory latency) into
 // unpadded 128-byte rows whose 16-byte slot is XOR-ed with a 3-bit key of the row -- the swizzle is
 // applied on the DMA's SOURCE address; A-fragment addresses then cost ~2 VALU per read instead of
@@ -70,8 +67,7 @@ struct bd_blk {
 // pixels the way consecutive GEMM rows visit them, so the 16 lanes of a ds_read_b128 group (rows
 // of consecutive m, any tap) see 16 consecutive D = 16 distinct (row parity, slot) pairs = all 64
 // banks, whereas a key on the raw row index collided across every row end (SQ_LDS_BANK_CONFLICT
-// was 51 % of the LDS cycles at 13- and 25-pixel rows).  !DMA: register-staged loads into
-// 144-byte-pitch rows (first version).
+// was 51 % of the LDS cycles at 13- and 25-pixel rows).
 // MS: 32-row MFMA sub-tiles per wave: 4 = 256-row workgroup tile (2 workgroups per CU), 2 = 128-row
 // tile (half the patch and accumulators: 3 workgroups per CU -- more tiles in flight to hide the
 // per-tile prologue / epilogue where the K loop is short, i.e. few input channels).
@@ -79,17 +75,16 @@ struct bd_blk {
 // WN: 64-cout column groups of the workgroup tile.  2: 128 couts, waves 2 (rows) x 2 (cols), MS*64 rows;
 // 1: 64 couts (layers with Cout = 64: the backward-data of a 64 -> 128 convolution, SegmentationNet10a c2), the
 // four waves stacked along the rows, MS*128 rows -- the wave tile stays MS x 2 MFMA blocks either way.
-template <bool GATHER, int ABL, bool DMA, int MS, int RED, int WN = 2>
+template <bool GATHER, int ABL, int MS, int RED, int WN = 2>
 __device__ __forceinline__ void bd_tile(
     const iic_conv_geom& g, const bf16_t* __restrict__ in, const unsigned char* __restrict__ wfrag,
     bf16_t* __restrict__ out, float* __restrict__ stats, const bf16_t* __restrict__ res_grad,
     const bf16_t* __restrict__ res_act, int accumulate, int lds_a_bytes,
-    int dense_key, const bf16_t* __restrict__ red_y, const float* __restrict__ red_coef,
+    const bf16_t* __restrict__ red_y, const float* __restrict__ red_coef,
     const bf16_t* __restrict__ red_y2, float* __restrict__ red_stats, float* __restrict__ red_stats2,
-    unsigned long long* __restrict__ prof, int stagger, int blk_in_class, int nwg_class, int m_base,
-    const bd_blk& B) {
+    unsigned long long* __restrict__ prof, int blk_in_class, int nwg_class, const bd_blk& B) {
   constexpr int BNT = WN * 64, NWM = 4 / WN;   // tile couts, wave row groups
-  constexpr bool CANBLK = !GATHER && DMA && MS * 32 * (4 / WN) == 256;      // 256-row tiles of either width
+  constexpr bool CANBLK = !GATHER && MS * 32 * (4 / WN) == 256;      // 256-row tiles of either width
   const bool blk = CANBLK && B.bw > 0;         // uniform
   constexpr int CLD = BNT + 8;
   constexpr bool PROF = (ABL & 128) != 0;
@@ -97,32 +92,20 @@ __device__ __forceinline__ void bd_tile(
   // ABL bit 512 (timing only, WRONG results): A-fragment addresses as for a 144-byte row pitch -- one add per tap and
   // sub-tile, immediate k-step offsets -- while the DMA still writes the swizzled 128-byte rows: what the K loop would
   // cost without its ~70 VALU of swizzle arithmetic per tap (LAB.md R6.9)
-  constexpr bool SWZ = DMA && (ABL & 512) == 0;
+  constexpr bool SWZ = (ABL & 512) == 0;
   // PROF (ABL bit 128, results CORRECT): wave 0 stamps s_memtime at the phase boundaries of its tile
   // into prof[blockIdx][BD_PROF_SLOTS] (tools/bd_timeline.py decodes them)
   unsigned long long t_stamp[8];
   unsigned long long t_bsum = 0, t_b0 = 0;
   int t_nb = 0;
   if (PROF) t_stamp[0] = __builtin_readcyclecounter();
-  // Stagger (stagger > 0 cycles): the two workgroups that share a CU start together and do identical
-  // work, so their prologues, chunk-boundary reloads and epilogues coincide instead of hiding behind
-  // each other's MFMA loops.  The workgroup in the odd threadgroup slot of its CU (HW_ID.TG_ID) of the
-  // FIRST dispatch round waits `stagger` cycles once; later workgroups inherit the offset from the
-  // slot they take over.
-  if (stagger > 0 && (int)blockIdx.x < 2 * 256) {
-    const unsigned hw = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 16 << 6 | 4);     // HW_ID.TG_ID
-    if (hw & 1u) {
-      const unsigned long long t_go = __builtin_readcyclecounter() + (unsigned long long)stagger;
-      while (__builtin_readcyclecounter() < t_go) __builtin_amdgcn_s_sleep(16);
-    }
-  }
   constexpr int BM = MS * 32 * NWM, WR = MS * 32;     // workgroup tile rows, rows per wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  unsigned char* sA = smem_raw;                                   // [NP256][ROWB]
+  unsigned char* sA = smem_raw;                                   // [NP256][128]
   int* s_pin = reinterpret_cast<int*>(smem_raw + lds_a_bytes);     // [256]
   int* s_pout = s_pin + BM;                                     // [256]
   float* s_red = reinterpret_cast<float*>(s_pout + BM);         // [NWM wm][2][BNT]  (512 floats)
-  unsigned char* s_key = reinterpret_cast<unsigned char*>(s_red + NWM * 2 * BNT);   // DMA: [npix] swizzle keys (after 512 floats)
+  unsigned char* s_key = reinterpret_cast<unsigned char*>(s_red + NWM * 2 * BNT);   // [npix] swizzle keys (after 512 floats)
   bf16_t* sC = reinterpret_cast<bf16_t*>(smem_raw);                // epilogue reuse of sA
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -134,7 +117,7 @@ __device__ __forceinline__ void bd_tile(
   const int tix = xcd_tile_index(blk_in_class, nwg_class);
   const int mtile = tix / nt, ntile = tix - mtile * nt;
   const int n0 = ntile * BNT;
-  const int m0 = m_base + mtile * BM;
+  const int m0 = mtile * BM;
   const int in_pixels = g.N * g.in_Hp * g.in_Wp;
 
   int v_tapoff = g.tap_off[lane & (IIC_MAX_TAPS - 1)];
@@ -173,10 +156,10 @@ __device__ __forceinline__ void bd_tile(
   // (block tiling: the same in patch coordinates -- row pitch PW, J = PW - bw, even by the host's choice)
   const int keyw = blk ? B.PW : g.in_Wp;
   const int jskip = blk ? B.PW - B.bw
-                        : ((dense_key && !GATHER && g.sx == 1 && ((g.in_Wp - g.MX) & 1) == 0) ? g.in_Wp - g.MX : 0);
+                        : ((!GATHER && g.sx == 1 && ((g.in_Wp - g.MX) & 1) == 0) ? g.in_Wp - g.MX : 0);
   auto dense_of = [&](int p) { return p - jskip * (p / keyw); };
-  int arow[MS];     // !DMA: byte offset of the lane's row (tap 0) + k-chunk; DMA: patch row index
-  int drow[MS];     // DMA: D of the lane's row at tap offset 0
+  int arow[MS];     // patch row index (ABL bit 512: byte offset of the lane's row at a 144-byte pitch + k-chunk)
+  int drow[MS];     // D of the lane's row at tap offset 0
 #pragma unroll
   for (int ms = 0; ms < MS; ++ms) {
     const int row = wm * WR + ms * 32 + l31;
@@ -184,13 +167,13 @@ __device__ __forceinline__ void bd_tile(
     arow[ms] = SWZ ? pr : pr * ROWB + g5 * 16;
     drow[ms] = (SWZ && !GATHER) ? dense_of(s_pin[row]) : pr;
   }
-  if (DMA && !GATHER && jskip != 0) {     // (without a skip the key is a function of r alone: no table)
+  if (!GATHER && jskip != 0) {     // (without a skip the key is a function of r alone: no table)
     for (int r = tid; r < npix; r += BD_THREADS) s_key[r] = (unsigned char)((dense_of(p_lo + r) >> 1) & 7);
     __syncthreads();
   }
   // per-tap increment of D: tap_off = dy * in_Wp + dx  ->  dy * (in_Wp - J) + dx
   const int v_tapd = v_tapoff - jskip * (v_tapoff / keyw);
-  // DMA patch loader: 1-KB blocks over the 4 waves; piece q -> LDS byte q*16 (row q>>3, physical
+  // patch loader: 1-KB blocks over the 4 waves; piece q -> LDS byte q*16 (row q>>3, physical
   // slot q&7), source = logical slot (q&7) ^ ((row>>1)&7) of the row's pixel
   const int nblk = (npix * 128 + 1023) >> 10;
   auto dma_patch = [&](int c0) {
@@ -213,7 +196,7 @@ __device__ __forceinline__ void bd_tile(
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
-  // DMA layout: byte address of A fragment (row R, k-step ks, lane half g5) = R*128 + ((2ks+g5) ^ key)*16,
+  // patch layout: byte address of A fragment (row R, k-step ks, lane half g5) = R*128 + ((2ks+g5) ^ key)*16,
   // key = (D >> 1) & 7 of the row
   auto a_base = [&](int R, int D) { return R * 128 + (((g5 ^ (D >> 1)) & 1) << 4); };
   auto a_kk = [&](int D) { return ((D >> 2) & 3) << 5; };
@@ -249,12 +232,7 @@ __device__ __forceinline__ void bd_tile(
         if (NEWORD) bd_bload(Bc[ks][ns], p + ns * 4096 + ks * 1024);
         else Bc[ks][ns] = *reinterpret_cast<const u32x4*>(p + ns * 4096 + ks * 1024);
   }
-  if (DMA) {
-    dma_patch(0);
-  } else {
-    // the accumulators are not live yet => 16 pieces (64 VGPRs) in flight per thread
-    igemm_load_patch<GATHER, BD_THREADS, 16>(sA, in, g.Cin, 0, p_lo, npix, in_pixels, s_pin, tid);
-  }
+  dma_patch(0);
   __syncthreads();
   if (PROF) t_stamp[2] = __builtin_readcyclecounter();
 
@@ -268,7 +246,7 @@ __device__ __forceinline__ void bd_tile(
   // the iteration and recycles the B registers as A temporaries (=> vmcnt(0) every iteration).
   int tap = 0, chunk = 0;
   bf16x8 a[2][MS];
-  int pcur[MS], kcur[MS];       // kcur: DMA only (k-step XOR term of the row's swizzle)
+  int pcur[MS], kcur[MS];       // kcur: the k-step XOR term of the row's swizzle (0 without SWZ)
 #pragma unroll
   for (int ms = 0; ms < MS; ++ms) {
     const int t0 = GATHER ? 0 : __builtin_amdgcn_readlane(v_tapoff, 0);
@@ -369,12 +347,7 @@ __device__ __forceinline__ void bd_tile(
     if (more && tn == 0 && !(ABL & 8)) {       // next iteration starts a new channel chunk
       if (PROF) t_b0 = __builtin_readcyclecounter();
       __syncthreads();           // everyone is done reading the patch
-      if (!(ABL & 1)) {
-        if (DMA)
-          dma_patch(cn * 64);
-        else
-          igemm_load_patch<GATHER, BD_THREADS, BD_RELOAD_NB>(sA, in, g.Cin, cn * 64, p_lo, npix, in_pixels, s_pin, tid);
-      }
+      if (!(ABL & 1)) dma_patch(cn * 64);
       __syncthreads();
       if (PROF) { t_bsum += __builtin_readcyclecounter() - t_b0; ++t_nb; }
 #pragma unroll
@@ -480,32 +453,19 @@ __device__ __forceinline__ void bd_tile(
 
 // Launch shape.  Tiles are equal work, so a launch runs in whole rounds over the chip's workgroup slots
 // (2 per CU): 1 612 layer-2 tiles take 4 rounds for 3.15 rounds of work, 872 layer-3 tiles 2 for 1.70
-// (tools/bd_timeline.py: slot occupancy 0.79 / 0.85).  MS2 != 0: the tiles of the last, partial round are
-// MS2 * 64 rows high instead of 256, sized so that they still fit ONE round (host: the split below): the
-// first n_big workgroups take 256-row tiles of rows [0, m_split), the others MS2-tiles of the rest.
-// Results per output row are unchanged (same K order); only the grouping of the statistics partials differs.
-template <bool GATHER, int ABL, bool DMA, int MS, int RED, int MS2, int WN = 2>
-__global__ __launch_bounds__(BD_THREADS, ((MS == 4 || MS2 != 0 || WN == 1) ? 2 : 3)) void conv_igemm_bd_kernel(
+// (tools/bd_timeline.py: slot occupancy 0.79 / 0.85).  Smaller tiles for the last, partial round measured -5 % per
+// launch alone, but inside the two-stream step the other view already fills those tails (38.0 vs 37.7 ms/step).
+template <bool GATHER, int ABL, int MS, int RED, int WN = 2>
+__global__ __launch_bounds__(BD_THREADS, ((MS == 4 || WN == 1) ? 2 : 3)) void conv_igemm_bd_kernel(
     const iic_conv_geom g, const bf16_t* __restrict__ in, const unsigned char* __restrict__ wfrag,
     bf16_t* __restrict__ out, float* __restrict__ stats, const bf16_t* __restrict__ res_grad,
     const bf16_t* __restrict__ res_act, int accumulate, int num_mtiles, int lds_a_bytes,
-    int dense_key, const bf16_t* __restrict__ red_y, const float* __restrict__ red_coef,
+    const bf16_t* __restrict__ red_y, const float* __restrict__ red_coef,
     const bf16_t* __restrict__ red_y2, float* __restrict__ red_stats, float* __restrict__ red_stats2,
-    unsigned long long* __restrict__ prof, int stagger, int n_big, int m_split, const bd_blk B) {
-  const bd_blk B0 = {0, 0, 0, 0, 0, 0, 0};
-  if (WN == 1) {
-    bd_tile<GATHER, ABL, DMA, MS, RED, 1>(g, in, wfrag, out, stats, res_grad, res_act, accumulate, lds_a_bytes,
-                                          dense_key, red_y, red_coef, red_y2, red_stats, red_stats2, prof, stagger,
-                                          (int)blockIdx.x, num_mtiles * (g.Cout / 64), 0, B);
-  } else if (MS2 == 0 || (int)blockIdx.x < n_big) {
-    bd_tile<GATHER, ABL, DMA, MS, RED>(g, in, wfrag, out, stats, res_grad, res_act, accumulate, lds_a_bytes,
-                                       dense_key, red_y, red_coef, red_y2, red_stats, red_stats2, prof, stagger,
-                                       (int)blockIdx.x, MS2 == 0 ? num_mtiles * (g.Cout / BD_BN) : n_big, 0, MS2 == 0 ? B : B0);
-  } else {
-    bd_tile<GATHER, ABL, DMA, (MS2 == 0 ? MS : MS2), RED>(
-        g, in, wfrag, out, stats, res_grad, res_act, accumulate, lds_a_bytes, dense_key, red_y, red_coef, red_y2,
-        red_stats, red_stats2, prof, stagger, (int)blockIdx.x - n_big, (int)gridDim.x - n_big, m_split, B0);
-  }
+    unsigned long long* __restrict__ prof, const bd_blk B) {
+  bd_tile<GATHER, ABL, MS, RED, WN>(g, in, wfrag, out, stats, res_grad, res_act, accumulate, lds_a_bytes, red_y,
+                                    red_coef, red_y2, red_stats, red_stats2, prof, (int)blockIdx.x,
+                                    num_mtiles * (g.Cout / (WN * 64)), B);
 }
 
 // fp32 OIHW -> bf16 MFMA-B-fragment order.  mode 0 (forward operand): GEMM N = Cout, K = Cin;
@@ -540,9 +500,6 @@ int iic_pw_supported(const iic_conv_geom* g);
 int iic_pw_launch(const iic_conv_geom* g, const void* in, const void* wfrag, void* out, float* stats,
                   const void* res_grad, const void* res_act, int accumulate, const void* red_y,
                   const float* red_coef, const void* red_y2, float* red_stats, float* red_stats2, void* stream);
-// also take LDS footprints that leave room for only one workgroup per CU (large-image segmentation layers: still
-// 15-20 % faster than conv_igemm_kernel)
-IIC_SWITCH(g_bd_one_wg, 1, iic_debug_bd_one_wg)
 IIC_SWITCH(g_p64_enabled, 1, iic_debug_enable_p64)
 IIC_SWITCH(g_p64_red, 0, iic_debug_p64_red)      // 1: allow the fused reduction in the persistent kernel (tests, A/B)
 
@@ -555,36 +512,21 @@ IIC_HOOK int iic_debug_bd_prof_slots(void) { return BD_PROF_SLOTS; }
 #else
 static constexpr unsigned long long* g_bd_prof = nullptr;
 #endif
-IIC_SWITCH(g_bd_stagger, 0, iic_debug_bd_stagger)   // cycles per tap by which odd-slot workgroups of the first round start late (0 = off)
-IIC_SWITCH(g_bd_dma, 1, iic_debug_bd_dma)           // 1: LDS-DMA patch loads (128-B swizzled rows), 0: register-staged (144-B rows)
 
 // ms: 4 = 256-row tiles, 2 = 128-row tiles (the kernel's MS)
 // (wn: the kernel's WN -- 1 = 64-cout tiles of ms*128 rows)
 static long bd_lds_a(const iic_conv_geom* g, int ms, int wn = 2) {
   const long bm = ms * 32 * (4 / wn);
   const long npix = g->ntaps == 1 ? bm : (bm >= 192 ? g->NP256 : g->NP);
-  long a = g_bd_dma ? ((npix * 128 + 1023) & ~1023L) : npix * ROWB;
+  long a = (npix * 128 + 1023) & ~1023L;
   long c = bm * (wn * 64 + 8) * 2;
   long m = a > c ? a : c;
   return (m + 15) & ~15L;
 }
 
-// input pixel of GEMM row m (conv_tile.h igemm_row_pixels, host side)
-static long bd_row_pin_host(const iic_conv_geom* g, long m) {
-  const long plane = (long)g->MY * g->MX, mp = g->MP > 0 ? g->MP : plane;
-  long n = m / mp, r = m - n * mp;
-  if (n >= g->N) { n = g->N - 1; r = plane - 1; }
-  r = r < plane ? r : plane - 1;
-  const long y = r / g->MX, x = r - y * g->MX;
-  return (n * g->in_Hp + y * g->sy + g->oy) * g->in_Wp + x * g->sx + g->ox;
-}
-// 1: last partial round in smaller tiles. Per launch alone -5 % (layer 2 / 3), but inside the two-stream step the other
-// view already fills those tails: 38.0 vs 37.7 ms/step (r03 A/B) => off
-IIC_SWITCH(g_bd_mixed, 0, iic_debug_bd_mixed)
-IIC_SWITCH(g_bd_dense_key, 1, iic_debug_bd_dense_key)   // 0: swizzle key from the raw pixel index (A/B: conflicts at row ends)
 static long bd_key_bytes(const iic_conv_geom* g, int ms, int wn = 2) {    // swizzle-key table of the DMA patch (1 B / row)
-  const int jskip = (g_bd_dense_key && g->ntaps > 1 && g->sx == 1 && ((g->in_Wp - g->MX) & 1) == 0) ? g->in_Wp - g->MX : 0;
-  return (g_bd_dma && jskip != 0) ? (((long)(ms * 32 * (4 / wn) >= 192 ? g->NP256 : g->NP) + 15) & ~15L) : 0;
+  const int jskip = (g->ntaps > 1 && g->sx == 1 && ((g->in_Wp - g->MX) & 1) == 0) ? g->in_Wp - g->MX : 0;
+  return jskip != 0 ? (((long)(ms * 32 * (4 / wn) >= 192 ? g->NP256 : g->NP) + 15) & ~15L) : 0;
 }
 static long bd_lds_total(const iic_conv_geom* g, int ms, int wn = 2) {
   return bd_lds_a(g, ms, wn) + 2L * ms * 32 * (4 / wn) * 4 + 4L * BD_BN * 4 + bd_key_bytes(g, ms, wn);
@@ -592,13 +534,15 @@ static long bd_lds_total(const iic_conv_geom* g, int ms, int wn = 2) {
 // 64-cout tiles (kernel WN = 1, 256 rows): layers whose Cout is an odd multiple of 64
 IIC_SWITCH(g_bd_w1, 1, iic_debug_bd_w1)
 static bool bd_w1_ok(const iic_conv_geom* g) {
-  return g_bd_w1 && g_bd_dma && g->Cout % 64 == 0 && g->Cout % BD_BN != 0 && g->ntaps > 1 && g->NP256 > 0 &&
+  return g_bd_w1 && g->Cout % 64 == 0 && g->Cout % BD_BN != 0 && g->ntaps > 1 && g->NP256 > 0 &&
          bd_lds_total(g, 2, 1) <= 160 * 1024;
 }
 // Tile height per geometry.  g_bd_ms: 0 = heuristic, 2 / 4 = forced (A/B runs, tests).
 IIC_SWITCH(g_bd_ms, 0, iic_debug_bd_ms)
 static int bd_pick_ms(const iic_conv_geom* g) {
-  const bool ok4 = (g->ntaps == 1 || g->NP256 > 0) && bd_lds_total(g, 4) <= (g_bd_one_wg ? 160 : 80) * 1024;
+  // (256-row tiles also where only one workgroup fits a CU: large-image segmentation layers, still 15-20 % faster
+  // than conv_igemm_kernel)
+  const bool ok4 = (g->ntaps == 1 || g->NP256 > 0) && bd_lds_total(g, 4) <= 160 * 1024;
   const bool ok2 = (g->ntaps == 1 || g->NP > 0) && bd_lds_total(g, 2) <= 160 * 1024;
   if (g_bd_ms == 4) return ok4 ? 4 : (ok2 ? 2 : 0);
   if (g_bd_ms == 2) return ok2 ? 2 : (ok4 ? 4 : 0);
@@ -634,10 +578,9 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
 // row-major 256-row patch is too big for two workgroups per CU, where the sub-image patch is not.  Block shape: fewest
 // tiles x (MFMA time + half the patch bytes), over shapes whose patch keeps two workgroups per CU.
 IIC_SWITCH(g_bd_blk, 1, iic_debug_bd_blk)       // 0: row-major tiles only; 2: block tiles wherever they apply (A/B)
-IIC_SWITCH(g_bd_blk_bw, 0, iic_debug_bd_blk_bw)  // > 0: force this block width where it is valid (shape sweeps)
 static int bd_block_config(const iic_conv_geom* g, bd_blk* B, int wn) {      // wn: the kernel's WN (tile couts / 64)
   B->bw = 0;
-  if (!g_bd_blk || !g_bd_dma || g->ntaps < 2 || g->Cout % (wn * 64) != 0 || g->Cin % 64 != 0) return 0;
+  if (!g_bd_blk || g->ntaps < 2 || g->Cout % (wn * 64) != 0 || g->Cin % 64 != 0) return 0;
   if (g->sy != 1 || g->sx != 1 || g->ty != 1 || g->tx != 1 || g->MY < 32 || g->MX < 32 || g->NP256 <= 0) return 0;
   int mix = 0, miy = 0;
   for (int t = 0; t < g->ntaps; ++t) {
@@ -653,7 +596,6 @@ static int bd_block_config(const iic_conv_geom* g, bd_blk* B, int wn) {      // 
   for (int bw = 8; bw <= 64 && bw <= g->MX; ++bw) {
     const int bh = BD_BM / bw;
     if (bh < 2 || bh > g->MY) continue;
-    if (g_bd_blk_bw > 0 && bw != g_bd_blk_bw) continue;
     const long tiles = (long)((g->MX + bw - 1) / bw) * ((g->MY + bh - 1) / bh);
     const long npix = (long)(bw + mix) * (bh + miy);
     const long a = (npix * 128 + 1023) & ~1023L;
@@ -665,7 +607,7 @@ static int bd_block_config(const iic_conv_geom* g, bd_blk* B, int wn) {      // 
   }
   if (best < 0) return 0;
   const int bw = best_bw, bh = BD_BM / bw;
-  if (g_bd_blk_bw == 0 && (double)g->MY * g->MX < 0.88 * (double)BD_BM * (double)best_tiles) return 0;      // > 12 % idle rows
+  if ((double)g->MY * g->MX < 0.88 * (double)BD_BM * (double)best_tiles) return 0;      // > 12 % idle rows
   const int npix = (bw + mix) * (bh + miy);
   // worth it where the row-major patch costs the second workgroup of a CU or is much larger
   if (g_bd_blk != 2 && !(bd_lds_total(g, wn == 2 ? 4 : 2, wn) > 80 * 1024 || npix * 10 < g->NP256 * 7)) return 0;
@@ -707,7 +649,7 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
     return iic_p64_launch(g, in, wfrag, out, stats, res_grad, res_act, accumulate, red_y, red_coef, red_y2,
                           red_stats, red_stats2, stream);
   }
-  if (iic_debug_get_ablate() == 0 && g_bd_dma && g_bd_ms == 0 && iic_pw_supported(g))
+  if (iic_debug_get_ablate() == 0 && g_bd_ms == 0 && iic_pw_supported(g))
     return iic_pw_launch(g, in, wfrag, out, stats, res_grad, res_act, accumulate, red_y, red_coef, red_y2, red_stats,
                          red_stats2, stream);
   const long M = igemm_rows_host(g);
@@ -731,16 +673,15 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
     static bool attr = false;                                                                          \
     if (!attr) {                                                                                       \
       (void)hipFuncSetAttribute(                                                                       \
-          reinterpret_cast<const void*>(&conv_igemm_bd_kernel<false, 0, true, 2, RD_, 0, 1>),          \
+          reinterpret_cast<const void*>(&conv_igemm_bd_kernel<false, 0, 2, RD_, 1>),          \
           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                     \
       attr = true;                                                                                     \
     }                                                                                                  \
-    hipLaunchKernelGGL((conv_igemm_bd_kernel<false, 0, true, 2, RD_, 0, 1>), dim3(grid1),              \
+    hipLaunchKernelGGL((conv_igemm_bd_kernel<false, 0, 2, RD_, 1>), dim3(grid1),              \
                        dim3(BD_THREADS), lds1, s1, *g, (const bf16_t*)in, (const unsigned char*)wfrag, \
                        (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act,           \
-                       accumulate, mt1, la1, g_bd_dense_key, (const bf16_t*)red_y, red_coef,           \
-                       (const bf16_t*)red_y2, red_stats, red_stats2, (unsigned long long*)nullptr, 0,  \
-                       0, 0, B1);                                                                      \
+                       accumulate, mt1, la1, (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2,    \
+                       red_stats, red_stats2, (unsigned long long*)nullptr, B1);                       \
   } while (0)
     if (red == 0) BD_LAUNCH_W1(0); else if (red == 1) BD_LAUNCH_W1(1); else BD_LAUNCH_W1(2);
     return iic_launch_status();
@@ -752,7 +693,7 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
   const int bm = ms * 64;
   const int mt = blocked ? g->N * BB.nbx * BB.nby : (int)((M + bm - 1) / bm);
   const int nt = g->Cout / BD_BN;
-  int grid = mt * nt;
+  const int grid = mt * nt;
   int la = (int)bd_lds_a(g, ms);
   long lds = bd_lds_total(g, ms);
   if (blocked) {
@@ -760,79 +701,39 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
     la = (int)(((a > c ? a : c) + 15) & ~15L);
     lds = la + 2L * BD_BM * 4 + 4L * BD_BN * 4 + ((BB.npix + 15) & ~15L);
   }
-  // last partial round in smaller tiles (see conv_igemm_bd_kernel)
-  int ms2 = 0, n_big = 0, m_split = 0;
-  if (g_bd_mixed && !blocked && ms == 4 && g->ntaps > 1 && g_bd_dma && iic_debug_get_ablate() == 0) {
-    const int slots = (lds <= 80 * 1024 ? 2 : 1) * 256;
-    const int per_round = slots / nt;                       // m-tiles per round
-    const int full = per_round > 0 ? mt / per_round : 0;    // whole rounds of 256-row tiles
-    if (full >= 1 && mt % per_round != 0) {
-      const long rem = M - (long)full * per_round * 256;
-      for (int c = 2; c <= 3 && ms2 == 0; ++c)
-        if ((rem + 64 * c - 1) / (64 * c) <= per_round) ms2 = c;
-      if (ms2 != 0) {
-        // the small tiles stage their patch in the 256-row tile's LDS image: every span must fit it
-        // (128-row tiles at multiples of 128 rows are covered by g->NP by construction)
-        int max_tap = 0;
-        for (int t = 0; t < g->ntaps; ++t) max_tap = g->tap_off[t] > max_tap ? g->tap_off[t] : max_tap;
-        const long bound = ms2 == 2 ? g->NP : g->NP256;
-        for (long m0 = (long)full * per_round * 256; m0 < M && ms2 != 0; m0 += 64 * ms2) {
-          const long m1 = (m0 + 64 * ms2 < M ? m0 + 64 * ms2 : M) - 1;
-          if (bd_row_pin_host(g, m1) - bd_row_pin_host(g, m0) + max_tap + 1 > bound) ms2 = 0;
-        }
-      }
-      if (ms2 != 0) {
-        n_big = full * per_round * nt;
-        m_split = full * per_round * 256;
-        grid = n_big + (int)((rem + 64 * ms2 - 1) / (64 * ms2)) * nt;
-      }
-    }
-  }
   hipStream_t s = (hipStream_t)stream;
-#define BD_LAUNCH5(GA_, AB_, DM_, MS_, RD_, M2_)                                                  \
+#define BD_LAUNCH4(GA_, AB_, MS_, RD_)                                                            \
   do {                                                                                           \
     static bool attr = false;                                                                    \
     if (!attr) {                                                                                 \
       (void)hipFuncSetAttribute(                                                                 \
-          reinterpret_cast<const void*>(&conv_igemm_bd_kernel<GA_, AB_, DM_, MS_, RD_, M2_>),    \
+          reinterpret_cast<const void*>(&conv_igemm_bd_kernel<GA_, AB_, MS_, RD_>),              \
           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                               \
       attr = true;                                                                               \
     }                                                                                            \
-    hipLaunchKernelGGL((conv_igemm_bd_kernel<GA_, AB_, DM_, MS_, RD_, M2_>), dim3(grid),         \
+    hipLaunchKernelGGL((conv_igemm_bd_kernel<GA_, AB_, MS_, RD_>), dim3(grid),                   \
                        dim3(BD_THREADS), lds, s, *g, (const bf16_t*)in,                          \
                        (const unsigned char*)wfrag, (bf16_t*)out, stats, (const bf16_t*)res_grad, \
-                       (const bf16_t*)res_act, accumulate, mt, la, g_bd_dense_key,               \
-                       (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2, red_stats,         \
-                       red_stats2, g_bd_prof, g_bd_stagger * (g->ntaps > 1 ? g->ntaps : 0),      \
-                       n_big, m_split, BB);                                                      \
+                       (const bf16_t*)res_act, accumulate, mt, la, (const bf16_t*)red_y,         \
+                       red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_bd_prof, BB);   \
   } while (0)
-#define BD_LAUNCH4(GA_, AB_, DM_, MS_, RD_)                                                       \
+#define BD_LAUNCH3(GA_, AB_, MS_)                                                                 \
   do {                                                                                           \
-    if (AB_ == 0 && !GA_ && DM_ && MS_ == 4 && ms2 == 2) BD_LAUNCH5(false, 0, true, 4, RD_, 2);  \
-    else if (AB_ == 0 && !GA_ && DM_ && MS_ == 4 && ms2 == 3) BD_LAUNCH5(false, 0, true, 4, RD_, 3); \
-    else BD_LAUNCH5(GA_, AB_, DM_, MS_, RD_, 0);                                                 \
-  } while (0)
-#define BD_LAUNCH3(GA_, AB_, DM_, MS_)                                                            \
-  do {                                                                                           \
-    if ((AB_ != 0 && AB_ != 128 && AB_ != 256) || GA_ || red == 0) {                                           \
+    if ((AB_ != 0 && AB_ != 128 && AB_ != 256) || GA_ || red == 0) {                             \
       if (red != 0) return IIC_ERR_UNSUPPORTED;                                                  \
-      BD_LAUNCH4(GA_, AB_, DM_, MS_, 0);                                                         \
-    } else if (red == 1) BD_LAUNCH4(false, (AB_ == 128 || AB_ == 256 ? AB_ : 0), DM_, MS_, 1);                 \
-    else BD_LAUNCH4(false, (AB_ == 128 || AB_ == 256 ? AB_ : 0), DM_, MS_, 2);                                 \
-  } while (0)
-#define BD_LAUNCH2(GA_, AB_, DM_)                                                                 \
-  do {                                                                                           \
-    if (ms == 4) BD_LAUNCH3(GA_, AB_, DM_, 4); else BD_LAUNCH3(GA_, AB_, DM_, 2);                \
+      BD_LAUNCH4(GA_, AB_, MS_, 0);                                                              \
+    } else if (red == 1) BD_LAUNCH4(false, (AB_ == 128 || AB_ == 256 ? AB_ : 0), MS_, 1);        \
+    else BD_LAUNCH4(false, (AB_ == 128 || AB_ == 256 ? AB_ : 0), MS_, 2);                        \
   } while (0)
 #define BD_LAUNCH(GA_, AB_)                                                                       \
   do {                                                                                           \
-    if (g_bd_dma) BD_LAUNCH2(GA_, AB_, true); else BD_LAUNCH2(GA_, AB_, false);                  \
+    if (ms == 4) BD_LAUNCH3(GA_, AB_, 4); else BD_LAUNCH3(GA_, AB_, 2);                          \
   } while (0)
   if (g->ntaps == 1) BD_LAUNCH(true, 0);
   else switch (iic_debug_get_ablate()) {
 #ifdef IIC_BD_ABLATIONS
     // timing-ablation and phase-stamp instantiations (tools/conv_perf.py --frag-ablate, tools/bd_timeline.py): NOT in the
-    // product library -- `make -C iic_amd/csrc ABL=1` builds them in (13 more instantiations of the kernel)
+    // product library -- `make -C iic_amd/csrc ABL=1` builds them in
     case 1: BD_LAUNCH(false, 1); break;
     case 2: BD_LAUNCH(false, 2); break;
     case 3: BD_LAUNCH(false, 3); break;

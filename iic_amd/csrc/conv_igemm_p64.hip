@@ -58,8 +58,8 @@ __device__ __forceinline__ void p64_walk_pixels(const P64Walk& w, const iic_conv
 // stores, 4 = one tap instead of nine.
 // RED: fused BatchNorm-backward reduction over the stored rows (conv_tile.h); the partial sums
 // stay in registers across all tiles of the workgroup.
-// NW = 8: two waves per SIMD, wave tile 64 rows x 32 couts (one A fragment read per MFMA: the LDS read
-// pipe is as busy as the matrix pipe).  NW = 4 ("wide", iic_debug_p64_wide(1)): one wave per SIMD with 64 rows x
+// Eight waves, two per SIMD, wave tile 64 rows x 32 couts (one A fragment read per MFMA: the LDS read
+// pipe is as busy as the matrix pipe).  Tried and rejected: four "wide" waves, one per SIMD with 64 rows x
 // 64 couts -- every A fragment feeds two MFMAs (half the LDS read traffic), the whole 9 x 64 x 64 weight operand
 // sits in 288 registers of the wave, the A fragments of tap t+1 are read while the MFMAs of tap t run.  Measured
 // (round 3, tools/p64_phases.py, 660 x 49 x 49, forward): NW = 8 155-165 us, wide 186-199 us -- a single wave per
@@ -67,22 +67,19 @@ __device__ __forceinline__ void p64_walk_pixels(const P64Walk& w, const iic_conv
 // Where a tile's 10.3 k cycles go at NW = 8 (matrix pipe alone: 4.6 k): K loop 5.9 k, barrier B 1.6 k, row tables +
 // DMA issue 1.4 k, accumulators -> LDS 1.0 k, waiting for the patch 0.3 k (the DMA is hidden); the residual
 // epilogue of backward-data adds 5.5 k (its 64 KB of residual-gradient / mask loads per tile are exposed).
-// BM = 128 (with NW = 4, wave tiles 64 x 32 as at NW = 8): half-height tiles, TWO workgroups per CU -- the serial
-// phases of one workgroup's tile loop (row tables + DMA issue, barriers, accumulators -> LDS, stores: 40 % of a
-// tile's cycles with the matrix pipe idle, tools/p64_phases.py) run under the other workgroup's K loop.
-template <int ABL, int RED, int NW, int BM>
-__global__ __launch_bounds__(NW * 64) void conv_igemm_p64_kernel(
+template <int ABL, int RED>
+__global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
     const iic_conv_geom g, const bf16_t* __restrict__ in, const unsigned char* __restrict__ wfrag,
     bf16_t* __restrict__ out, float* __restrict__ stats, const bf16_t* __restrict__ res_grad,
     const bf16_t* __restrict__ res_act, int accumulate, int num_tiles, int pb_bytes, int max_tap_off,
     const bf16_t* __restrict__ red_y, const float* __restrict__ red_coef,
     const bf16_t* __restrict__ red_y2, float* __restrict__ red_stats, float* __restrict__ red_stats2,
-    int g_spread, unsigned long long* __restrict__ prof) {
+    unsigned long long* __restrict__ prof) {
   // PROF (ABL bit 8, results CORRECT): wave 0 sums the cycles (s_memtime) its workgroup spends in each phase of
   // the tile loop into prof[blockIdx][8]: wait for patch + barrier A | store of tile t-1 | DMA issue + row
   // tables | K loop | barrier B | accumulators -> LDS; [6] = tiles, [7] = whole loop (tools/p64_phases.py)
   constexpr bool PROF = (ABL & 8) != 0;
-  constexpr bool WIDE = NW * 64 == BM;          // one 64-row group per wave, all 64 couts
+  constexpr int NW = 8, BM = P64_BM;
   constexpr int NWM = BM / 64;                  // 64-row groups of the tile
   constexpr int SC_BYTES = BM * P64_CLD * 2, TAB_ROWS = P64_NTAB * BM;
   unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, t_a = 0, t_b = 0, t_loop = 0;
@@ -95,12 +92,12 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_p64_kernel(
   unsigned short* const s_prow = reinterpret_cast<unsigned short*>(s_pout + TAB_ROWS);
   float* const s_red = reinterpret_cast<float*>(sC);      // [4 wm][2][64], after the last store
 
-  // (WIDE / NWM / SC_BYTES / TAB_ROWS: see the top of the kernel)
+  // (NW / BM / NWM / SC_BYTES / TAB_ROWS: see the top of the kernel)
   constexpr int NTH = NW * 64;
-  constexpr int NCO = WIDE ? 2 : 1;             // 32-wide cout fragments per wave
+  constexpr int NCO = 1;                        // 32-wide cout fragments per wave
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = WIDE ? wave : wave >> 1, wn = WIDE ? 0 : wave & 1;
+  const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, g5 = lane >> 5;
   const int M = g.N * g.MY * g.MX;
   const int in_pixels = g.N * g.in_Hp * g.in_Wp;
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_p64_kernel(
     // over the taps of the K loop below instead: issued in one go, 32 KB of stores per workgroup back up in
     // the CU's memory pipeline at the speed HBM drains them, with the matrix pipe idle meanwhile (measured:
     // compute-only 108 us + stores 34 us + patch reads 22 us = the full 170 us, i.e. no overlap)
-    const bool spread = RED == 0 && g_spread && !res_grad && !res_act && !accumulate;
+    const bool spread = RED == 0 && !res_grad && !res_act && !accumulate;
     if (t > t0 && !(ABL & 2) && !spread)
       igemm_store_tile<P64_BN, BM, NTH, 0, RED, (RED ? 1 : 4)>(sC, s_pout + ((t - 1) & (P64_NTAB - 1)) * BM,
                                                             out, res_grad, res_act, accumulate, P64_BN, 0, tid,
@@ -223,16 +220,10 @@ __global__ __launch_bounds__(NW * 64) void conv_igemm_p64_kernel(
           a[ms][ks] = *reinterpret_cast<const bf16x8*>(sP + base + ((ks << 5) ^ kk));
       }
     };
-    bf16x8 abuf[WIDE ? 2 : 1][2][4];
-    if (WIDE) load_a(0, abuf[0]);
 #pragma unroll
     for (int tap = 0; tap < NTAPS; ++tap) {
-      if (WIDE) {
-        if (tap + 1 < NTAPS) load_a(tap + 1, abuf[(tap + 1) & 1]);     // under this tap's 16 MFMAs
-      } else {
-        load_a(tap, abuf[0]);
-      }
-      bf16x8 (&a)[2][4] = abuf[WIDE ? (tap & 1) : 0];
+      bf16x8 a[2][4];
+      load_a(tap, a);
       if (spread && t > t0 && !(ABL & 2)) {
         constexpr int SIT = BM * 8 / NTH;           // 16-byte pieces per thread and tile (4 | 8)
         constexpr int PER = (SIT + P64_NT - 2) / (P64_NT - 1);
@@ -349,8 +340,6 @@ IIC_HOOK void iic_debug_p64_prof(void* buf) { g_p64_prof = (unsigned long long*)
 #else
 static constexpr unsigned long long* g_p64_prof = nullptr;
 #endif
-IIC_SWITCH(g_p64_spread, 1, iic_debug_p64_spread)   // 1: plain output stores spread over the K loop's taps (see the kernel)
-IIC_SWITCH(g_p64_wide, 0, iic_debug_p64_wide)       // 1: four "wide" waves per workgroup (64 x 64 wave tiles), 0: eight 64 x 32 waves
 IIC_SWITCH(g_p64_grid, 0, iic_debug_p64_grid)       // tests: force a small persistent grid (many tiles per workgroup)
 
 static int p64_num_cus() {
@@ -370,8 +359,8 @@ static int p64_num_cus() {
 static long p64_pb_bytes(const iic_conv_geom* g, int bm = P64_BM) {
   return (((long)(bm == 128 ? g->NP : g->NP256) * 128) + 1023) & ~1023L;
 }
-// Half-height tiles with two workgroups per CU (BM = 128: the kernel is written for it) would let one
-// workgroup's serial phases run under the other's K loop, but do not fit: at layer1 of ClusterNet5g a 128-row
+// Half-height tiles with two workgroups per CU (BM = 128) would let one
+// workgroup's serial phases (40 % of a tile's cycles with the matrix pipe idle) run under the other's K loop, but do not fit: at layer1 of ClusterNet5g a 128-row
 // tile still spans 340 patch rows (42.5 KB; 474 rows at 256), so two double-buffered workgroups need 208 KB.
 
 // used by conv_igemm_bd.hip's dispatcher
@@ -397,24 +386,19 @@ int iic_p64_launch(const iic_conv_geom* g, const void* in, const void* wfrag, vo
   for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
   const int ncu = p64_num_cus();
   const int grid = nt < ncu ? nt : ncu;
-#define P64_LAUNCH3(AB_, RD_, NW_, BM_)                                                                     \
-  do {                                                                                                     \
-    static bool attr = false;                                                                              \
-    if (!attr) {                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_p64_kernel<AB_, RD_, NW_, BM_>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                   \
-      attr = true;                                                                                         \
-    }                                                                                                      \
-    hipLaunchKernelGGL((conv_igemm_p64_kernel<AB_, RD_, NW_, BM_>), dim3(grid), dim3(NW_ * 64), lds,       \
-                       (hipStream_t)stream, *g, (const bf16_t*)in, (const unsigned char*)wfrag,       \
-                       (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act,          \
-                       accumulate, nt, pb, mto, (const bf16_t*)red_y, red_coef,                       \
-                       (const bf16_t*)red_y2, red_stats, red_stats2, g_p64_spread, g_p64_prof);       \
-  } while (0)
-#define P64_LAUNCH2(AB_, RD_)                                              \
-  do {                                                                     \
-    if (g_p64_wide) P64_LAUNCH3(AB_, RD_, 4, 256);                         \
-    else P64_LAUNCH3(AB_, RD_, 8, 256);                                    \
+#define P64_LAUNCH2(AB_, RD_)                                                                          \
+  do {                                                                                                 \
+    static bool attr = false;                                                                          \
+    if (!attr) {                                                                                       \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_p64_kernel<AB_, RD_>),       \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);               \
+      attr = true;                                                                                     \
+    }                                                                                                  \
+    hipLaunchKernelGGL((conv_igemm_p64_kernel<AB_, RD_>), dim3(grid), dim3(512), lds,                  \
+                       (hipStream_t)stream, *g, (const bf16_t*)in, (const unsigned char*)wfrag,   \
+                       (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act,      \
+                       accumulate, nt, pb, mto, (const bf16_t*)red_y, red_coef,                   \
+                       (const bf16_t*)red_y2, red_stats, red_stats2, g_p64_prof);                 \
   } while (0)
 #define P64_LAUNCH(AB_) P64_LAUNCH2(AB_, 0)
   if (red == 1) { P64_LAUNCH2(0, 1); return iic_launch_status(); }

@@ -68,7 +68,6 @@ struct pw_args {
   int M;               // GEMM rows
   int in_pixels;       // N * in_Hp * in_Wp
   int pad_rows;        // 1: g.MP pads the per-image row count (rows >= plane are invalid)
-  int dbg;             // timing experiments (results WRONG): 1 = every B fragment from the same 8 KB (L1-hot)
 };
 
 // B fragment: 16 bytes per lane from (scalar base + per-lane offset + immediate); inline asm so that hipcc's
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
     bf16_t* __restrict__ out, float* __restrict__ stats, const bf16_t* __restrict__ res_grad,
     const bf16_t* __restrict__ res_act, int accumulate, const bf16_t* __restrict__ red_y,
     const float* __restrict__ red_coef, const bf16_t* __restrict__ red_y2, float* __restrict__ red_stats,
-    float* __restrict__ red_stats2, unsigned long long* __restrict__ prof, int stagger) {
+    float* __restrict__ red_stats2, unsigned long long* __restrict__ prof) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -248,14 +247,6 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
   const int n0 = ntile << 7;
   int mtile = mt_lo + kx;
   if (mtile >= mt_hi) return;
-  // Stagger experiment (iic_debug_pw_stagger, cycles): all workgroups start together and do identical work, so the
-  // two that share a CU reach their epilogues -- and the whole chip its HBM burst -- at the same moment.  The
-  // workgroup in an odd threadgroup slot of its CU (HW_ID.TG_ID) starts `stagger` cycles late.
-  const unsigned hw_id = __builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4);
-  if (stagger > 0 && ((hw_id >> 16) & 1u)) {
-    const unsigned long long t_go = __builtin_readcyclecounter() + (unsigned long long)stagger;
-    while (__builtin_readcyclecounter() < t_go) __builtin_amdgcn_s_sleep(32);
-  }
 
   const int v_tapoff = g.tap_off[lane & (IIC_MAX_TAPS - 1)];
   const int v_tapw = g.tap_w[lane & (IIC_MAX_TAPS - 1)];
@@ -266,7 +257,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
   const unsigned boff = (unsigned)(((n0 + wn * 64) >> 5) * 4096 + lane * 16);    // this lane's fragment offset
   auto frag_base = [&](int tap, int chunk) {             // scalar: + 4096 so that all 8 immediates fit [-4096, 3072]
     const int tw = __builtin_amdgcn_readlane(v_tapw, tap);
-    return wfrag + ((A.dbg & 1) ? 0L : ((long)tw * nchunks + chunk) * frag_it) + 4096;
+    return wfrag + ((long)tw * nchunks + chunk) * frag_it + 4096;
   };
 
   // swizzle keys of a tile's patch rows (conv_igemm_bd.hip: key = (D >> 1) & 7, D the dense pixel count)
@@ -609,15 +600,11 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
       for (int j = 0; j < 4; ++j) q[8 + i * 4 + j] = t_line[i][j];
     q[24] = rt0;
     q[25] = __builtin_amdgcn_s_memrealtime();
-    q[7] = (unsigned long long)hw_id | ((unsigned long long)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) << 32);   // HW_ID, XCC_ID
+    q[7] = (unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) << 32);   // HW_ID, XCC_ID
   }
 }
 
 IIC_SWITCH(g_pw_enabled, 1, iic_debug_enable_pw)
-IIC_SWITCH(g_pw_stagger, 0, iic_debug_pw_stagger)             // start offset (cycles) of the workgroups in odd threadgroup slots (A/B)
-IIC_SWITCH(g_pw_min_tiles10, 25, iic_debug_pw_min_tiles10)    // take a launch only if it has >= this many tiles per workgroup slot (x 10)
-IIC_SWITCH(g_pw_dbg, 0, iic_debug_pw_dbg)                     // timing experiment (results WRONG): 1 = every B fragment from the same 8 KB
-IIC_SWITCH(g_pw_one_wg, 0, iic_debug_pw_one_wg)               // 1: pad the LDS request so that only one workgroup fits a CU (A/B)
 #ifdef IIC_DEBUG_HOOKS
 static unsigned long long* g_pw_prof = nullptr;
 IIC_HOOK void iic_debug_pw_prof(void* buf) { g_pw_prof = (unsigned long long*)buf; }
@@ -637,7 +624,8 @@ static int pw_supported_shape(const iic_conv_geom* g);
 int iic_pw_supported(const iic_conv_geom* g) {
   if (!g || !g_pw_enabled || !pw_supported_shape(g)) return 0;
   const long M = igemm_rows_host(g);
-  if (g_pw_min_tiles10 > 0 && ((M + 255) / 256) * (g->Cout / 128) * 10 < (long)g_pw_min_tiles10 * 2 * pw_num_cus()) return 0;
+  // take a launch only if it has at least 2.5 tiles per workgroup slot
+  if (((M + 255) / 256) * (g->Cout / 128) * 10 < 25L * 2 * pw_num_cus()) return 0;
   return 1;
 }
 static int pw_supported_shape(const iic_conv_geom* g) {
@@ -700,10 +688,8 @@ int iic_pw_launch(const iic_conv_geom* g, const void* in, const void* wfrag, voi
   A.M = (int)M;
   A.in_pixels = g->N * g->in_Hp * g->in_Wp;
   A.pad_rows = (g->MP > 0 && g->MP != A.plane) ? 1 : 0;
-  A.dbg = g_pw_dbg;
-  long lds = pw_lds_bytes(g);
+  const long lds = pw_lds_bytes(g);
   const int grid = pw_grid(g, lds);
-  if (g_pw_one_wg) lds = 96 * 1024;
   const int red = red_y ? (red_y2 ? 2 : 1) : 0;
   hipStream_t s = (hipStream_t)stream;
 #define PW_LAUNCH(RD_, PR_)                                                                                   \
@@ -717,7 +703,7 @@ int iic_pw_launch(const iic_conv_geom* g, const void* in, const void* wfrag, voi
     hipLaunchKernelGGL((conv_igemm_pw_kernel<RD_, PR_>), dim3(grid), dim3(PW_THREADS), lds, s, *g, A,         \
                        (const bf16_t*)in, (const unsigned char*)wfrag, (bf16_t*)out, stats,                   \
                        (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, (const bf16_t*)red_y,     \
-                       red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_pw_prof, g_pw_stagger);      \
+                       red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_pw_prof);                    \
   } while (0)
 #ifdef IIC_DEBUG_HOOKS
   if (g_pw_prof) {

@@ -77,23 +77,6 @@ __device__ __forceinline__ bf16x8 wd_frag(uint32_t a0, uint32_t a1) {
   return u.v;
 }
 
-// The same read as inline asm.  hipcc treats the ds_read_tr builtin as a possible reader of LDS that
-// an in-flight LDS-DMA is writing and puts s_waitcnt vmcnt(0) in front of the first one -- right
-// after the next K-tile's DMA was issued, which serialised DMA and MFMA inside the workgroup (the
-// stall profile showed its waves parked 34-39 % of the time).  The compiler cannot see through the
-// asm, so the DMA stays in flight until the counted wait at the top of the next tile; the price is
-// that lgkmcnt has to be waited for by hand (the wait asm in the K loop ties the fragments to it).
-// Opt-in (g_wd_asm): it turned out not to change the kernel's time, see there.
-__device__ __forceinline__ void wd_tr_issue(uint32_t addr, s16x4& d) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(d) : "v"(addr));
-}
-__device__ __forceinline__ bf16x8 wd_pack(const s16x4 h0, const s16x4 h1) {
-  union { bf16x8 v; s16x4 h[2]; } u;
-  u.h[0] = h0;
-  u.h[1] = h1;
-  return u.v;
-}
-
 // Row walkers.  Dense numbering (g.MP == 0 or == MY*MX): (n, y, x) advanced by one K-tile at a time, no
 // divisions.  Padded numbering (g.MP rows per image, a multiple of 256 > MY*MX: large images, so that no tile
 // straddles two images -- iic_amd/geom.py): the walker keeps (n, r = row within the image) in (n, y) and
@@ -148,19 +131,12 @@ __device__ __forceinline__ void wd_walk_pixels(const WdWalk& w, const iic_conv_g
   pout = valid ? (n * g.out_Hp + y * g.ty + g.py) * g.out_Wp + x * g.tx + g.px : -1;
 }
 
-// SWP (round 6, 12-wave form only): the fragments of k-step ks + 1 are read while the MFMAs of k-step ks run (two
-// register sets, compile-time indices) -- a wave no longer parks on lgkmcnt(0) between issuing its 10 transposing
-// reads and its 6 MFMAs eight times per K-tile (r05_pmc_stalls.txt: 35 % of the wave cycles parked, 34 % of the matrix
-// pipe busy).  Three waves per SIMD stay (<= 170 registers), unlike the 4-wave PF form.
-template <int COT, int WD_BM, int NBUF, bool ASMRD, bool PF, bool SWP = false>
-__global__ __launch_bounds__(PF ? 256 : WD_THREADS) void conv_wgrad_dma_kernel(
+template <int COT, int WD_BM, int NBUF>
+__global__ __launch_bounds__(WD_THREADS) void conv_wgrad_dma_kernel(
     const iic_conv_geom g, const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
     float* __restrict__ partials, int nsplit, int num_ktiles, int xb_bytes, int max_tap_off, int abl) {
   constexpr int CS = COT / 64;                  // 32-wide co sub-tiles per wave
-  // PF: 4 fat waves (one per SIMD), each with all 9 taps of its (co half, ci half): 11 operand
-  // fragments feed 18 MFMAs per k-step (22 transposing reads per 18 MFMAs instead of 10 per 6: the
-  // kernel is LDS-read-bound), the next k-step's fragments are read under the current MFMAs.
-  constexpr int NTG = PF ? 1 : 3;               // tap groups = waves / 4
+  constexpr int NTG = 3;                        // tap groups = waves / 4
   constexpr int TPW = 9 / NTG;                  // taps per wave
   constexpr int NTH = 256 * NTG;                // threads
   constexpr int DROW = COT * 2;                 // dY tile row bytes (256 | 128)
@@ -176,7 +152,7 @@ __global__ __launch_bounds__(PF ? 256 : WD_THREADS) void conv_wgrad_dma_kernel(
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tg = PF ? 0 : wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
+  const int tg = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
   const int l31 = lane & 31;
   const int q = lane >> 4, i16 = lane & 15;
   const int ncit = g.Cin >> 6;
@@ -316,117 +292,25 @@ __global__ __launch_bounds__(PF ? 256 : WD_THREADS) void conv_wgrad_dma_kernel(
         rr0[ks] = prow[ks * 16 + trow];
         rr1[ks] = prow[ks * 16 + trow + 4];
       }
-      if (!ASMRD && PF) {
-        // fragments of k-step ks+1 are read while the MFMAs of k-step ks run (two register sets,
-        // the loop is fully unrolled): a wave no longer sits out the LDS round trip of its 10
-        // transposing reads once per k-step
-        // pipeline unit = (k-step, group of 3 taps): dY fragments of the k-step + 3 input fragments.
-        // Unit u+1 is read while unit u's 6 MFMAs run; everything is unrolled (compile-time indices).
-        constexpr int NU = (WD_BM / 16) * 3;
-        bf16x8 fa[2][CS], fb[2][3];
-        auto load_unit = [&](int u) {
-          const int ks = u / 3, gq = u - 3 * ks;
-          if (gq == 0) {
 #pragma unroll
-            for (int c = 0; c < CS; ++c)
-              fa[ks & 1][c] = wd_frag(db + ks * 16 * DROW + aoff[c], db + (ks * 16 + 4) * DROW + aoff[c]);
-          }
+      for (int ks = 0; ks < WD_BM / 16; ++ks) {
+        bf16x8 a[CS], bfr[3];
 #pragma unroll
-          for (int t = 0; t < 3; ++t) {
-            const int toff = __builtin_amdgcn_readlane(v_tapoff, tfirst + 3 * gq + t);
-            const int R0 = rr0[ks] + toff, R1 = rr1[ks] + toff;
-            fb[u & 1][t] = wd_frag(xb + (R0 << 7) + (R0 & 2) * xs32, xb + (R1 << 7) + (R1 & 2) * xs32);
-          }
-        };
-        load_unit(0);
+        for (int c = 0; c < CS; ++c)
+          a[c] = wd_frag(db + ks * 16 * DROW + aoff[c], db + (ks * 16 + 4) * DROW + aoff[c]);
 #pragma unroll
-        for (int u = 0; u < NU; ++u) {
-          if (u + 1 < NU) load_unit(u + 1);
-          __builtin_amdgcn_sched_barrier(0);
-          const int ks = u / 3, gq = u - 3 * ks;
-#pragma unroll
-          for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int c = 0; c < CS; ++c)
-              acc[3 * gq + t][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks & 1][c], fb[u & 1][t],
-                                                                         acc[3 * gq + t][c], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
+        for (int t = 0; t < 3; ++t) {
+          const int toff = __builtin_amdgcn_readlane(v_tapoff, tfirst + t);
+          const int R0 = rr0[ks] + toff, R1 = rr1[ks] + toff;
+          bfr[t] = wd_frag(xb + (R0 << 7) + (R0 & 2) * xs32, xb + (R1 << 7) + (R1 & 2) * xs32);
         }
-      } else if (SWP) {
-        constexpr int NKS = WD_BM / 16;
-        bf16x8 fa[2][CS], fb[2][3];
-        auto load_ks = [&](int ks) {
+        __builtin_amdgcn_sched_barrier(0);   // all 10 transposing reads of the k-step in flight
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
 #pragma unroll
           for (int c = 0; c < CS; ++c)
-            fa[ks & 1][c] = wd_frag(db + ks * 16 * DROW + aoff[c], db + (ks * 16 + 4) * DROW + aoff[c]);
-#pragma unroll
-          for (int t = 0; t < 3; ++t) {
-            const int toff = __builtin_amdgcn_readlane(v_tapoff, tfirst + t);
-            const int R0 = rr0[ks] + toff, R1 = rr1[ks] + toff;
-            fb[ks & 1][t] = wd_frag(xb + (R0 << 7) + (R0 & 2) * xs32, xb + (R1 << 7) + (R1 & 2) * xs32);
-          }
-        };
-        load_ks(0);
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-          if (ks + 1 < NKS) load_ks(ks + 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int c = 0; c < CS; ++c)
-              acc[t][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks & 1][c], fb[ks & 1][t], acc[t][c], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
-  #pragma unroll
-        for (int ks = 0; ks < WD_BM / 16; ++ks) {
-          bf16x8 a[CS], bfr[3];
-          if (ASMRD) {
-            s16x4 ah[CS][2], bh[3][2];
-  #pragma unroll
-            for (int c = 0; c < CS; ++c) {
-              wd_tr_issue(db + ks * 16 * DROW + aoff[c], ah[c][0]);
-              wd_tr_issue(db + (ks * 16 + 4) * DROW + aoff[c], ah[c][1]);
-            }
-  #pragma unroll
-            for (int t = 0; t < 3; ++t) {
-              const int toff = __builtin_amdgcn_readlane(v_tapoff, tfirst + t);
-              const int R0 = rr0[ks] + toff, R1 = rr1[ks] + toff;
-              wd_tr_issue(xb + (R0 << 7) + (R0 & 2) * xs32, bh[t][0]);
-              wd_tr_issue(xb + (R1 << 7) + (R1 & 2) * xs32, bh[t][1]);
-            }
-            // all reads of the k-step in flight; wait, and make every fragment depend on the wait
-            if (CS == 2)
-              asm volatile("s_waitcnt lgkmcnt(0)"
-                           : "+v"(ah[0][0]), "+v"(ah[0][1]), "+v"(ah[CS - 1][0]), "+v"(ah[CS - 1][1]));
-            else
-              asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ah[0][0]), "+v"(ah[0][1]));
-            asm volatile("" : "+v"(bh[0][0]), "+v"(bh[0][1]), "+v"(bh[1][0]), "+v"(bh[1][1]),
-                              "+v"(bh[2][0]), "+v"(bh[2][1]));
-  #pragma unroll
-            for (int c = 0; c < CS; ++c) a[c] = wd_pack(ah[c][0], ah[c][1]);
-  #pragma unroll
-            for (int t = 0; t < 3; ++t) bfr[t] = wd_pack(bh[t][0], bh[t][1]);
-          } else {
-  #pragma unroll
-            for (int c = 0; c < CS; ++c)
-              a[c] = wd_frag(db + ks * 16 * DROW + aoff[c], db + (ks * 16 + 4) * DROW + aoff[c]);
-  #pragma unroll
-            for (int t = 0; t < 3; ++t) {
-              const int toff = __builtin_amdgcn_readlane(v_tapoff, tfirst + t);
-              const int R0 = rr0[ks] + toff, R1 = rr1[ks] + toff;
-              bfr[t] = wd_frag(xb + (R0 << 7) + (R0 & 2) * xs32, xb + (R1 << 7) + (R1 & 2) * xs32);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);   // all 10 transposing reads of the k-step in flight
-  #pragma unroll
-          for (int t = 0; t < 3; ++t)
-  #pragma unroll
-            for (int c = 0; c < CS; ++c)
-              acc[t][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[c], bfr[t], acc[t][c], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+            acc[t][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[c], bfr[t], acc[t][c], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
   }
@@ -472,6 +356,9 @@ __device__ __forceinline__ void wdp_xcd_map(int& tile, int& split) {
   tile = v - split * tiles;
 }
 
+// The transposing read as inline asm.  hipcc treats the ds_read_tr builtin as a possible reader of LDS that an in-flight
+// LDS-DMA is writing and puts s_waitcnt vmcnt(0) in front of the first one, right after the next K-tile's DMA was issued;
+// it cannot see through the asm, so the DMA stays in flight, and lgkmcnt has to be waited for by hand.
 template <int OFF>
 __device__ __forceinline__ void wdp_tr_asm(uint32_t addr, s16x4& d) {
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
@@ -728,13 +615,14 @@ __global__ __launch_bounds__(WD_THREADS) void conv_wgrad_pl_kernel(
   }
 }
 
-// Third form of the loop (iic_debug_wgrad_planar = 3, the default): the planar-patch kernel above with the per-tile work
-// taken off the critical path between the tile barrier and the first MFMA (LAB.md R6.8: of a 144-us launch at layer 3,
-// 61 us are MFMA time, 26 us the k-steps' own inefficiency, 27 us DMA / compute overlap loss, 30 us fixed):
+// Pipelined form of the loop (iic_debug_wgrad_planar = 4; the default for 64-cout tiles): the planar-patch kernel above
+// with the per-tile work taken off the critical path between the tile barrier and the first MFMA (LAB.md R6.8: of a
+// 144-us launch at layer 3, 61 us are MFMA time, 26 us the k-steps' own inefficiency, 27 us DMA / compute overlap loss,
+// 30 us fixed):
 //   * the read addresses of tile kt + 1 are formed at the END of tile kt (their table reads are issued behind the last
 //     k-step's fragment reads and land under its MFMAs), so the first fragment reads issue right after the barrier;
 //   * the next tile's DMA is issued behind those first reads (its scalar address work runs under their LDS latency);
-//   * SWP: the fragment reads of k-step ks + 1 are issued before the MFMAs of k-step ks (two register sets);
+//   * the fragment reads of k-step ks + 1 are issued before the MFMAs of k-step ks (two register sets);
 //   * row tables by an incremental walker (adds and selects; the first two forms recompute four products per row).
 // All transposing reads are inline asm with hand-counted lgkmcnt waits (LDS operations complete in order, so a wait for
 // "at most N outstanding" retires everything but the N youngest whatever else the compiler has in flight).
@@ -752,7 +640,7 @@ __device__ __forceinline__ void wdp_lgkm_wait() {
   asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int COT, int WD_BM, int NBUF, int TXS, bool SWP, int NTAB = WD_NTAB>
+template <int COT, int WD_BM, int NBUF, int TXS, int NTAB = WD_NTAB>
 __global__ __launch_bounds__(WD_THREADS) void conv_wgrad_pl2_kernel(
     const iic_conv_geom g, const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
     float* __restrict__ partials, int nsplit, int num_ktiles, int plane_bytes, int max_tap_off, int abl,
@@ -942,10 +830,10 @@ __global__ __launch_bounds__(WD_THREADS) void conv_wgrad_pl2_kernel(
         asm volatile("" : "+v"(ab[c]));
       }
     };
-    bf16x8 fa[SWP ? 2 : 1][CS], fb[SWP ? 2 : 1][3];
+    bf16x8 fa[2][CS], fb[2][3];
     auto reads = [&](auto KS) {                     // the NRD transposing reads of k-step ks, dY first, then tap by tap
       constexpr int ks = decltype(KS)::value;
-      constexpr int s = SWP ? (ks & 1) : 0;
+      constexpr int s = ks & 1;
 #pragma unroll
       for (int c = 0; c < CS; ++c) fa[s][c] = wdp_frag_pair<ks * 16 * DROW, 4 * DROW, true>(ab[c]);
       fb[s][0] = wdp_frag<0, true>(pb[ks][0], pb[ks][1]);
@@ -954,7 +842,7 @@ __global__ __launch_bounds__(WD_THREADS) void conv_wgrad_pl2_kernel(
     };
     auto mfmas = [&](auto KS, auto YOUNGER) {       // YOUNGER: LDS operations issued after this k-step's reads
       constexpr int ks = decltype(KS)::value;
-      constexpr int s = SWP ? (ks & 1) : 0;
+      constexpr int s = ks & 1;
       constexpr int Y = decltype(YOUNGER)::value;
       constexpr int W0 = Y + 4 > 15 ? 15 : Y + 4, W1 = Y + 2 > 15 ? 15 : Y + 2, W2 = Y > 15 ? 15 : Y;
       if (CS == 2) asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(fa[s][0]), "+v"(fa[s][1]), "+v"(fb[s][0]) : "n"(W0));
@@ -995,22 +883,12 @@ __global__ __launch_bounds__(WD_THREADS) void conv_wgrad_pl2_kernel(
       if (!(abl & 2)) {
         auto step = [&](auto KS) {
           constexpr int ks = decltype(KS)::value;
-          if constexpr (SWP) {
-            if constexpr (ks + 1 < NKS) {
-              reads(std::integral_constant<int, ks + 1>{});
-              mfmas(KS, std::integral_constant<int, NRD>{});
-            } else {
-              prep_issue(kt + 1);
-              mfmas(KS, std::integral_constant<int, NKS>{});
-            }
+          if constexpr (ks + 1 < NKS) {
+            reads(std::integral_constant<int, ks + 1>{});
+            mfmas(KS, std::integral_constant<int, NRD>{});
           } else {
-            if constexpr (ks > 0) reads(KS);
-            if constexpr (ks + 1 < NKS) {
-              mfmas(KS, std::integral_constant<int, 0>{});
-            } else {
-              prep_issue(kt + 1);
-              mfmas(KS, std::integral_constant<int, NKS>{});
-            }
+            prep_issue(kt + 1);
+            mfmas(KS, std::integral_constant<int, NKS>{});
           }
         };
         wdp_unroll<NKS>(step);
@@ -1270,30 +1148,14 @@ static long wd_lds(int np, int cot, int bmk, int nbuf) {
   return nbuf * (wd_xb_bytes(np) + (long)bmk * cot * 2) + WD_TAB_BYTES(bmk) + 64;
 }
 
-// 1: transposing reads as inline asm (see wd_tr_issue).  Measured (tools/conv_perf.py, same process):
-// the compiler's vmcnt(0) disappears from the K-tile loop, the time does not change (layer1 187 ->
-// 181 us, layer2 144 -> 143, layer3 143 -> 145, layer4 169 -> 172): the DMA wait was not what parks
-// the waves.  Default stays on the builtin; the switch is kept for the next experiments.
-IIC_SWITCH(g_wd_asm, 0, iic_debug_wgrad_asm)
-// 1: "fat wave" variant -- 4 waves (one per SIMD) with all 9 taps each, 22 transposing reads per 18
-// MFMAs instead of 10 per 6, the next pipeline unit's fragments read under the current MFMAs.
-// Measured (tools/wgrad_ab.sh, per launch incl. the reduce pass): layer2-4 within 2 % of the 12-wave
-// kernel, layer1 28 % slower -- 27 % less LDS-read traffic buys nothing, i.e. the kernel is not
-// LDS-read-bound as round 1 assumed.  Default 0 (12 waves).
 // timing ablation (WRONG results): 1 = no DMA after the prologue (compute-only time of the K loop); planar kernel also
 // 2 = no k-steps (DMA + bookkeeping only), 4 = no per-tile wait / barrier
 IIC_SWITCH(g_wd_ablate, 0, iic_debug_wgrad_ablate)
-IIC_SWITCH(g_wd_prefetch, 0, iic_debug_wgrad_prefetch)
-// 1: 12-wave kernel with the next k-step's fragments read under the current k-step's MFMAs (template SWP).  Measured
-// (tools/wgrad_swp_ab.py, profiles/r06_wgrad_swp_ab.txt): bit-identical, 1.01-1.03 x per launch in isolation (layer 1
-// 215.5 -> 209.1 us, layer 3 159.1 -> 155.4), and 36.31 / 36.26 -> 36.38 / 36.34 ms per step interleaved on one box: the
-// wave-level lgkmcnt park was not what sets the step.  Default 0; instantiated in the instrumented library only.
-IIC_SWITCH(g_wd_swp, 0, iic_debug_wgrad_swp)
 // K-loop form where the planar layout fits: 0 = first generation; 1 = planar patch, builtin transposing reads; 2 = planar,
-// inline-asm reads (no compiler-inserted vmcnt(0) between the next tile's DMA and this tile's reads); 3 = pipelined form
-// (conv_wgrad_pl2_kernel); 4 = pipelined + software-pipelined k-steps; 5 (default) = 4 for 64-cout tiles (115 registers: no
-// spills; layer 1: 172 -> 164 us), 2 for 128-cout tiles (form 4 spills there and measured 6 % slower, form 3 equal to form 2:
-// tools/wgrad_pl_ab.py, profiles/r06_wgrad_planar_ab.txt).
+// inline-asm reads (no compiler-inserted vmcnt(0) between the next tile's DMA and this tile's reads); 4 = pipelined form
+// with software-pipelined k-steps (conv_wgrad_pl2_kernel); 5 (default) = 4 for 64-cout tiles (115 registers: no spills;
+// layer 1: 172 -> 164 us), 2 for 128-cout tiles (form 4 spills there and measured 6 % slower: tools/wgrad_pl_ab.py,
+// profiles/r06_wgrad_planar_ab.txt).
 IIC_SWITCH(g_wd_planar, 5, iic_debug_wgrad_planar)
 IIC_SWITCH(g_wd_enabled, 1, iic_debug_enable_wgrad_dma)     // 0: register-staged kernel, 1: DMA kernel, 3: force 64-pixel K-tiles
 
@@ -1331,9 +1193,8 @@ static int wd_config(const iic_conv_geom* g, int* bmk, int* nbuf) {
 // kernels need not fit the first generation's and vice versa): 128-pixel tiles with 2 buffers where they fit (if need be
 // with the 4-tile table ring: SegmentationNet10a c3 / c4 fit 160 KB to the byte that way), else the 64-pixel ring.
 // A wave's three taps must be one tap row with a fixed x step (1, or 2 = dilation 2); dY row offsets must fit 32 bits.
-// Padded row numbering (large images): allowed (g_wd_planar_padded) -- LAB.md R6.12 / profiles/r06_wgrad_seg_ab.txt have
-// the per-layer A/B against the register-staged kernel that used to keep these layers (Potsdam c3 / c4: 1.28-1.30 x).
-IIC_SWITCH(g_wd_planar_padded, 1, iic_debug_wgrad_planar_padded)
+// Padded row numbering (large images) is allowed: LAB.md R6.12 / profiles/r06_wgrad_seg_ab.txt have the per-layer A/B
+// against the register-staged kernel that used to keep these layers (Potsdam c3 / c4: 1.28-1.30 x).
 static int wdp_txs(const iic_conv_geom* g) {
   if (g->ntaps != 9) return 0;
   int txs = g->tap_off[1] - g->tap_off[0];
@@ -1347,7 +1208,6 @@ static int wdp_txs(const iic_conv_geom* g) {
 // span of span + max tap offset + 1 rows -- for dilated convolutions and wide images the rows between the tap rows are
 // most of that span (SegmentationNet10a c5 at Potsdam: 500 rows per 64-pixel tile contiguous, 3 x 80 banded).  Only
 // where the bands do not overlap (tap-row distance >= band) and only for the 128-cout kernel.
-IIC_SWITCH(g_wd_banded, 1, iic_debug_wgrad_banded)
 static int wdp_band_rows(const iic_conv_geom* g, int np, int txs) {
   int mto = 0;
   for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
@@ -1360,8 +1220,6 @@ static int wdp_config(const iic_conv_geom* g, int* bmk, int* nbuf, int* ntab, in
   const int txs = wdp_txs(g);
   if (!txs) return 0;
   if ((long)g->N * g->out_Hp * g->out_Wp * g->Cout * 2 >= (1L << 32)) return 0;
-  const bool padded = g->MP > 0 && g->MP != g->MY * g->MX;
-  if (padded && !g_wd_planar_padded && g_wd_enabled != 3) return 0;
   const int cot = (g->Cout % 128 == 0) ? 128 : 64;
   const long lim = 160 * 1024;
   if (g_wd_enabled != 3 && (g->MP <= 0 || g->MP % 128 == 0)) {
@@ -1373,7 +1231,7 @@ static int wdp_config(const iic_conv_geom* g, int* bmk, int* nbuf, int* ntab, in
       if (wdp_lds(g->NP64, cot, 64, nb, 8) <= lim) { *bmk = 64; *nbuf = nb; *ntab = 8; return 1; }
     // banded 64-pixel ring: 3 bands of (64 + wraps + 2 txs + 1) rows instead of the contiguous span
     const int bstride = g->tap_off[3] - g->tap_off[0];
-    if (g_wd_banded && cot == 128 && bstride > 0 && g->tap_off[6] - g->tap_off[3] == bstride) {
+    if (cot == 128 && bstride > 0 && g->tap_off[6] - g->tap_off[3] == bstride) {
       const int bp = wdp_band_rows(g, g->NP64, txs);
       if (bp <= bstride && 3 * bp < g->NP64) {
         for (int nb = 4; nb >= 2; --nb)
@@ -1395,12 +1253,10 @@ static int wdp_config(const iic_conv_geom* g, int* bmk, int* nbuf, int* ntab, in
 }
 
 // Block-tiled kernel (conv_wgrad_b2d_kernel): block shape by exhaustive search -- the fewest 128-row tiles per image, then
-// the smallest patch.  0 = not applicable.  mode (g_wd_b2d): 2 (default) = wherever it applies (every layer of
-// profiles/r06_wgrad_b2d_ab.txt is faster on it: 1.08-1.42 x), 1 = only where the planar kernels would need the 64-pixel
-// ring or bands, 0 = off.
-IIC_SWITCH(g_wd_b2d, 2, iic_debug_wgrad_b2d)
+// the smallest patch.  0 = not applicable.  Taken wherever it applies: every layer of profiles/r06_wgrad_b2d_ab.txt is
+// faster on it (1.08-1.42 x), including those the planar kernels keep on their 128-pixel contiguous layout.
 static int wdb_config(const iic_conv_geom* g, wdb_args* A) {
-  if (!g_wd_b2d || !g_wd_enabled || g->ntaps != 9 || g->Cin % 64 != 0 || g->Cout % 128 != 0) return 0;
+  if (!g_wd_enabled || g->ntaps != 9 || g->Cin % 64 != 0 || g->Cout % 128 != 0) return 0;
   if (g->sy != 1 || g->sx != 1 || g->ty != 1 || g->tx != 1) return 0;
   const int txs = wdp_txs(g);
   if (!txs) return 0;
@@ -1435,10 +1291,6 @@ static int wdb_config(const iic_conv_geom* g, wdb_args* A) {
   A->NPR = A->PW * (A->bh + 2 * drow);
   A->plane_bytes = (int)wdp_plane_bytes(A->NPR);
   A->num_tiles = (int)(best_tiles * g->N);
-  if (g_wd_b2d == 1) {                             // only where the planar kernels fall off their 128-pixel contiguous layout
-    int bmk, nbuf, ntab, band;
-    if (wdp_config(g, &bmk, &nbuf, &ntab, &band) && bmk == 128 && band == 0) return 0;
-  }
   return 1;
 }
 
@@ -1511,31 +1363,30 @@ int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, 
                        dim3(WD_THREADS), ldsp, s, *g, (const bf16_t*)x, (const bf16_t*)dy,      \
                        partials, nsplit, kt, plane, mto, g_wd_ablate, pband, bstride);          \
   } while (0)
-#define WDP2_LAUNCH3(COT_, BMK_, NBUF_, TXS_, SWP_, NTAB_)                                       \
+#define WDP2_LAUNCH3(COT_, BMK_, NBUF_, TXS_, NTAB_)                                             \
   do {                                                                                          \
     static bool attr = false;                                                                   \
     if (!attr) {                                                                                \
       (void)hipFuncSetAttribute(                                                                \
-          reinterpret_cast<const void*>(&conv_wgrad_pl2_kernel<COT_, BMK_, NBUF_, TXS_, SWP_, NTAB_>), \
+          reinterpret_cast<const void*>(&conv_wgrad_pl2_kernel<COT_, BMK_, NBUF_, TXS_, NTAB_>), \
           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                              \
       attr = true;                                                                              \
     }                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_pl2_kernel<COT_, BMK_, NBUF_, TXS_, SWP_, NTAB_>), grid,     \
+    hipLaunchKernelGGL((conv_wgrad_pl2_kernel<COT_, BMK_, NBUF_, TXS_, NTAB_>), grid,           \
                        dim3(WD_THREADS), ldsp, s, *g, (const bf16_t*)x, (const bf16_t*)dy,      \
                        partials, nsplit, kt, plane, mto, g_wd_ablate, pband, bstride);          \
   } while (0)
 #ifdef IIC_DEBUG_HOOKS
 #define WDP_LAUNCH2(COT_, BMK_, NBUF_, TXS_, NTAB_)                                              \
   do {                                                                                          \
-    if (g_wd_planar == 4 || (g_wd_planar == 5 && COT_ == 64)) WDP2_LAUNCH3(COT_, BMK_, NBUF_, TXS_, true, NTAB_); \
-    else if (g_wd_planar == 3) WDP2_LAUNCH3(COT_, BMK_, NBUF_, TXS_, false, NTAB_);             \
+    if (g_wd_planar == 4 || (g_wd_planar == 5 && COT_ == 64)) WDP2_LAUNCH3(COT_, BMK_, NBUF_, TXS_, NTAB_); \
     else if (g_wd_planar == 1) WDP_LAUNCH3(COT_, BMK_, NBUF_, TXS_, false, NTAB_);              \
     else WDP_LAUNCH3(COT_, BMK_, NBUF_, TXS_, true, NTAB_);                                     \
   } while (0)
 #else      /* the product library instantiates the default forms only */
 #define WDP_LAUNCH2(COT_, BMK_, NBUF_, TXS_, NTAB_)                                              \
   do {                                                                                          \
-    if (COT_ == 64) WDP2_LAUNCH3(64, BMK_, NBUF_, TXS_, true, NTAB_);                           \
+    if (COT_ == 64) WDP2_LAUNCH3(64, BMK_, NBUF_, TXS_, NTAB_);                                 \
     else WDP_LAUNCH3(128, BMK_, NBUF_, TXS_, true, NTAB_);                                      \
   } while (0)
 #endif
@@ -1557,31 +1408,17 @@ int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, 
   const int np = bmk == 64 ? g->NP64 : g->NP;
   const int xb = (int)wd_xb_bytes(np);
   const long lds = wd_lds(np, cot, bmk, nbuf);
-#define WD_LAUNCH2(COT_, BMK_, NBUF_, ASM_, PF_, SWP_)                                           \
+#define WD_LAUNCH(COT_, BMK_, NBUF_)                                                             \
   do {                                                                                          \
     static bool attr = false;                                                                   \
     if (!attr) {                                                                                \
-      (void)hipFuncSetAttribute(                                                                \
-          reinterpret_cast<const void*>(&conv_wgrad_dma_kernel<COT_, BMK_, NBUF_, ASM_, PF_, SWP_>), \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                              \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma_kernel<COT_, BMK_, NBUF_>), \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
       attr = true;                                                                              \
     }                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_dma_kernel<COT_, BMK_, NBUF_, ASM_, PF_, SWP_>), grid,       \
-                       dim3(PF_ ? 256 : WD_THREADS), lds, s, *g, (const bf16_t*)x,              \
-                       (const bf16_t*)dy,                                                       \
-                       partials, nsplit, kt, xb, mto, g_wd_ablate);                             \
+    hipLaunchKernelGGL((conv_wgrad_dma_kernel<COT_, BMK_, NBUF_>), grid, dim3(WD_THREADS), lds, s, *g, \
+                       (const bf16_t*)x, (const bf16_t*)dy, partials, nsplit, kt, xb, mto, g_wd_ablate); \
   } while (0)
-#ifdef IIC_DEBUG_HOOKS
-#define WD_LAUNCH(COT_, BMK_, NBUF_)                                                             \
-  do {                                                                                          \
-    if (g_wd_asm) WD_LAUNCH2(COT_, BMK_, NBUF_, true, false, false);                            \
-    else if (g_wd_prefetch) WD_LAUNCH2(COT_, BMK_, NBUF_, false, true, false);                  \
-    else if (g_wd_swp) WD_LAUNCH2(COT_, BMK_, NBUF_, false, false, true);                       \
-    else WD_LAUNCH2(COT_, BMK_, NBUF_, false, false, false);                                    \
-  } while (0)
-#else
-#define WD_LAUNCH(COT_, BMK_, NBUF_) WD_LAUNCH2(COT_, BMK_, NBUF_, false, false, (g_wd_swp != 0))
-#endif
   if (bmk == 64 && nbuf == 4) {
     if (cot == 128) WD_LAUNCH(128, 64, 4); else WD_LAUNCH(64, 64, 4);
   } else if (bmk == 64 && nbuf == 3) {

@@ -75,7 +75,7 @@ def _all_reduce_now(t, grp):
   polling its completion event for a while after it finished -- if that stream starts a graph capture in the meantime
   (the warm-up step of a CapturedPairStep runs on the very streams it then captures on), HIP refuses the query
   (hipErrorCapturedEvent: 'operation not permitted on an event last recorded in a capturing stream') and the watchdog
-  takes the process down.  Seen in about one of ten one-rank RCCL runs (round 6, tools/r06_rccl_flaky.sh)."""
+  takes the process down.  Seen in about one of ten one-rank RCCL runs (round 6)."""
   _count("all_reduce")
   if dist.get_backend(grp) == "nccl":
     dist.all_reduce(t, op=dist.ReduceOp.SUM, group=grp, async_op=True).wait()

@@ -477,12 +477,11 @@ def test_conv_backward_weight(case, use_tr):
 
 
 def _wgrad_dma(mode):
-  """mode 1 / 3 / 0 as iic_debug_enable_wgrad_dma; 11: mode 1 with the inline-asm transposing reads."""
-  hook("iic_debug_wgrad_asm", 1 if int(mode) == 11 else 0)
-  hook("iic_debug_enable_wgrad_dma", 1 if int(mode) == 11 else int(mode))
+  """mode 1 / 3 / 0 as iic_debug_enable_wgrad_dma."""
+  hook("iic_debug_enable_wgrad_dma", int(mode))
 
 
-@pytest.mark.parametrize("dma", [1, pytest.param(11, marks=HOOKS), pytest.param(3, marks=HOOKS), pytest.param(0, marks=HOOKS)])
+@pytest.mark.parametrize("dma", [1, pytest.param(3, marks=HOOKS), pytest.param(0, marks=HOOKS)])
 @pytest.mark.parametrize("case,nsplit", [((64, 64, 3, 1, 1, 2, 49), 2), ((128, 128, 3, 1, 1, 20, 25), 3),
                                          ((512, 512, 3, 1, 1, 6, 7), 1), ((64, 64, 3, 1, 1, 5, 13), 1)])
 def test_conv_backward_weight_long_k_ranges(case, nsplit, dma):
@@ -537,8 +536,8 @@ def test_conv_backward_weight_padded_row_numbering(cin, cout, H, dil, dma):
     (64, 64, 200, 1, 2, 2, 3),       # 64-pixel ring, padded row numbering, 64-cout tiles
     (64, 128, 200, 1, 2, 2, 3)])     # 64-pixel ring, padded row numbering, 128-cout tiles
 def test_weight_gradient_k_loop_forms_are_bit_identical(cin, cout, H, dil, N, nsplit, dma):
-  """conv_wgrad_dma.hip holds five forms of the K loop behind iic_debug_wgrad_planar (0 = first generation, 1 / 2 =
-  planar patch with builtin / inline-asm reads, 3 / 4 = pipelined, 5 = the default choice): same work split, same k
+  """conv_wgrad_dma.hip holds four forms of the K loop behind iic_debug_wgrad_planar (0 = first generation, 1 / 2 =
+  planar patch with builtin / inline-asm reads, 4 = pipelined, 5 = the default choice): same work split, same k
   order, same MFMA sequence => the same bits; and the result against F.conv2d's weight gradient."""
   from iic_amd import geom, ops
   K, P = 3, max(dil, 1) if H < 200 else 3
@@ -554,14 +553,14 @@ def test_weight_gradient_k_loop_forms_are_bit_identical(cin, cout, H, dil, N, ns
   out = {}
   _wgrad_dma(dma)
   try:
-    for form in (0, 1, 2, 3, 4, 5):
+    for form in (0, 1, 2, 4, 5):
       hook("iic_debug_wgrad_planar", form)
       out[form] = ops.conv_wgrad(g, xp, dyp, K * K, use_tr=True, nsplit=nsplit).clone()
     torch.cuda.synchronize()
   finally:
     hook("iic_debug_wgrad_planar", 5)
     _wgrad_dma(1)
-  for form in (1, 2, 3, 4, 5):
+  for form in (1, 2, 4, 5):
     assert torch.equal(out[form], out[0]), form
   got = out[5].view(cout, cin, K, K).cpu()
   scale = ref.abs().max().item()

@@ -5,7 +5,7 @@ thread trace: the ATT decoder library is not part of this image).  The kernel's 
 phase boundaries; this tool launches one layer, decodes the stamps and prints where a tile's cycles go,
 how the workgroups of a launch are packed onto the CUs, and what the MFMA loop would need alone.
 
-python tools/bd_timeline.py [--layer l2|l3|l4|all] [--stagger CYCLES_PER_TAP] [--red]
+python tools/bd_timeline.py [--layer l2|l3|l4|all] [--red]
 """
 import argparse
 import ctypes
@@ -26,7 +26,7 @@ LAYERS = {
 }
 
 
-def run_layer(L, key, N, stagger, red, iters):
+def run_layer(L, key, N, red, iters):
   name, cin, cout, H = LAYERS[key]
   dev = torch.device("cuda:0")
   spec = geom.ConvSpec(cin, cout, 3, 1, 1)
@@ -46,7 +46,6 @@ def run_layer(L, key, N, stagger, red, iters):
   tiles = (M + 255) // 256 * (cout // 128)
   slots = L.iic_debug_bd_prof_slots()
   buf = torch.zeros(tiles * slots, device=dev, dtype=torch.int64)
-  L.iic_debug_bd_stagger(stagger)
 
   def launch():
     ops.conv_igemm(g, x, pw[0], y, **kw)
@@ -73,7 +72,6 @@ def run_layer(L, key, N, stagger, red, iters):
   torch.cuda.synchronize()
   L.iic_debug_set_ablate(0)
   L.iic_debug_bd_prof(None)
-  L.iic_debug_bd_stagger(0)
   r = buf.view(tiles, slots).cpu().numpy().astype(np.int64)
   t0, t1, t2, t3, t4, t5, bsum, nb, hw, tix, rt = [r[:, i] for i in range(11)]
   base = t0.min()      # (s_memtime is NOT synchronised between XCDs: only per-CU differences below are meaningful)
@@ -83,7 +81,7 @@ def run_layer(L, key, N, stagger, red, iters):
   span = t5.max() - base
   rts = (rt.max() - rt.min()) / 100.0    # us between first and last end stamp (100 MHz)
   ghz = span / max(us_prof, 1e-9) / 1e3
-  print("== %s  N=%d  stagger=%d cyc/tap  %s" % (name, N, stagger, "fused reduction" if red else "fwd + stats"))
+  print("== %s  N=%d  %s" % (name, N, "fused reduction" if red else "fwd + stats"))
   print("   launch %.1f us (%.0f TF/s); PROF build %.1f us; %d tiles; kernel span %d cycles => ~%.2f GHz "
         "(s_memrealtime span of end stamps %.1f us)" % (us_plain, flops / us_plain / 1e6, us_prof, tiles, span, ghz, rts))
   ph = [("setup (row table, keys)", t1 - t0), ("prologue loads (B ring + patch DMA + barrier)", t2 - t1),
@@ -155,17 +153,15 @@ def main():
   ap.add_argument("--layer", default="all")
   ap.add_argument("--n", type=int, default=660)
   ap.add_argument("--iters", type=int, default=10)
-  ap.add_argument("--stagger", type=str, default="0")
   ap.add_argument("--red", action="store_true")
   a = ap.parse_args()
   L = ctypes.CDLL(_lib.LIB_PATH)
   L.iic_debug_bd_prof.argtypes = [ctypes.c_void_p]
   _lib.lib()
   for key in (LAYERS if a.layer == "all" else [a.layer]):
-    for stg in [int(v) for v in a.stagger.split(",")]:
-      run_layer(L, key, a.n, stg, False, a.iters)
+    run_layer(L, key, a.n, False, a.iters)
     if a.red:
-      run_layer(L, key, a.n, 0, True, a.iters)
+      run_layer(L, key, a.n, True, a.iters)
 
 
 if __name__ == "__main__":

@@ -66,11 +66,9 @@ def main():
   ap.add_argument("--bm", type=int, default=0)
   ap.add_argument("--frag", type=int, default=1, help="1: weights-direct kernel where supported (A/B column)")
   ap.add_argument("--no-wgrad", action="store_true")
-  ap.add_argument("--bd-dma", type=int, default=1, help="weights-direct kernel: 1 = LDS-DMA patch loads, 0 = register-staged")
   ap.add_argument("--frag-ablate", type=str, default="", help="comma list of ablation codes for the frag kernel")
   ap.add_argument("--cold", action="store_true", help="also time every kernel with cold caches (a 1-GB fill in front of each launch)")
   ap.add_argument("--no-pw", action="store_true", help="persistent kernel off: every launch on conv_igemm_bd_kernel (the ablation codes' baseline)")
-  ap.add_argument("--dense-key-ab", action="store_true", help="A/B the weights-direct kernel's swizzle key (dense pixel count vs raw index)")
   a = ap.parse_args()
   dev = torch.device("cuda:0")
   N = a.n
@@ -79,11 +77,6 @@ def main():
     from iic_amd import _lib
     ctypes.CDLL(_lib.LIB_PATH).iic_debug_enable_pw(0)
     print("persistent kernel off")
-  if not a.bd_dma:
-    import ctypes
-    from iic_amd import _lib
-    ctypes.CDLL(_lib.LIB_PATH).iic_debug_bd_dma(0)
-    print("weights-direct kernel: register-staged patch loads")
   if a.bm:
     import ctypes
     from iic_amd import _lib
@@ -123,24 +116,11 @@ def main():
       L.iic_debug_enable_wgrad_dma(3)     # 64-pixel K-tiles, 3-4 buffers
       t_w0 = timeit(lambda: ops.conv_wgrad(gf, x, dy, K * K, True), a.iters)
       L.iic_debug_enable_wgrad_dma(1)
-      L.iic_debug_wgrad_asm(0)            # ds_read_tr builtin: compiler waits for the DMA before it
-      t_w1 = timeit(lambda: ops.conv_wgrad(gf, x, dy, K * K, True), a.iters)
-      L.iic_debug_wgrad_asm(1)
-      t_w2 = timeit(lambda: ops.conv_wgrad(gf, x, dy, K * K, True), a.iters)
-    extra = "" if a.no_wgrad else " | wgrad(dma 64-px ring) %7.1f us | builtin tr reads %7.1f us, asm again %7.1f us" % (t_w0, t_w1, t_w2)
+    extra = "" if a.no_wgrad else " | wgrad(dma 64-px ring) %7.1f us" % t_w0
     if a.frag:
       if ops.frag_supported(gf):
         t2 = timeit(lambda: ops.conv_igemm(gf, x, pw[0], y, stats=st), a.iters)
         extra += " | frag fwd %7.1f us %7.1f TF/s" % (t2, flops / t2 / 1e6)
-        if a.dense_key_ab:
-          import ctypes
-          from iic_amd import _lib
-          L = ctypes.CDLL(_lib.LIB_PATH)
-          L.iic_debug_bd_dense_key(0)
-          t4 = timeit(lambda: ops.conv_igemm(gf, x, pw[0], y, stats=st), a.iters)
-          L.iic_debug_bd_dense_key(1)
-          t5 = timeit(lambda: ops.conv_igemm(gf, x, pw[0], y, stats=st), a.iters)
-          extra += " | raw-index key %7.1f us, dense again %7.1f us" % (t4, t5)
         for code in [int(c) for c in a.frag_ablate.split(",") if c]:
           import ctypes
           from iic_amd import _lib

@@ -148,12 +148,7 @@ def stl_5g_twohead(bn=700, sz=64):
 if __name__ == "__main__":
   ap = argparse.ArgumentParser()
   ap.add_argument("--which", default="mnist,cifar,stl2h,potsdam,coco")
-  ap.add_argument("--bd-one-wg", type=int, default=0)
   a = ap.parse_args()
-  if a.bd_one_wg:
-    import ctypes
-    from iic_amd import _lib
-    ctypes.CDLL(_lib.LIB_PATH).iic_debug_bd_one_wg(1)
   if "mnist" in a.which:
     bn, t = mnist_6c_twohead()
     print("MNIST 24x24 ClusterNet6cTwoHead batch %d (head A + head B steps): %.2f ms -> %.0f paired-images/s" % (bn, 1e3 * t, bn / t))

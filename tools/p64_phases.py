@@ -3,7 +3,7 @@ Where a tile's cycles go in the persistent 64 -> 64 convolution (conv_igemm_p64_
 ClusterNet5g): the kernel's PROF build (iic_debug_set_ablate(8), results unchanged) sums, per workgroup, the
 s_memtime cycles of each phase of its tile loop.
 
-python tools/p64_phases.py [--n 660] [--wide 0|1] [--spread 0|1] [--bwd]
+python tools/p64_phases.py [--n 660] [--bwd]
 """
 import argparse
 import ctypes
@@ -24,12 +24,10 @@ PH = ["wait patch + barrier A", "store of tile t-1", "DMA issue + row tables", "
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--n", type=int, default=660)
-  ap.add_argument("--wide", type=int, default=0)
-  ap.add_argument("--spread", type=int, default=1)
   ap.add_argument("--bwd", action="store_true", help="backward-data with the residual gradient + ReLU mask epilogue")
   args = ap.parse_args()
   L = _lib.lib()
-  for name in ("iic_debug_p64_prof", "iic_debug_p64_wide", "iic_debug_p64_spread", "iic_debug_set_ablate"):
+  for name in ("iic_debug_p64_prof", "iic_debug_set_ablate"):
     getattr(L, name).restype = None
   L.iic_debug_p64_prof.argtypes = [ctypes.c_void_p]
   dev = torch.device("cuda:0")
@@ -46,8 +44,6 @@ def main():
   if args.bwd:
     rg = torch.randn_like(x)
     kw = dict(res_grad=rg, res_act=x, premask=True)
-  L.iic_debug_p64_wide(args.wide)
-  L.iic_debug_p64_spread(args.spread)
   ncu = 2 * torch.cuda.get_device_properties(0).multi_processor_count
   buf = torch.zeros(ncu * 8, device=dev, dtype=torch.int64)
 
@@ -78,15 +74,13 @@ def main():
   per_tile = q[:, :6].sum(0) / tiles.sum()
   loop = q[:, 7].sum() / tiles.sum()
   flops = 2.0 * N * H * H * C * C * 9
-  print("layer1 3x3 64->64 @49, %d images, %s, wide=%d spread=%d: %.1f us per launch (%.0f TF/s); with stamps %.1f us"
-        % (N, "backward-data + residual epilogue" if args.bwd else "forward", args.wide, args.spread, us_plain,
+  print("layer1 3x3 64->64 @49, %d images, %s: %.1f us per launch (%.0f TF/s); with stamps %.1f us"
+        % (N, "backward-data + residual epilogue" if args.bwd else "forward", us_plain,
            flops / us_plain / 1e6, us_prof))
   print("%d workgroups, %.1f tiles each; cycles per tile (s_memtime, mean over all tiles): %.0f" % (len(q), tiles.mean(), loop))
   for n, v in zip(PH, per_tile):
     print("  %-34s %8.0f  %5.1f %%" % (n, v, 100 * v / loop))
-  mf = 72 * 32 * (2 if not args.wide else 2) * (1 if not args.wide else 1)
-  print("  (matrix pipe alone: %d MFMAs per wave and tile x 32 cycles x %d waves per SIMD = %d cycles)"
-        % (72 if not args.wide else 144, 2 if not args.wide else 1, 72 * 32 * 2))
+  print("  (matrix pipe alone: 72 MFMAs per wave and tile x 32 cycles x 2 waves per SIMD = %d cycles)" % (72 * 32 * 2))
 
 
 if __name__ == "__main__":

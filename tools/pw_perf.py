@@ -1,7 +1,7 @@
 """A/B of the persistent weights-direct conv kernel (csrc/conv_igemm_pw.hip) against conv_igemm_bd_kernel at the
 north-star shapes: outputs bit-identical?, statistics equal to rounding?, us / TF/s per launch class (forward + BN
-statistics, backward-data, backward-data with the fused BatchNorm-backward reduction), the same with ONE workgroup
-per CU (a wave alone on its SIMD), and the per-phase cycle sums of the PROF build.
+statistics, backward-data, backward-data with the fused BatchNorm-backward reduction), and the per-phase cycle sums of
+the PROF build.
   python tools/pw_perf.py [--n 660] [--iters 20] [--only l3]"""
 import argparse
 import ctypes
@@ -50,14 +50,11 @@ def main():
   ap.add_argument("--iters", type=int, default=20)
   ap.add_argument("--only", type=str, default="")
   ap.add_argument("--no-prof", action="store_true")
-  ap.add_argument("--prof-stagger", type=int, default=0, help="start offset used in the PROF run")
-  ap.add_argument("--dbg", type=int, default=0, help="iic_debug_pw_dbg for the PROF run and an extra timing column")
-  ap.add_argument("--stagger", type=str, default="", help="comma list of start offsets (cycles) of the odd-slot workgroups to time")
   a = ap.parse_args()
   dev = torch.device("cuda:0")
   L = _lib.lib()
   N = a.n
-  print("%-22s %-10s | %9s %8s | %9s %8s | %s" % ("layer", "class", "bd us", "TF/s", "pw us", "TF/s", "pw alone (1 WG/CU) us / bd alone us"))
+  print("%-22s %-10s | %9s %8s | %9s %8s" % ("layer", "class", "bd us", "TF/s", "pw us", "TF/s"))
   for name, cin, cout, H in LAYERS:
     if a.only and a.only not in name:
       continue
@@ -112,38 +109,17 @@ def main():
         for use_pw in (0, 1):
           L.iic_debug_enable_pw(use_pw)
           t.setdefault(use_pw, []).append(timeit(lambda: run(cls, scratch, st, sums), a.iters))
-      L.iic_debug_enable_pw(1)
-      L.iic_debug_pw_one_wg(1)
-      t_alone = timeit(lambda: run(cls, scratch, st, sums), a.iters)
-      L.iic_debug_pw_one_wg(0)
-      L.iic_debug_enable_pw(0)
       tb, tp = min(t[0]), min(t[1])
-      print("%-22s %-10s | %9.1f %8.1f | %9.1f %8.1f | %7.1f | out identical %s (nonzero %.2f) stats rel %.1e sums rel %.1e | runs bd %s pw %s" % (
-        name, cls, tb, flops / tb / 1e6, tp, flops / tp / 1e6, t_alone, same, nz, dstat, dsum,
+      print("%-22s %-10s | %9.1f %8.1f | %9.1f %8.1f | out identical %s (nonzero %.2f) stats rel %.1e sums rel %.1e | runs bd %s pw %s" % (
+        name, cls, tb, flops / tb / 1e6, tp, flops / tp / 1e6, same, nz, dstat, dsum,
         ["%.1f" % v for v in t[0]], ["%.1f" % v for v in t[1]]))
       L.iic_debug_enable_pw(1)
-      if a.stagger:
-        row = []
-        for sg in [int(v) for v in a.stagger.split(",")]:
-          L.iic_debug_pw_stagger(sg)
-          row.append("%d: %.1f" % (sg, timeit(lambda: run(cls, scratch, st, sums), a.iters)))
-        L.iic_debug_pw_stagger(0)
-        print("    stagger (cycles: us)  " + "   ".join(row))
       if not a.no_prof and cls != "bwd":
         slots = L.iic_debug_pw_prof_slots()
         grid = L.iic_debug_pw_grid(ctypes.byref(gf if cls == "fwd+stats" else gb))
         buf = torch.zeros(grid * slots, device=dev, dtype=torch.int64)
         L.iic_debug_pw_prof(ctypes.c_void_p(buf.data_ptr()))
-        L.iic_debug_pw_stagger(a.prof_stagger)
-        L.iic_debug_pw_dbg(a.dbg)
         run(cls, scratch, st, sums)
-        if a.dbg:
-          print("    dbg %d: %.1f us (2 WG/CU)" % (a.dbg, timeit(lambda: run(cls, scratch, st, sums), a.iters)))
-          L.iic_debug_pw_one_wg(1)
-          print("    dbg %d: %.1f us (1 WG/CU)" % (a.dbg, timeit(lambda: run(cls, scratch, st, sums), a.iters)))
-          L.iic_debug_pw_one_wg(0)
-        L.iic_debug_pw_dbg(0)
-        L.iic_debug_pw_stagger(0)
         torch.cuda.synchronize()
         L.iic_debug_pw_prof(None)
         p = buf.view(grid, slots).cpu().numpy().astype(np.float64)
