@@ -1,0 +1,225 @@
+// GPU-side paired augmentation for the segmentation scripts: what the training __getitem__ of the
+// reference's Potsdam and COCO-Stuff datasets returns, for a whole batch in one launch.
+//
+// Replaces, per sample,
+//   /root/reference/code/datasets/segmentation/potsdam.py:95-216    (_Potsdam._prepare_train)
+//   /root/reference/code/datasets/segmentation/cocostuff.py:104-230 (_Coco._prepare_train)
+// which run on the host, one image at a time:
+//   pad_if_too_small + pad_and_or_crop (code/utils/segmentation/transforms.py:23-88): sources smaller
+//     than S are centred in zeros (int(x / 2.) arithmetic), then an S x S window is cut;
+//   img1 = the crop as uint8; img2 = torchvision ColorJitter of its RGB part (never of IR,
+//     potsdam.py:147-156) -- PIL arithmetic, aug_jitter.h;
+//   custom_greyscale_numpy (transforms.py:7-20) unless no_sobel: grey appended after RGB
+//     (include_rgb) or instead of it; IR, when the source has it, comes last;
+//   astype(float32) / 255. (the 256-entry table of the clustering augmenter);
+//   torch.flip(img2, dims=[2]) and the negated top row of affine2_to_1 (potsdam.py:194-202);
+//   mask_img1: ones (Potsdam) or _filter_label's mask (cocostuff.py:137-141) as a 256-entry table
+//     of the fine label, 255 standing for -1; padded label pixels are fine-label 0.
+// The random affine of img2 (transforms.py:91-128) is NOT in this kernel: the host warps the batch
+// with iic_affine_warp_fwd afterwards and folds the mirror into the warp's matrix (flip bit 1 below).
+//
+// Grey is OpenCV's 8-bit COLOR_RGB2GRAY, not PIL's "L": restated here from OpenCV 3.x's source
+// (fixed point, 14 fractional bits), NOT compared against a cv2 binary -- cv2 is not installable
+// where this is built and tested.  Newer OpenCV builds use a 15-bit variant that can differ by one
+// grey level.  The formula lives in seg_grey() alone.
+//
+// Shape: a streaming kernel, one workgroup per sample.  A thread owns four consecutive output x of
+// one row: it reads the four source pixels once for both views and writes every planar fp32
+// channel with one 16-byte store (S % 4 == 0).  The only LDS is the reduction of ColorJitter's
+// contrast mean (the rounded mean of the L image the preceding ops produced), which needs one
+// extra pass over the crop for the samples whose op list holds contrast.  No atomics: two calls
+// with the same parameters give identical bytes.
+#include "common.h"
+#include "aug_jitter.h"
+#include "../../include/iic_hip.h"
+
+#pragma clang fp contract(off)
+
+#define SEG_IP IIC_SEG_AUG_IPARAMS   // src, x0, y0, flip bits, nops, op[4], hue_delta, -, -
+#define SEG_FP IIC_SEG_AUG_FPARAMS   // brightness, contrast, saturation, (hue), affine2_to_1 before the flip [6]
+#define SEG_THREADS 512
+
+// OpenCV 3.x RGB2Gray for 8-bit images (modules/imgproc/src/color.cpp: yuv_shift = 14, R2Y = 4899,
+// G2Y = 9617, B2Y = 1868, CV_DESCALE rounds to nearest)
+#define SEG_GREY_R 4899
+#define SEG_GREY_G 9617
+#define SEG_GREY_B 1868
+#define SEG_GREY_SHIFT 14
+__device__ __forceinline__ int seg_grey(int r, int g, int b) {
+  return (r * SEG_GREY_R + g * SEG_GREY_G + b * SEG_GREY_B + (1 << (SEG_GREY_SHIFT - 1))) >> SEG_GREY_SHIFT;
+}
+
+// ops [first, last) of the shuffled ColorJitter list on one pixel; opsw holds op o in bits 4o..4o+3
+__device__ __forceinline__ void seg_jitter(int& r, int& g, int& b, int opsw, int first, int last, float f_b,
+                                           float f_c, float f_s, int mean, int hdelta) {
+  for (int o = first; o < last; ++o) {
+    const int op = (opsw >> (4 * o)) & 15;
+    if (op == 0) {
+      r = aug_blend(0, r, f_b); g = aug_blend(0, g, f_b); b = aug_blend(0, b, f_b);
+    } else if (op == 1) {
+      r = aug_blend(mean, r, f_c); g = aug_blend(mean, g, f_c); b = aug_blend(mean, b, f_c);
+    } else if (op == 2) {
+      const int L = aug_luma(r, g, b);
+      r = aug_blend(L, r, f_s); g = aug_blend(L, g, f_s); b = aug_blend(L, b, f_s);
+    } else {
+      aug_hue(r, g, b, hdelta);
+    }
+  }
+}
+
+// one source pixel of the padded image at crop position (y, x): zeros outside the source
+template <int CS>
+__device__ __forceinline__ void seg_load(const uint8_t* __restrict__ im, int sy, int sx, int H, int W, int& r,
+                                         int& g, int& b, int& ir) {
+  r = g = b = ir = 0;
+  if (im != nullptr && sy >= 0 && sy < H && sx >= 0 && sx < W) {
+    const uint8_t* p = im + ((long)sy * W + sx) * CS;
+    if (CS == 4) {
+      const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
+      r = v & 255; g = (v >> 8) & 255; b = (v >> 16) & 255; ir = v >> 24;
+    } else {
+      r = p[0]; g = p[1]; b = p[2];
+    }
+  }
+}
+
+// MODE 0: no_sobel, RGB(+IR); 1: RGB, grey(, IR); 2: grey(, IR)
+template <int CS, int MODE>
+__global__ __launch_bounds__(SEG_THREADS) void seg_augment_kernel(
+    const uint8_t* __restrict__ imgs, const uint8_t* __restrict__ labels, const uint8_t* __restrict__ table, int B,
+    int H, int W, int pad_y, int pad_x, const int* __restrict__ iparams, const float* __restrict__ fparams, int S,
+    const float* __restrict__ lut, float* __restrict__ img1, float* __restrict__ img2, uint8_t* __restrict__ mask,
+    float* __restrict__ aff) {
+  __shared__ int s_red[SEG_THREADS / 64];
+  constexpr int C = (MODE == 0 ? 3 : (MODE == 1 ? 4 : 1)) + (CS == 4 ? 1 : 0);
+  constexpr int CG = MODE == 1 ? 3 : 0;              // grey's channel (IR, when present, is C - 1)
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const int* ip = iparams + (long)n * SEG_IP;
+  const float* fp = fparams + (long)n * SEG_FP;
+  const int src = ip[0], x0 = ip[1] - pad_x, y0 = ip[2] - pad_y, flip = ip[3] & 1, defer = (ip[3] >> 1) & 1;
+  int nops = ip[4];
+  nops = nops < 0 ? 0 : (nops > 4 ? 4 : nops);
+  const int opsw = (ip[5] & 3) | ((ip[6] & 3) << 4) | ((ip[7] & 3) << 8) | ((ip[8] & 3) << 12);
+  const int hdelta = ip[9] & 255;
+  const float f_b = fp[0], f_c = fp[1], f_s = fp[2];
+  const bool valid = src >= 0 && src < B;           // an index outside the dataset reads as a black image
+  const uint8_t* im = valid ? imgs + (long)src * H * W * CS : nullptr;
+  const uint8_t* lb = (labels != nullptr && valid) ? labels + (long)src * H * W : nullptr;
+  const int Q = S >> 2, nquads = S * Q;
+
+  // ---- affine2_to_1: the given rows, top row negated when flipped (potsdam.py:202)
+  if (tid < 6) {
+    const float v = fp[4 + tid];
+    aff[(long)n * 6 + tid] = (flip && tid < 3) ? v * -1.f : v;
+  }
+
+  // ---- contrast: rounded mean of the L image after the ops that precede it
+  int cpos = -1;
+  for (int o = 0; o < nops; ++o)
+    if (((opsw >> (4 * o)) & 15) == 1 && cpos < 0) cpos = o;
+  int mean = 0;
+  if (cpos >= 0) {                                   // uniform over the workgroup
+    int part = 0;
+    for (int q = tid; q < nquads; q += SEG_THREADS) {
+      const int y = q / Q, xq = (q - y * Q) << 2;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int r, g, b, ir;
+        seg_load<CS>(im, y0 + y, x0 + xq + j, H, W, r, g, b, ir);
+        seg_jitter(r, g, b, opsw, 0, cpos, f_b, f_c, f_s, 0, hdelta);
+        part += aug_luma(r, g, b);
+      }
+    }
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) part += __shfl_xor(part, sft, 64);
+    if ((tid & 63) == 0) s_red[tid >> 6] = part;
+    __syncthreads();
+    int tot = 0;
+#pragma unroll
+    for (int w = 0; w < SEG_THREADS / 64; ++w) tot += s_red[w];
+    mean = (int)((double)tot / (double)(S * S) + 0.5);
+  }
+
+  // ---- both views
+  const long plane = (long)S * S;
+  float* o1 = img1 + (long)n * C * plane;
+  float* o2 = img2 + (long)n * C * plane;
+  uint8_t* om = mask + (long)n * plane;
+  const bool mirror = flip && !defer;
+  for (int q = tid; q < nquads; q += SEG_THREADS) {
+    const int y = q / Q, xq = (q - y * Q) << 2;
+    f32x4 v1[C], v2[C];
+    uint32_t mk = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int r, g, b, ir;
+      const int sy = y0 + y, sx = x0 + xq + j;
+      seg_load<CS>(im, sy, sx, H, W, r, g, b, ir);
+      int m = 1;
+      if (labels != nullptr) {
+        const int l = (lb != nullptr && sy >= 0 && sy < H && sx >= 0 && sx < W) ? (int)lb[(long)sy * W + sx] : 0;
+        m = table[l];
+      }
+      mk |= (uint32_t)(m & 255) << (8 * j);
+      int r2 = r, g2 = g, b2 = b;
+      seg_jitter(r2, g2, b2, opsw, 0, nops, f_b, f_c, f_s, mean, hdelta);
+      if (MODE != 2) {
+        v1[0][j] = lut[r]; v1[1][j] = lut[g]; v1[2][j] = lut[b];
+        v2[0][j] = lut[r2]; v2[1][j] = lut[g2]; v2[2][j] = lut[b2];
+      }
+      if (MODE != 0) {
+        v1[CG][j] = lut[seg_grey(r, g, b)];
+        v2[CG][j] = lut[seg_grey(r2, g2, b2)];
+      }
+      if (CS == 4) {
+        v1[C - 1][j] = lut[ir];
+        v2[C - 1][j] = lut[ir];
+      }
+    }
+    const long off1 = (long)y * S + xq;
+    const long off2 = (long)y * S + (mirror ? S - 4 - xq : xq);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      *reinterpret_cast<f32x4*>(o1 + c * plane + off1) = v1[c];
+      const f32x4 m2 = {v2[c][3], v2[c][2], v2[c][1], v2[c][0]};     // torch.flip(img2, dims=[2]) within the run
+      *reinterpret_cast<f32x4*>(o2 + c * plane + off2) = mirror ? m2 : v2[c];
+    }
+    *reinterpret_cast<uint32_t*>(om + off1) = mk;
+  }
+}
+
+extern "C" {
+
+int iic_seg_augment(const void* imgs_u8, int B, int H, int W, int Cs, const void* labels_u8,
+                    const void* relevance, const int* iparams, const float* fparams, int N, int S,
+                    int no_sobel, int include_rgb, const float* lut, float* img1, float* img2,
+                    void* mask_img1, float* affine2_to_1, void* stream) {
+  if (!imgs_u8 || !iparams || !fparams || !lut || !img1 || !img2 || !mask_img1 || !affine2_to_1) return IIC_ERR_ARG;
+  if (B <= 0 || N <= 0 || S <= 0 || H <= 0 || W <= 0) return IIC_ERR_ARG;
+  if ((labels_u8 == nullptr) != (relevance == nullptr)) return IIC_ERR_ARG;
+  if (Cs != 3 && Cs != 4) return IIC_ERR_UNSUPPORTED;
+  if (S % 4 != 0 || S > 4096 || H > 16384 || W > 16384) return IIC_ERR_UNSUPPORTED;
+  // pad_if_too_small (transforms.py:34-41): centre of the padded image minus half the source, int(x / 2.)
+  const int new_h = H > S ? H : S, new_w = W > S ? W : S;
+  const int pad_y = new_h / 2 - H / 2, pad_x = new_w / 2 - W / 2;     // 0 for a side that is not padded
+  const int mode = no_sobel ? 0 : (include_rgb ? 1 : 2);
+  hipStream_t s = (hipStream_t)stream;
+#define SEG_LAUNCH(CS_, MODE_)                                                                            \
+  hipLaunchKernelGGL((seg_augment_kernel<CS_, MODE_>), dim3(N), dim3(SEG_THREADS), 0, s,                  \
+                     (const uint8_t*)imgs_u8, (const uint8_t*)labels_u8, (const uint8_t*)relevance, B, H, \
+                     W, pad_y, pad_x, iparams, fparams, S, lut, img1, img2, (uint8_t*)mask_img1,          \
+                     affine2_to_1)
+  if (Cs == 3) {
+    if (mode == 0) SEG_LAUNCH(3, 0);
+    else if (mode == 1) SEG_LAUNCH(3, 1);
+    else SEG_LAUNCH(3, 2);
+  } else {
+    if (mode == 0) SEG_LAUNCH(4, 0);
+    else if (mode == 1) SEG_LAUNCH(4, 1);
+    else SEG_LAUNCH(4, 2);
+  }
+#undef SEG_LAUNCH
+  return iic_launch_status();
+}
+
+}  // extern "C"

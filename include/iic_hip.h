@@ -470,6 +470,40 @@ int iic_augment(const void* imgs_u8, int B, int H, int W, int channels, const in
                 const int* bounds, const int* kk, int S, const float* lut, float* out,
                 int include_rgb, const float* norm, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Paired augmentation of the segmentation datasets on the GPU -- replaces the per-sample host
+ * pipeline of the training __getitem__:
+ *   code/datasets/segmentation/potsdam.py:95-216    (_Potsdam._prepare_train)
+ *   code/datasets/segmentation/cocostuff.py:104-230 (_Coco._prepare_train)
+ * with pad_if_too_small / pad_and_or_crop / custom_greyscale_numpy of
+ * code/utils/segmentation/transforms.py:7-88, for a whole batch in one launch.  The random affine
+ * of the second view (transforms.py:91-128) is a following iic_affine_warp_fwd of img2.
+ * imgs_u8    uint8 [B][H][W][Cs], Cs = 3 (RGB) or 4 (RGB + IR), resident in HBM.  With
+ *            pre_scale_all these are the pre-scaled, truncated images (prepared once by the caller).
+ * labels_u8  uint8 [B][H][W] fine labels, 255 = the reference's -1, or NULL (Potsdam: mask of ones);
+ * relevance  uint8 [256]: _filter_label's mask (cocostuff.py:629-657, :734-760) as a function of the
+ *            fine label; NULL exactly when labels_u8 is.  Padded label pixels are fine-label 0.
+ * iparams    int32 [N][12]: source image, crop origin x0, y0 IN THE PADDED image (sources smaller
+ *            than S are centred in zeros, int(x / 2.) arithmetic), flip bits (bit 0: img2 is flipped --
+ *            the top row of affine2_to_1 is negated and the pixels are mirrored; bit 1: leave the
+ *            mirroring of the pixels to the caller's warp), n_ops, op[4] (0 brightness, 1 contrast,
+ *            2 saturation, 3 hue -- in application order), hue shift (uint8 wrap), 2 unused.
+ * fparams    float [N][10]: factor of brightness, contrast, saturation, hue (not read: iparams[9]),
+ *            then affine2_to_1 [2][3] before the flip (the identity without random affine).
+ * lut        float [256] = v / 255 as torch computes it.
+ * img1, img2 float [N][C][S][S]: no_sobel: R,G,B(,IR); else include_rgb: R,G,B,grey(,IR); else
+ *            grey(,IR) -- the layouts sobel_process(..., using_IR) expects.  ColorJitter (PIL
+ *            arithmetic, bit-exact) touches img2's RGB only.  grey = OpenCV 3.x's 8-bit RGB2GRAY,
+ *            (R 4899 + G 9617 + B 1868 + 8192) >> 14, restated from its source (not PIL's L).
+ * mask_img1  uint8 [N][S][S]; affine2_to_1 float [N][2][3].  S % 4 == 0 (16-byte stores).
+ * ------------------------------------------------------------------------------- */
+#define IIC_SEG_AUG_IPARAMS 12
+#define IIC_SEG_AUG_FPARAMS 10
+int iic_seg_augment(const void* imgs_u8, int B, int H, int W, int Cs, const void* labels_u8,
+                    const void* relevance, const int* iparams, const float* fparams, int N, int S,
+                    int no_sobel, int include_rgb, const float* lut, float* img1, float* img2,
+                    void* mask_img1, float* affine2_to_1, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
