@@ -138,7 +138,7 @@ class _ConvHolder(object):
     # (one operand set per branch: a side branch must not read operands whose layout kernels
     # were enqueued on the other stream)
     w = self.conv.weight
-    b = ops.BRANCH[0]
+    b = ops.current_branch()
     key = (w.data_ptr(), w._version, _WEIGHTS_EPOCH[0])
     ent = self._wbranch.get(b)                  # [key, PreppedWeights]
     if ent is not None and ent[0] == key:
@@ -166,7 +166,7 @@ class _ConvHolder(object):
     return g
 
   def stats(self, device, which="fwd"):
-    key = (str(device), which, ops.BRANCH[0])
+    key = (str(device), which, ops.current_branch())
     s = self._stats.get(key)
     if s is None:
       s = ops.new_stats(self.spec.cout, device)
@@ -215,7 +215,7 @@ class _StemFn(torch.autograd.Function):
     ops.stem_apply_pool(x, wd, coef, out)
     ctx.mod = mod
     ctx.training = training
-    ctx.branch, ctx.pt_dtype = ops.BRANCH[0], ops.PT_DTYPE[0]
+    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
     ctx.save_for_backward(x, w, gamma, coef, out)
     return out
 
@@ -267,7 +267,7 @@ class _StemF32Fn(torch.autograd.Function):
     a = ops.bn_apply(y, coef, ops.pt_alloc(N, H, W, 64, 1, dev), N, H, W, 1, 64, relu=True)
     Ho, Wo = H // 2 + 1, W // 2 + 1
     out = ops.f32_maxpool_s2p1_fwd(a, ops.pt_alloc(N, Ho, Wo, 64, 1, dev), N, H, W, 64)
-    ctx.mod, ctx.training, ctx.branch, ctx.pt_dtype = mod, training, ops.BRANCH[0], ops.PT_DTYPE[0]
+    ctx.mod, ctx.training, ctx.branch, ctx.pt_dtype = mod, training, ops.current_branch(), ops.PT_DTYPE[0]
     ctx.dims = (N, C, H, W)
     ctx.save_for_backward(xp, y, a, coef, gamma)
     return out
@@ -346,7 +346,7 @@ class _BlockFn(torch.autograd.Function):
 
     if need_grad:
       ctx.blk = blk
-      ctx.branch, ctx.pt_dtype = ops.BRANCH[0], ops.PT_DTYPE[0]
+      ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
       ctx.dims = (N, H, W, Ho, Wo, Cin, planes)
       ctx.bn_batch = (_bn_training(blk.bn1) and _bn_training(blk.bn2))
       # (set by the trunk for the duration of its sequential forward, see PREMASK)
@@ -508,7 +508,7 @@ class _AvgPoolFn(torch.autograd.Function):
   def forward(ctx, x, premask):
     N, Hp, Wp, C = x.shape
     ctx.dims = (N, Hp - 2, Wp - 2, C)
-    ctx.branch, ctx.pt_dtype = ops.BRANCH[0], ops.PT_DTYPE[0]
+    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
     ctx.premask = bool(premask)
     if premask:
       ctx.save_for_backward(x)      # its ReLU mask is applied to the gradient here (PREMASK)
@@ -537,7 +537,7 @@ class _HeadsFn(torch.autograd.Function):
     probs = ops.softmax_fwd(logits, N * H, k)
     ctx.save_for_backward(feats, Wcat, probs)
     ctx.hk = (H, k)
-    ctx.branch, ctx.pt_dtype = ops.BRANCH[0], ops.PT_DTYPE[0]   # (the K-split GEMM workspace is per branch)
+    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]   # (the K-split GEMM workspace is per branch)
     return probs.view(N, H, k)
 
   @ops.branch_backward

@@ -57,7 +57,7 @@ class _SegHeadFn(torch.autograd.Function):
     ctx.save_for_backward(x if fused else Fm, W2, probs)
     ctx.fused = fused
     ctx.meta = (tuple(x.shape), P, S, Hw, Ww, off, k)
-    ctx.branch, ctx.pt_dtype = ops.BRANCH[0], x.dtype
+    ctx.branch, ctx.pt_dtype = ops.current_branch(), x.dtype
     return out
 
   @ops.branch_backward

@@ -84,7 +84,7 @@ class _StageFn(torch.autograd.Function):
     need_grad = any(ctx.needs_input_grad)
     if need_grad:
       ctx.st = st
-      ctx.branch, ctx.pt_dtype = ops.BRANCH[0], ops.PT_DTYPE[0]
+      ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
       ctx.dims = (N, H, W, Ho, Wo)
       ctx.training = training
       ctx.dout_prereduced = False
@@ -181,7 +181,7 @@ class _FlattenFn(torch.autograd.Function):
   def forward(ctx, x, P):
     N, Hp, Wp, C = x.shape
     ctx.meta = (tuple(x.shape), P)
-    ctx.branch, ctx.pt_dtype = ops.BRANCH[0], x.dtype
+    ctx.branch, ctx.pt_dtype = ops.current_branch(), x.dtype
     out = torch.empty((N, C, Hp - 2 * P, Wp - 2 * P), dtype=torch.float32, device=x.device)
     out.copy_(x[:, P:Hp - P, P:Wp - P, :].permute(0, 3, 1, 2))
     return out.view(N, -1)

@@ -20,7 +20,7 @@ optimiser.param_groups) keeps working with no device-side learning rate, and a s
 captured for (the last, smaller batch of an epoch) simply runs eager.
 
 Works under iic_amd.ops.auto_branch (the first forward of a step on a side stream): the BatchNorm
-running-statistic updates a branch forward postpones to the join (ops._DEFERRED_RUNNING) are recorded at
+running-statistic updates a branch forward postpones to the join (BranchContext.deferred_running) are recorded at
 capture time and re-queued at every replay; both positions re-lay their own bf16 weight operands inside
 their forward graph (one operand set per branch, ops / archs.cluster._ConvHolder.weights).
 
@@ -41,6 +41,7 @@ import weakref
 import torch
 
 from . import ops
+from .branches import context
 from .archs import cluster as _cl
 
 WARMUP = 2          # eager occurrences of a key before it is captured
@@ -65,7 +66,8 @@ class _ViewGraph(object):
     self.cap.wait_stream(cur)
     pool = torch.cuda.graph_pool_handle()
     mode = "thread_local" if torch.distributed.is_available() and torch.distributed.is_initialized() else "global"
-    n_def = len(ops._DEFERRED_RUNNING)
+    bc = context()
+    n_def = len(bc.deferred_running)
     _cl.bump_weights_epoch()                 # the bf16 operand re-layout belongs INSIDE the forward graph
     # The captured forward sees the parameters through leaf ALIASES created on the capture stream (same
     # storage): the parameters' own AccumulateGrad nodes live on the stream the script's warm-up steps
@@ -75,31 +77,28 @@ class _ViewGraph(object):
     with torch.cuda.stream(self.cap):
       self.leaves = [p.detach().requires_grad_(True) for p in self.params]
     self.g_f = torch.cuda.CUDAGraph()
-    ops._CAPTURE_PROXIES[0] = {id(p): q for p, q in zip(self.params, self.leaves)}
+    bc.capture_proxies = {id(p): q for p, q in zip(self.params, self.leaves)}
     # Resource namespace (PT buffer pool, statistic accumulators, scratch, weight operands are keyed by
-    # ops.BRANCH): the forward and the backward of a view are captured back to back, so the pool believes the
+    # the current branch): the forward and the backward of a view are captured back to back, so the pool believes the
     # view's saved activations are free again when the NEXT position is captured -- although at replay the
     # other view's forward runs between this view's forward and backward.  Positions that share a real
     # branch (one-stream runs) therefore get a namespace of their own.
-    prev_branch = ops.BRANCH[0]
-    ops.BRANCH[0] = res_branch
     # no cyclic garbage collection while a stream is capturing: a collected tensor / graph would be freed by a HIP call
     # that is illegal under capture (torch.cuda.graph collects once on entry, but a capture allocates plenty itself)
     gc_was = gc.isenabled()
     gc.disable()
     try:
-      with torch.cuda.graph(self.g_f, pool=pool, stream=self.cap, capture_error_mode=mode):
+      with bc.as_branch(res_branch), torch.cuda.graph(self.g_f, pool=pool, stream=self.cap, capture_error_mode=mode):
         with torch.enable_grad():
           out = fwd(mod, self.static_in, *args, **kwargs)
     finally:
-      ops._CAPTURE_PROXIES[0] = None
-      ops.BRANCH[0] = prev_branch
+      bc.capture_proxies = None
       if gc_was:
         gc.enable()
     self.outs, self.out_type = _flat(out)
     # running-statistic updates this forward postponed to the join (branch mode): the same (static) tensors
     # at every replay
-    self.deferred = list(ops._DEFERRED_RUNNING[n_def:])
+    self.deferred = bc.deferred_running[n_def:]
     self.gouts = [torch.zeros_like(o) for o in self.outs]
     self.g_b = torch.cuda.CUDAGraph()
     gc.disable()
@@ -174,12 +173,13 @@ class _GraphedFn(torch.autograd.Function):
   def forward(ctx, vg, x, *params):
     vg.static_in.copy_(x)
     vg.g_f.replay()
+    bc = context()
     if not vg.first:                         # (at capture the forward itself queued them)
-      ops._DEFERRED_RUNNING.extend(vg.deferred)
+      bc.deferred_running.extend(vg.deferred)
     vg.first = False
     ctx.vg = vg
     # the stream the script itself is on (inside ops.branch: the stream that forked): its optimiser will read the gradients
-    ctx.caller_stream = ops._BRANCH_MAIN[0] or torch.cuda.current_stream()
+    ctx.caller_stream = bc.branch_main or torch.cuda.current_stream()
     return tuple(o.detach() for o in vg.static_outs)       # fresh tensor objects over the static storage
 
   @staticmethod
@@ -255,9 +255,10 @@ def _state(mod):
 
 
 def eligible(mod, x, args, kwargs):
+  bc = context()
   return (ops.GRAPH_FORWARD[0] and mod.training and torch.is_grad_enabled() and torch.is_tensor(x) and x.is_cuda
           and not x.requires_grad and not args and set(kwargs) <= {"head"}
-          and (ops.BRANCH[0] == 0 or ops.BRANCH[0] in ops._NO_PROXY_BRANCHES)    # (parameters, not leaf aliases)
+          and (bc.branch == 0 or bc.branch in bc.no_proxy_branches)    # (parameters, not leaf aliases)
           and ops.PT_DTYPE[0] is ops.BF16 and not torch.cuda.is_current_stream_capturing())
 
 
@@ -294,7 +295,7 @@ def plan(mod, x, kwargs, branch):
     clash = any(k[:4] == key[:4] and k[4] < pos and r == branch for k, r in st["res"].items())
     res = st["res"][key] = (100 + pos) if clash else branch
     if clash:
-      ops._NO_PROXY_BRANCHES.add(res)        # a namespace, not a stream branch: parameters stay themselves
+      context().no_proxy_branches.add(res)        # a namespace, not a stream branch: parameters stay themselves
   vg = st["graphs"].get(key)
   if vg is not None and vg is not _FAILED and _sig_changed(mod, st, vg):
     # the module's storage moved (.cpu() / .cuda() / .to()): every graph of this module is stale
@@ -324,11 +325,11 @@ def forward(fwd, mod, x, args, kwargs, pl=None):
   """Called by ops.auto_branch's wrapper for an eligible training forward (inside the branch context when
   there is one).  Returns the forward's result, from a replayed graph when this key has been captured."""
   if pl is None:
-    pl = plan(mod, x, kwargs, ops.BRANCH[0])
+    pl = plan(mod, x, kwargs, ops.current_branch())
   st, key, res, vg = pl.st, pl.key, pl.res, pl.vg
 
   def eager():
-    main = ops._BRANCH_MAIN[0]
+    main = context().branch_main
     if main is not None and torch.cuda.current_stream() != main:
       # A capture failed INSIDE a forked branch (ops.auto_branch entered it because a captured view was planned).  Eager
       # launches do not run on the side stream (their gradient accumulation would cross the two streams): leave it --
@@ -341,18 +342,12 @@ def forward(fwd, mod, x, args, kwargs, pl=None):
     return eager_here()
 
   def eager_here():
-    if res == ops.BRANCH[0]:
+    with context().as_branch(res):
       return fwd(mod, x, *args, **kwargs)
-    prev = ops.BRANCH[0]
-    ops.BRANCH[0] = res
-    try:
-      return fwd(mod, x, *args, **kwargs)
-    finally:
-      ops.BRANCH[0] = prev
   if pl.mode == "eager":
     return eager()
   if pl.mode == "capture":
-    n_def = len(ops._DEFERRED_RUNNING)
+    n_def = len(context().deferred_running)
     try:
       vg = _ViewGraph(fwd, mod, x, args, kwargs, res)
     except Exception as e:                   # noqa: BLE001 -- never take a run down over an optimisation
@@ -362,7 +357,7 @@ def forward(fwd, mod, x, args, kwargs, pl=None):
       # Undo what the aborted capture left on the host: running-statistic updates it queued (their kernels never
       # ran), operand sets whose re-layout was only recorded (a fresh weights epoch makes every holder re-lay
       # them eagerly), and the step position (the capture bumped the epoch once already).
-      del ops._DEFERRED_RUNNING[n_def:]
+      del context().deferred_running[n_def:]
       _cl.bump_weights_epoch()
       st["epoch"] = _epoch(mod)
       return eager()

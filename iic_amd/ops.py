@@ -2,534 +2,22 @@
 
 PyTorch is plumbing here: it owns device memory and the HIP stream; every arithmetic op on
 the hot path is a kernel of libiic_hip.so.  All wrappers enqueue on torch's current stream.
+
+The two-stream execution state lives in iic_amd.branches and the PT buffer pool / scratch buffers in
+iic_amd.pool; their public names are re-exported here.
 """
 import ctypes
 import os
-import threading
-import weakref
 
 import torch
 
 from . import _lib
 from ._lib import IIC_STAT_STRIPES, check, lib, ptr, stream_ptr
-
-BF16 = torch.bfloat16
-F32 = torch.float32
-
-
-# ------------------------------------------------------------------------------------
-# Branches: two independent forwards of a step (net(all_imgs), net(all_imgs_tf):
-# cluster_sobel.py:238-239) can run on two HIP streams -- as two parallel branches of the captured
-# step graph -- so that the tail of one view's kernel is filled by the other view's next kernel
-# (measured: 42.6 -> 38.2 ms for the two forward+backward passes, tools/graph_probes.py dual_branch_probe).
-# Everything the kernels share through HBM is therefore keyed by the branch index: PT buffers,
-# BatchNorm statistic accumulators, split-K / stem scratch, the bf16 weight operands.  A branch's
-# autograd Functions remember their branch (ctx.branch) and restore it in backward, where the
-# engine already runs them on the stream they were recorded on.
-#   with ops.branch():            # fork: side stream waits for the current one
-#     xo = net(all_imgs)          # the view that comes FIRST is enqueued on the side stream
-#   xt = net(all_imgs_tf)         # main stream, concurrently
-#   ops.join()                    # the current stream waits for the side stream (the losses and
-#                                 # the optimiser call it themselves if it is still pending)
-# Inside a branch: parameters are seen through per-branch leaf aliases (`pv`), so that gradient
-# accumulation of shared parameters never synchronises the branches (the optimiser adds the two
-# gradient sets, iic_amd.optim.Adam); while a branch is pending, BatchNorm running-statistic
-# updates of BOTH views are postponed to the join and applied there in call order -- the order a
-# sequential run would have used (bn_finalize -> _DEFERRED_RUNNING).
-# ------------------------------------------------------------------------------------
-class BranchContext(object):
-  """Everything the two-stream execution keeps between calls, in ONE object per thread (round 6; until round 5 these
-  were nine module-level lists / dicts, which is the style that produced round 5's read-before-join race): the branch
-  the calling code is on, the side streams, the per-branch leaf aliases of the parameters, the forks not joined yet
-  and the running-statistic updates they postponed.  One process drives one device (the data-parallel design: one
-  process per GPU), so a context is per thread, and its streams are keyed by device inside.  The autograd engine runs
-  backward nodes on its own threads: every Function records its branch at forward time (ctx.branch) and
-  `branch_backward` restores it there, so a backward thread never depends on the forward thread's context.
-  The module-level names below (BRANCH[0], _PENDING_JOIN, ...) are views of the calling thread's context."""
-  __slots__ = ("branch", "streams", "proxies", "deferred_running", "pending_join", "branch_main", "no_proxy_branches",
-               "capture_proxies", "solo_first")
-
-  def __init__(self):
-    self.branch = 0                 # BRANCH[0]: 0 = the caller's stream, >= 1 = a side branch / resource namespace
-    self.streams = {}               # _BRANCH_STREAM: (device, branch index) -> side stream
-    self.proxies = {}               # _PROXIES: id(param) -> (param, {branch: leaf alias sharing its storage})
-    self.deferred_running = []      # _DEFERRED_RUNNING: (coef, running_mean, running_var, num_batches_tracked, C)
-    self.pending_join = []          # _PENDING_JOIN: (main stream, side stream) of branches not joined yet
-    self.branch_main = None         # _BRANCH_MAIN[0]: inside `with branch():` the stream the caller was on
-    self.no_proxy_branches = set()  # _NO_PROXY_BRANCHES (see below)
-    self.capture_proxies = None     # _CAPTURE_PROXIES[0]: iic_amd.graphed, {id(param): leaf alias} during a capture
-    self.solo_first = 0             # _SOLO_FIRST[0] (see auto_branch)
-
-
-_TLS = threading.local()
-
-
-def context():
-  """The calling thread's BranchContext."""
-  c = getattr(_TLS, "ctx", None)
-  if c is None:
-    c = _TLS.ctx = BranchContext()
-  return c
-
-
-class _CtxCell(object):
-  """`NAME[0]` view of a scalar field of the calling thread's context."""
-  __slots__ = ("_attr",)
-
-  def __init__(self, attr):
-    self._attr = attr
-
-  def __getitem__(self, i):
-    return getattr(context(), self._attr)
-
-  def __setitem__(self, i, v):
-    setattr(context(), self._attr, v)
-
-
-class _CtxView(object):
-  """Container view (list / dict / set) of a field of the calling thread's context."""
-  __slots__ = ("_attr",)
-
-  def __init__(self, attr):
-    self._attr = attr
-
-  def _o(self):
-    return getattr(context(), self._attr)
-
-  def __getattr__(self, name):
-    return getattr(self._o(), name)
-
-  def __len__(self):
-    return len(self._o())
-
-  def __bool__(self):
-    return bool(self._o())
-
-  def __iter__(self):
-    return iter(self._o())
-
-  def __contains__(self, x):
-    return x in self._o()
-
-  def __getitem__(self, k):
-    return self._o()[k]
-
-  def __setitem__(self, k, v):
-    self._o()[k] = v
-
-  def __delitem__(self, k):
-    del self._o()[k]
-
-
-BRANCH = _CtxCell("branch")
-_BRANCH_STREAM = _CtxView("streams")
-_PROXIES = _CtxView("proxies")                    # id(param) -> (param, {branch: leaf alias sharing its storage})
-_DEFERRED_RUNNING = _CtxView("deferred_running")  # (coef, running_mean, running_var, num_batches_tracked, C) of a branch
-_PENDING_JOIN = _CtxView("pending_join")          # (main stream, side stream) of branches not joined yet
-_BRANCH_MAIN = _CtxCell("branch_main")            # inside `with branch():` the stream the caller was on (iic_amd.graphed orders it after a view's backward)
-
-
-# IIC_BRANCH_PROXIES=0 (debugging only): side branches use the parameters themselves and autograd accumulates both
-# views' gradients into p.grad ACROSS the two streams.
-USE_PROXIES = [os.environ.get("IIC_BRANCH_PROXIES", "1") != "0"]
-
-
-# Branch indices that see the parameters themselves (no leaf aliases): the side stream of ops.auto_branch -- only
-# captured / replayed views run there, and those hand their gradients over explicitly (iic_amd/graphed.py) -- and the
-# resource namespaces iic_amd.graphed gives to positions that share a real branch.
-# (Rounds 3-4 also had an EAGER two-stream mode for unchanged scripts -- leaf aliases plus an end-of-backward fold of the
-# alias gradients into .grad.  It was demoted to opt-in in round 4 because about 1 run in 13 differed from the one-stream
-# run; round 5 found the cause -- the loss stacked the forked view's outputs before joining it, iic_amd/losses.py -- and
-# removed the mode rather than carry a second gradient hand-over for launches that are host-bound anyway.)
-_NO_PROXY_BRANCHES = _CtxView("no_proxy_branches")
-
-
-_CAPTURE_PROXIES = _CtxCell("capture_proxies")   # iic_amd.graphed: {id(param): leaf alias} while a view's graphs are captured
-
-
-def pv(p):
-  """Parameter as seen by the current branch (the parameter itself on the main branch)."""
-  cp = _CAPTURE_PROXIES[0]
-  if cp is not None and p is not None:
-    q = cp.get(id(p))
-    if q is not None:
-      return q
-  b = BRANCH[0]
-  if b == 0 or p is None or not p.requires_grad or not USE_PROXIES[0] or b in _NO_PROXY_BRANCHES:
-    return p
-  ent = _PROXIES.get(id(p))
-  if ent is None or ent[0] is not p:
-    ent = (p, {})
-    _PROXIES[id(p)] = ent
-  q = ent[1].get(b)
-  if q is None or q.data_ptr() != p.data_ptr():
-    q = p.detach().requires_grad_(True)
-    ent[1][b] = q
-  return q
-
-
-def branch_leaf(p, index):
-  """The autograd leaf branch `index` saw for parameter p (its alias, or p itself when the branch ran
-  without aliases / never touched p)."""
-  ent = _PROXIES.get(id(p))
-  if ent is None or ent[0] is not p or index in _NO_PROXY_BRANCHES:
-    return p
-  return ent[1].get(index, p)
-
-
-def branch_grads(p):
-  """Gradients the side branches accumulated for parameter p (list, possibly empty)."""
-  ent = _PROXIES.get(id(p))
-  if ent is None or ent[0] is not p:
-    return []
-  return [q.grad for q in ent[1].values() if q.grad is not None]
-
-
-def fold_branch_grads(params):
-  """p.grad += the gradients the side branches accumulated for p (and drop those): for callers that
-  need ONE gradient per parameter before the optimiser -- e.g. a gradient all-reduce."""
-  tgt, src = [], []
-  for p in params:
-    for g in branch_grads(p):
-      if p.grad is None:
-        p.grad = g.clone()
-      else:
-        tgt.append(p.grad)
-        src.append(g)
-  if tgt:
-    torch._foreach_add_(tgt, src)
-  clear_branch_grads()
-
-
-def clear_branch_grads():
-  for _, d in _PROXIES.values():
-    for q in d.values():
-      q.grad = None
-
-
-class branch(object):
-  """Fork the enclosed forward onto a side stream / graph branch (see above).  Not re-entrant."""
-
-  def __init__(self, index=1, proxies=True):
-    assert index >= 1
-    self.index = index
-    self.proxies = proxies
-
-  def __enter__(self):
-    assert BRANCH[0] == 0, "branches do not nest"
-    (_NO_PROXY_BRANCHES.discard if self.proxies else _NO_PROXY_BRANCHES.add)(self.index)
-    dev = torch.cuda.current_device()
-    key = (dev, self.index)
-    self.main = torch.cuda.current_stream()
-    st = _BRANCH_STREAM.get(key)
-    if st is None:
-      # HIP multiplexes streams onto a few hardware queues: keep a side stream that really runs beside the
-      # caller's and is not parked behind the process group's collectives (iic_amd.graph.pick_stream; a pair on
-      # one queue would run the two views one after the other)
-      from .graph import pick_stream
-      st = _BRANCH_STREAM[key] = pick_stream((self.main,), "side stream of ops.branch", collective_free=True)
-    self.side = st
-    st.wait_stream(self.main)                       # fork
-    for _, d in _PROXIES.values():                  # last step's branch gradients are consumed
-      q = d.get(self.index)
-      if q is not None:
-        q.grad = None
-    self.ctx = torch.cuda.stream(st)
-    self.ctx.__enter__()
-    BRANCH[0] = self.index
-    _BRANCH_MAIN[0] = self.main
-    return self
-
-  def __exit__(self, *exc):
-    BRANCH[0] = 0
-    _BRANCH_MAIN[0] = None
-    self.ctx.__exit__(*exc)
-    _PENDING_JOIN.append((self.main, self.side))    # joined later: the main view runs meanwhile
-    if exc and exc[0] is not None:
-      join()            # the forward raised: nobody downstream will join -- do not leave the fork pending
-    return False
-
-
-class on_branch(object):
-  """Low-level: run the enclosed code as branch `index` on `stream` WITHOUT any fork / join
-  synchronisation (iic_amd.graph.CapturedPairStep orders its per-view graphs itself)."""
-
-  def __init__(self, index, stream):
-    self.index, self.stream = index, stream
-
-  def __enter__(self):
-    assert BRANCH[0] == 0, "branches do not nest"
-    # (this view sees the parameters through leaf aliases whatever an earlier auto_branch run left behind: with the
-    #  index still marked alias-free, its gradients would be accumulated into .grad across the two streams)
-    _NO_PROXY_BRANCHES.discard(self.index)
-    self.ctx = torch.cuda.stream(self.stream)
-    self.ctx.__enter__()
-    BRANCH[0] = self.index
-    return self
-
-  def __exit__(self, *exc):
-    BRANCH[0] = 0
-    self.ctx.__exit__(*exc)
-    return False
-
-
-# Automatic two-stream execution for UNCHANGED training scripts (IIC_AUTO_BRANCH=1; `python -m
-# iic_amd.run` switches it on).  The reference's step calls net(all_imgs) and net(all_imgs_tf) one
-# after the other (cluster_sobel.py:238-239, segmentation_twohead.py:300-306) and hands both
-# results to the loss: the first training forward since the last join is put on the side stream,
-# the second runs on the caller's stream meanwhile, and the loss (ours) joins.  No parameter
-# aliases here -- autograd accumulates both views into p.grad, so any optimiser works.  Contract:
-# the outputs of the first forward must not be consumed by anything but this library's losses
-# before the join (true of every reference script); evaluation / no_grad forwards never branch.
-AUTO_BRANCH = [os.environ.get("IIC_AUTO_BRANCH", "0") == "1"]
-# A forward of the pair that runs EAGERLY -- graph replay off, a warm-up occurrence, a shape that was not captured --
-# stays on the caller's stream; the two streams are for captured / replayed views, whose gradient hand-over is explicit
-# (iic_amd/graphed.py).
-_SOLO_FIRST = _CtxCell("solo_first")   # 1: the first forward of a pair ran on the caller's stream (the second one must not fork either)
-# forwards that hand back FEATURES (semisup heads: sup_head5.py:34-35, net6c_two_head.py:78-94,
-# k-means feature extraction) are consumed by modules outside this library, which know nothing about
-# the side stream: they never branch
-_FEATURE_FLAGS = ("trunk_features", "penultimate_features", "kmeans_use_features")
-# running-statistic updates postponed by branch forwards (bn_finalize): flushed at every join; the
-# optimiser and the losses join.  A caller that does neither would grow the list without bound and
-# evaluate on stale running statistics -- past this many entries the next forward joins by itself.
-_DEFERRED_LIMIT = 1024
-
-
-class HeadPack(object):
-  """What the sub-head outputs of ONE forward share: the reference hands the loss a python list of per-sub-head
-  [bn, k] tensors (net5g.py:76-80) and calls IID_loss once per sub-head (cluster_sobel.py:241-253).  The list's
-  tensors are tagged with their pack and index so that iic_amd.losses.IID_loss can evaluate all sub-head pairs of
-  two packs in ONE set of launches at the first call and hand the other calls their share."""
-  __slots__ = ("tensors", "cache", "__weakref__")
-
-  def __init__(self, tensors):
-    # weak references: a tensor -> pack -> tensor cycle would keep a step's autograd graph (and with it ~18 GB of
-    # saved activations at the north-star batch) alive until the cyclic garbage collector happens to run
-    self.tensors = [weakref.ref(t) for t in tensors]
-    self.cache = {}
-
-  def alive(self):
-    ts = [r() for r in self.tensors]
-    return ts if all(t is not None for t in ts) else None
-
-
-def tag_pack(tensors):
-  """Tag a list of per-sub-head output tensors (returns the list)."""
-  if len(tensors) > 1 and all(torch.is_tensor(t) and t.dim() == 2 for t in tensors):
-    pack = HeadPack(tensors)
-    for i, t in enumerate(tensors):
-      t._iic_pack = (pack, i)
-  return tensors
-
-
-# Graph replay of the training forwards / backwards for unchanged scripts (iic_amd/graphed.py);
-# `python -m iic_amd.run` switches it on (IIC_GRAPH_FORWARD=0 keeps eager launches).
-GRAPH_FORWARD = [os.environ.get("IIC_GRAPH_FORWARD", "0") == "1"]
-
-
-def auto_branch(fwd):
-  """Decorator for the architectures' forward()."""
-  def wrapped(self, x, *a, **k):
-    if BRANCH[0] == 0 and (_PENDING_JOIN or _DEFERRED_RUNNING) and (
-        not self.training or not torch.is_grad_enabled() or len(_DEFERRED_RUNNING) > _DEFERRED_LIMIT):
-      join()      # evaluation must see up-to-date running statistics; bound the postponed list
-    run = fwd
-    will_branch = (AUTO_BRANCH[0] and self.training and torch.is_grad_enabled() and BRANCH[0] == 0
-                   and not _PENDING_JOIN and not _SOLO_FIRST[0] and torch.is_tensor(x) and x.is_cuda
-                   and not any(k.get(f) for f in _FEATURE_FLAGS))
-    pl = None
-    if GRAPH_FORWARD[0]:
-      from . import graphed
-      if graphed.eligible(self, x, a, k):
-        pl = graphed.plan(self, x, k, 1 if will_branch else BRANCH[0])
-
-        def run(self_, x_, *a_, **k_):      # captured-graph replay once this (shape, head, position) is warm
-          return graphed.forward(fwd, self_, x_, a_, k_, pl)
-    if will_branch:
-      if pl is None or pl.mode == "eager":
-        # eager launches stay on the caller's stream.  A planned position keeps its resource namespace (so that its
-        # buffers exist before the capture) but sees the parameters themselves; the pair's second forward must not
-        # fork in its place, and the running-statistic updates of both are applied at the join, in call order.
-        _SOLO_FIRST[0] = 1
-        if pl is not None:
-          _NO_PROXY_BRANCHES.add(pl.res)
-        try:
-          return run(self, x, *a, **k)
-        except BaseException:
-          _SOLO_FIRST[0] = 0              # the forward raised: there will be no second view to wait for
-          raise
-      # a replayed / captured view: side stream, the parameters themselves, gradients handed over by its autograd node
-      with branch(proxies=False) as br:
-        x.record_stream(br.side)         # allocated on the caller's stream, consumed on the side stream
-        return run(self, x, *a, **k)
-    if _SOLO_FIRST[0] == 1 and self.training and torch.is_grad_enabled() and BRANCH[0] == 0:
-      # the second view of a pair whose first view stayed on the caller's stream: its running-statistic updates are
-      # postponed like the first view's (bn_finalize) and the pair ends with it.  Both views ran on the caller's
-      # stream, so nothing is left to wait for: the postponed updates are applied right here, in call order -- a
-      # state_dict() / checkpoint taken after the step sees them whoever owns the loss and the optimiser (ADVICE r5)
-      try:
-        return run(self, x, *a, **k)
-      finally:
-        join()
-    if not torch.is_grad_enabled():
-      mark = POOL.mark()                 # evaluation: nothing will release the activations later
-      try:
-        return fwd(self, x, *a, **k)
-      finally:
-        POOL.sweep(mark)
-    return run(self, x, *a, **k)
-  wrapped.__name__ = getattr(fwd, "__name__", "forward")
-  wrapped.__doc__ = fwd.__doc__
-  wrapped.__wrapped__ = fwd          # inspect.signature() shows the architecture's own parameters
-  return wrapped
-
-
-def join():
-  """Main stream waits for the side branches forked since the last join, then applies their
-  postponed running-statistic updates (after the main view's own: sequential order)."""
-  while _PENDING_JOIN:
-    main, side = _PENDING_JOIN.pop()
-    main.wait_stream(side)
-  _SOLO_FIRST[0] = 0
-  flush_deferred_running()
-
-
-def flush_deferred_running():
-  """Apply the running-statistic updates the branch forwards postponed (one launch)."""
-  if not _DEFERRED_RUNNING:
-    return
-  items = list(_DEFERRED_RUNNING)
-  del _DEFERRED_RUNNING[:]
-  n = len(items)
-  VP = ctypes.c_void_p * n
-  IP = ctypes.c_int * n
-  check(lib().iic_bn_running_update(
-    n, VP(*[ptr(c) for c, _, _, _, _ in items]), VP(*[ptr(rm) for _, rm, _, _, _ in items]),
-    VP(*[ptr(rv) for _, _, rv, _, _ in items]), VP(*[ptr(nb) for _, _, _, nb, _ in items]),
-    IP(*[C for _, _, _, _, C in items]), BN_MOMENTUM, stream_ptr()), "iic_bn_running_update")
-
-
-def branch_backward(fn):
-  """Decorator for autograd Function.backward: run under the branch the forward recorded."""
-  def wrapped(ctx, *grads):
-    if getattr(ctx, "_iic_ran", False):
-      raise RuntimeError("iic_amd: backward through this graph a second time -- the saved activation "
-                         "buffers went back to the pool after the first pass (retain_graph is not "
-                         "supported on the HIP path)")
-    ctx._iic_ran = True
-    prev, prev_dt = BRANCH[0], PT_DTYPE[0]
-    BRANCH[0] = getattr(ctx, "branch", 0)
-    PT_DTYPE[0] = getattr(ctx, "pt_dtype", prev_dt)     # (fp32_mode() forwards allocate fp32 in backward too)
-    try:
-      return fn(ctx, *grads)
-    finally:
-      BRANCH[0], PT_DTYPE[0] = prev, prev_dt
-  wrapped.__name__ = getattr(fn, "__name__", "backward")
-  return staticmethod(wrapped)
-
-
-# ------------------------------------------------------------------------------------
-# PT ("padded tile") activation buffers: bf16 [N, H+2P, W+2P, C], zero border.
-# Kernels write interiors only, so buffers are zeroed ONCE and recycled through a pool
-# (no per-step memset traffic).  A buffer is handed out by `alloc`, and returned with
-# `release` once every kernel that reads it has been enqueued (stream-ordered reuse).
-# ------------------------------------------------------------------------------------
-# Storage type of PT tensors: bf16 (the product path) or, inside `with fp32_mode():`, fp32 -- the
-# exact-fp32 parity path of csrc/f32_path.hip (SURVEY.md §8c tier T2): same orchestration, plain
-# fp32 kernels, for whole-network comparisons with the reference's fp32 results.  Every wrapper
-# below dispatches on the dtype of the tensors it is handed.
-PT_DTYPE = [BF16]
-
-
-class fp32_mode(object):
-  def __enter__(self):
-    self.prev = PT_DTYPE[0]
-    PT_DTYPE[0] = F32
-    return self
-
-  def __exit__(self, *exc):
-    PT_DTYPE[0] = self.prev
-    return False
-
-
-class PTPool(object):
-  """Buffers are keyed by (shape, border P, device, branch, dtype): a recycled buffer is only valid
-  for a tensor with the SAME interior/border split (its border must still be zero), and only on
-  the stream (branch) whose kernels used it last.
-
-  The pool keeps a reference to every buffer it created (`owned`), so an address can never come
-  back from the caching allocator as some other tensor and be mistaken for a zero-border buffer;
-  `release` only accepts buffers that are currently handed out (a second release -- e.g. a
-  backward run twice -- is ignored instead of putting one buffer on the free list twice)."""
-
-  def __init__(self):
-    self.free = {}
-    self.owned = {}           # data_ptr -> (tensor, P, branch) of every buffer this pool created
-    self.live = {}            # data_ptr -> serial of the alloc() that handed it out
-    self.serial = 0
-    self.allocated_bytes = 0
-
-  def alloc(self, shape, device, P=1):
-    dt = PT_DTYPE[0]
-    key = (tuple(shape), int(P), str(device), BRANCH[0], dt)
-    lst = self.free.get(key)
-    if lst:
-      t = lst.pop()
-    else:
-      t = torch.zeros(shape, dtype=dt, device=device)
-      self.owned[t.data_ptr()] = (t, int(P), BRANCH[0])
-      self.allocated_bytes += t.numel() * t.element_size()
-    self.serial += 1
-    self.live[t.data_ptr()] = self.serial
-    # a fresh tensor object per hand-out: the caller's autograd state (grad_fn of the Function that
-    # returns it, user hooks registered on it) must not survive into the buffer's next life
-    return t.detach()
-
-  def release(self, t):
-    if t is None:
-      return
-    ent = self.owned.get(t.data_ptr())
-    if ent is None or ent[0].shape != t.shape:
-      return                  # not one of ours (a user tensor, a view): never recycle it
-    if self.live.pop(t.data_ptr(), None) is None:
-      return                  # already back in the pool
-    key = (tuple(t.shape), ent[1], str(t.device), ent[2], t.dtype)
-    self.free.setdefault(key, []).append(ent[0])
-
-  def mark(self):
-    return self.serial
-
-  def sweep(self, mark):
-    """Return every buffer handed out since `mark` that is still out: the end of a forward that
-    no backward will follow (torch.no_grad evaluation), whose consumers are all enqueued."""
-    for dp in [dp for dp, ser in self.live.items() if ser > mark]:
-      self.release(self.owned[dp][0])
-
-  def clear(self):
-    self.free.clear()
-    self.owned.clear()
-    self.live.clear()
-
-
-POOL = PTPool()
-
-
-def pt_alloc(N, H, W, C, P, device):
-  return POOL.alloc((N, H + 2 * P, W + 2 * P, C), device, P)
-
-
-def pt_from_nchw(x, P):
-  """(test / boundary helper) NCHW float tensor -> PT (bf16, or fp32 inside fp32_mode())."""
-  n, c, h, w = x.shape
-  out = torch.zeros((n, h + 2 * P, w + 2 * P, c), dtype=PT_DTYPE[0], device=x.device)
-  out[:, P:P + h, P:P + w, :] = x.permute(0, 2, 3, 1).to(PT_DTYPE[0])
-  return out
-
-
-def pt_to_nchw(x, P):
-  n, hp, wp, c = x.shape
-  return x[:, P:hp - P, P:wp - P, :].permute(0, 3, 1, 2).float().contiguous()
+from .branches import (AUTO_BRANCH, BN_MOMENTUM, GRAPH_FORWARD, USE_PROXIES, BranchContext, HeadPack,  # noqa: F401
+                       auto_branch, branch, branch_backward, branch_grads, branch_leaf, clear_branch_grads, context,
+                       current_branch, flush_deferred_running, fold_branch_grads, join, on_branch, pv, tag_pack)
+from .pool import (BF16, F32, POOL, PT_DTYPE, PTPool, Scratch, fp32_mode, pt_alloc, pt_from_nchw,  # noqa: F401
+                   pt_to_nchw)
 
 
 def new_stats(C, device):
@@ -738,19 +226,10 @@ def conv_igemm(g, x_pt, w_t, out_pt, stats=None, res_grad=None, res_act=None, ac
   return out_pt
 
 
-_WG_PART = {}
-
-
-def _conv_wgrad_launch(g, x_pt, dy_pt, wtaps, use_tr, out, accumulate, ns, key):
-  need = ns * g.ntaps * g.Cout * g.Cin
-  part = _WG_PART.get(key)
-  if part is None or part.numel() < need:
-    part = torch.empty(max(need, 1 << 22), dtype=F32, device=x_pt.device)
-    _WG_PART[key] = part
-  check(lib().iic_conv_wgrad(ctypes.byref(g), ptr(x_pt), ptr(dy_pt), ptr(part), ns,
-                             1 if use_tr else 0, stream_ptr()), "iic_conv_wgrad")
-  check(lib().iic_conv_wgrad_reduce(ptr(part), ns, wtaps, g.Cout, g.Cin, ptr(out),
-                                    1 if accumulate else 0, stream_ptr()), "iic_conv_wgrad_reduce")
+WG_PART = Scratch()      # split-K partials of conv_wgrad
+STEM_PART = Scratch()    # per-block partials of the stem's weight gradient
+FC_PART = Scratch()      # per-block partials of firstconv_wgrad
+GEMM_WS = Scratch()      # workspace of the K-split GEMMs
 
 
 def conv_wgrad(g, x_pt, dy_pt, wtaps, use_tr=True, out=None, accumulate=False, nsplit=None):
@@ -766,15 +245,18 @@ def conv_wgrad(g, x_pt, dy_pt, wtaps, use_tr=True, out=None, accumulate=False, n
   if out is None:
     out = torch.empty((g.Cout, g.Cin, wtaps), dtype=F32, device=x_pt.device)
   assert g.ntaps == wtaps, "wgrad geometry must list every weight tap once"
-  _conv_wgrad_launch(g, x_pt, dy_pt, wtaps, use_tr, out, accumulate, ns, (str(x_pt.device), BRANCH[0]))
+  part = WG_PART.get(x_pt.device, ns * g.ntaps * g.Cout * g.Cin, minimum=1 << 22)
+  check(lib().iic_conv_wgrad(ctypes.byref(g), ptr(x_pt), ptr(dy_pt), ptr(part), ns,
+                             1 if use_tr else 0, stream_ptr()), "iic_conv_wgrad")
+  check(lib().iic_conv_wgrad_reduce(ptr(part), ns, wtaps, g.Cout, g.Cin, ptr(out),
+                                    1 if accumulate else 0, stream_ptr()), "iic_conv_wgrad_reduce")
   return out
 
 
 # ------------------------------------------------------------------------------------
 # batch norm
 # ------------------------------------------------------------------------------------
-BN_EPS = 1e-5
-BN_MOMENTUM = 0.1
+BN_EPS = 1e-5      # (BN_MOMENTUM: iic_amd.branches, beside the postponed running-statistic update)
 
 
 # Replica de-duplication (opt-in, archs.cluster.DEDUP): while a de-duplicated forward runs, the
@@ -785,11 +267,12 @@ BN_REPLICAS = [1]
 def bn_finalize(stats, gamma, beta, running_mean, running_var, nbt, C, count, training):
   """coef [5][C]: scale, shift, mean, invstd, unbiased batch variance."""
   coef = torch.empty((5, C), dtype=F32, device=gamma.device)
-  if training and running_mean is not None and (BRANCH[0] != 0 or _PENDING_JOIN or _SOLO_FIRST[0]):
+  bc = context()
+  if training and running_mean is not None and (bc.branch != 0 or bc.pending_join or bc.solo_first):
     # a side branch is (or may still be) running: both views update the same running statistics,
     # so every update is postponed to the join and applied there in CALL order -- the order a
     # sequential run would have used (fork the view that comes first in the script)
-    _DEFERRED_RUNNING.append((coef, running_mean, running_var, nbt, C))
+    bc.deferred_running.append((coef, running_mean, running_var, nbt, C))
     running_mean = running_var = nbt = None
   check(lib().iic_bn_finalize(ptr(stats), ptr(gamma), ptr(beta), ptr(running_mean),
                               ptr(running_var), ptr(nbt), ptr(coef), C, count,
@@ -871,9 +354,6 @@ def stem_bwd_reduce(x, w, coef, dpool, sums):
                                   stream_ptr()), "iic_stem_bwd_reduce")
 
 
-_STEM_PART = {}
-
-
 def stem_bwd_wgrad(x, w, coef, bcoef, dpool):
   n, c, h, wd = x.shape
   part = _stem_partials(x.device)
@@ -884,12 +364,7 @@ def stem_bwd_wgrad(x, w, coef, bcoef, dpool):
 
 
 def _stem_partials(device):
-  key = (str(device), BRANCH[0])
-  part = _STEM_PART.get(key)
-  if part is None:
-    part = torch.empty(lib().iic_stem_wgrad_partial_floats(), dtype=F32, device=device)
-    _STEM_PART[key] = part
-  return part
+  return STEM_PART.get(device, lib().iic_stem_wgrad_partial_floats())
 
 
 def stem_bwd_fused_ok(cin):
@@ -955,21 +430,9 @@ def avgpool_bwd(dfeats, out_pt, N, H, W, P, C, mask_act=None):
   return out_pt
 
 
-_GEMM_WS = {}      # (branch, device) -> fp32 workspace of the K-split GEMMs (grown on demand, reused)
-_GEMM_WS_RETIRED = []   # superseded workspaces: a captured graph may have their address baked in -- never freed
-
-
 def gemm_f32(A, sam, sak, B, sbk, sbn, C, scm, M, N, K, bias=None, accumulate=False):
   need = lib().iic_gemm_f32_ws_floats(sam, sak, sbk, sbn, M, N, K)
-  ws = None
-  if need:
-    key = (BRANCH[0], C.device.index)
-    ws = _GEMM_WS.get(key)
-    if ws is None or ws.numel() < need:
-      if ws is not None:
-        _GEMM_WS_RETIRED.append(ws)        # (head B's graphs kept replaying into a buffer that head A's
-                                           #  larger request had freed)
-      ws = _GEMM_WS[key] = torch.empty(max(need, 1 << 20), dtype=F32, device=C.device)
+  ws = GEMM_WS.get(C.device, need, minimum=1 << 20) if need else None
   check(lib().iic_gemm_f32_ws(ptr(A), sam, sak, ptr(B), sbk, sbn, ptr(bias), ptr(C), scm, M, N, K,
                               1 if accumulate else 0, ptr(ws), need, stream_ptr()), "iic_gemm_f32_ws")
   return C
@@ -1004,16 +467,9 @@ def firstconv_fwd(x, w, out_pt, stats, K, pad, P):
   return out_pt
 
 
-_FC_PART = {}
-
-
 def firstconv_wgrad(x, dy_pt, w_shape, K, pad, P):
   n, c, h, wd = x.shape
-  key = (str(x.device), BRANCH[0])
-  part = _FC_PART.get(key)
-  if part is None:
-    part = torch.empty(lib().iic_firstconv_wgrad_partial_floats(), dtype=F32, device=x.device)
-    _FC_PART[key] = part
+  part = FC_PART.get(x.device, lib().iic_firstconv_wgrad_partial_floats())
   dW = torch.empty(w_shape, dtype=F32, device=x.device)
   check(lib().iic_firstconv_wgrad(ptr(x), ptr(dy_pt), ptr(part), ptr(dW), n, c, h, wd, K, pad, P,
                                   stream_ptr()), "iic_firstconv_wgrad")

@@ -67,8 +67,9 @@ def test_k_split_workspace_is_never_freed_when_it_grows():
   import torch
   from iic_amd import ops
   dev = torch.device("cuda:0")
-  ops._GEMM_WS.clear()
-  del ops._GEMM_WS_RETIRED[:]
+  ws = ops.GEMM_WS                        # the iic_amd.pool.Scratch of the K-split GEMMs
+  ws.bufs.clear()
+  del ws.retired[:]
 
   def logits(n, k_out, kdim=512):
     x = torch.randn(n, kdim, device=dev)
@@ -78,14 +79,14 @@ def test_k_split_workspace_is_never_freed_when_it_grows():
     torch.cuda.synchronize()
     assert torch.allclose(c, x @ w.t(), rtol=2e-4, atol=2e-3)
   logits(660, 50)
-  key = (ops.BRANCH[0], dev.index)
-  first = ops._GEMM_WS.get(key)
+  key = (dev.index, ops.current_branch())
+  first = ws.bufs.get(key)
   if first is None:
     pytest.skip("this shape takes no K split on this build")
   p0, n0 = first.data_ptr(), first.numel()
   logits(4096, 700)                       # a larger request on the same branch
-  second = ops._GEMM_WS[key]
+  second = ws.bufs[key]
   if second.data_ptr() != p0:
     assert second.numel() > n0
-    assert any(t.data_ptr() == p0 for t in ops._GEMM_WS_RETIRED), "the superseded workspace was freed"
+    assert any(t.data_ptr() == p0 for t in ws.retired), "the superseded workspace was freed"
   logits(660, 50)                         # and the small shape still computes right

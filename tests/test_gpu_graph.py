@@ -87,11 +87,8 @@ def test_adam_second_gradient_source():
   o1, o2 = Adam([p1], lr=1e-2), Adam([p2], lr=1e-2)
   p1.grad = g1 + g2
   o1.step()
-  ops.BRANCH[0] = 1
-  try:
+  with ops.context().as_branch(1):
     q = ops.pv(p2)
-  finally:
-    ops.BRANCH[0] = 0
   assert q is not p2 and q.data_ptr() == p2.data_ptr()
   p2.grad, q.grad = g1.clone(), g2.clone()
   o2.step()
@@ -278,14 +275,14 @@ def test_auto_branch_reference_call_sequence_is_bit_identical():
       for _ in range(4):
         net.zero_grad()
         xo = net(sobel_process(imgs, False))
-        assert not ops._PENDING_JOIN
-        assert ops._SOLO_FIRST[0] == (1 if auto else 0)
+        assert not ops.context().pending_join
+        assert ops.context().solo_first == (1 if auto else 0)
         xt = net(sobel_process(imgs_tf, False))
         tot = None
         for i in range(2):
           l, _ = IID_loss(xo[i], xt[i], lamb=1.0)
           tot = l if tot is None else tot + l
-        assert not ops._PENDING_JOIN and not ops._SOLO_FIRST[0]          # the loss joined
+        assert not ops.context().pending_join and not ops.context().solo_first          # the loss joined
         tot /= 2
         losses.append(tot.item())
         tot.backward()
@@ -293,7 +290,7 @@ def test_auto_branch_reference_call_sequence_is_bit_identical():
       net.eval()
       with torch.no_grad():
         ev = net(sobel_process(imgs, False))[0].clone()     # evaluation never branches
-      assert not ops._PENDING_JOIN
+      assert not ops.context().pending_join
     finally:
       ops.AUTO_BRANCH[0] = False
     torch.cuda.synchronize()
@@ -314,3 +311,44 @@ def test_captured_pair_steps_share_one_stream_pair_that_really_overlaps():
   assert a[0] is b[0] and a[1] is b[1] and a[0] is not a[1]
   assert _streams_overlap(a[0], a[1])
   assert not _streams_overlap(a[0], a[0])
+
+
+def test_captured_wgrad_survives_a_larger_request_for_split_k_partials():
+  """A captured weight-gradient launch has the address of its split-K partials baked in.  A later, larger request on the
+  same branch (3 x 3, 512 -> 512, two splits: 2 * 9 * 512 * 512 floats, past the 4 M-float minimum) replaces the
+  buffer; the superseded one must stay alive (iic_amd.pool.Scratch.retired) and the replayed graph must still produce
+  the bits it produced eagerly before the growth."""
+  from iic_amd import geom, ops
+  dev = torch.device("cuda:0")
+  N, H, P = 2, 6, 1
+  sc = ops.WG_PART
+  key = (dev.index, ops.current_branch())
+  if key in sc.bufs:                         # (an earlier test may have grown it already: start from the minimum)
+    sc.retired.append(sc.bufs.pop(key))
+
+  def case(c, seed):
+    gen = torch.Generator().manual_seed(seed)
+    x = ops.pt_from_nchw(torch.randn(N, c, H, H, generator=gen).to(dev), P)
+    dy = ops.pt_from_nchw(torch.randn(N, c, H, H, generator=gen).to(dev), P)
+    return geom.fwd_geom(geom.ConvSpec(c, c, 3, 1, 1), N, H, H, P, P), x, dy
+
+  g, x, dy = case(64, 0)
+  eager = ops.conv_wgrad(g, x, dy, 9).clone()            # (also creates the partials buffer outside the capture)
+  torch.cuda.synchronize()
+  small = sc.bufs[key]
+  p0 = small.data_ptr()
+  assert small.numel() == 1 << 22
+  out = torch.zeros_like(eager)
+  graph = torch.cuda.CUDAGraph()
+  with torch.cuda.graph(graph):
+    ops.conv_wgrad(g, x, dy, 9, out=out)
+  assert sc.bufs[key] is small
+  gb, xb, dyb = case(512, 1)
+  ops.conv_wgrad(gb, xb, dyb, 9, nsplit=2)               # 4.7 M floats: the buffer grows
+  torch.cuda.synchronize()
+  assert sc.bufs[key] is not small and sc.bufs[key].numel() >= 2 * 9 * 512 * 512
+  assert any(t is small for t in sc.retired) and small.data_ptr() == p0
+  out.zero_()
+  graph.replay()
+  torch.cuda.synchronize()
+  assert np.array_equal(out.cpu().numpy(), eager.cpu().numpy())

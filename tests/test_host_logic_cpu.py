@@ -4,7 +4,7 @@ import types
 
 import torch
 
-from iic_amd import graphed, ops
+from iic_amd import branches, graphed, ops
 
 
 class _Net(torch.nn.Module):
@@ -35,7 +35,7 @@ def test_plan_gives_one_stream_positions_their_own_namespace_and_notices_moved_p
   graphed._cl.bump_weights_epoch()
   p0 = graphed.plan(net, x, {}, 0)
   p1 = graphed.plan(net, x, {}, 0)          # second forward of the step on the SAME branch
-  assert p0.res == 0 and p1.res >= 100 and p1.res in ops._NO_PROXY_BRANCHES
+  assert p0.res == 0 and p1.res >= 100 and p1.res in ops.context().no_proxy_branches
   # a captured graph whose parameters were re-allocated (.cpu() / .cuda() round trip of a checkpoint) is dropped
   st = p0.st
   st["graphs"][p0.key] = types.SimpleNamespace(sig=graphed._storage_sig(net))
@@ -56,7 +56,7 @@ class _FakeDeviceTensor(torch.Tensor):
 
 
 def test_auto_branch_keeps_eager_pair_forwards_on_the_callers_stream(monkeypatch):
-  """A forward of the pair that runs eagerly does not fork; the first one marks the pair (_SOLO_FIRST = 1) so that the
+  """A forward of the pair that runs eagerly does not fork; the first one marks the pair (solo_first = 1) so that the
   second one does not fork in its place; both postpone their running-statistic updates, and the second one ends the
   pair by applying them itself (both ran on the caller's stream: nothing to wait for -- a checkpoint taken right after
   a step with a foreign loss and a foreign optimiser sees them).
@@ -71,32 +71,33 @@ def test_auto_branch_keeps_eager_pair_forwards_on_the_callers_stream(monkeypatch
 
     @ops.auto_branch
     def forward(self, x, head="B"):
-      calls.append((ops.BRANCH[0], ops._SOLO_FIRST[0], ops.pv(self.fc.weight) is self.fc.weight))
+      calls.append((ctx.branch, ctx.solo_first, ops.pv(self.fc.weight) is self.fc.weight))
       if getattr(self, "boom", False):
         raise RuntimeError("boom")
       return [torch.as_tensor(x).as_subclass(torch.Tensor) @ self.fc.weight.t()]
 
+  ctx = ops.context()
   flushes = []
-  monkeypatch.setattr(ops, "flush_deferred_running", lambda: flushes.append(1))
+  monkeypatch.setattr(branches, "flush_deferred_running", lambda: flushes.append(1))
   net = Net().train()
   x = torch.zeros(5, 4).as_subclass(_FakeDeviceTensor)
   prev = ops.AUTO_BRANCH[0], ops.GRAPH_FORWARD[0]
   try:
     ops.AUTO_BRANCH[0], ops.GRAPH_FORWARD[0] = True, False
     net(x)
-    assert ops._SOLO_FIRST[0] == 1 and not ops._PENDING_JOIN and calls[-1] == (0, 1, True)
+    assert ctx.solo_first == 1 and not ctx.pending_join and calls[-1] == (0, 1, True)
     n_fl = len(flushes)
     net(x)
     # the second view ends the pair: mark cleared, postponed running-statistic updates flushed -- with no join of ours
-    assert calls[-1] == (0, 1, True) and not ops._PENDING_JOIN and ops._SOLO_FIRST[0] == 0 and len(flushes) == n_fl + 1
+    assert calls[-1] == (0, 1, True) and not ctx.pending_join and ctx.solo_first == 0 and len(flushes) == n_fl + 1
     ops.join()
-    assert not ops._SOLO_FIRST[0]
+    assert not ctx.solo_first
     # nothing of ours joins (a foreign loss and a foreign optimiser): every pair still flushes once, at its second view
     n_fl = len(flushes)
     net(x); net(x)
-    assert ops._SOLO_FIRST[0] == 0 and len(flushes) == n_fl + 1
+    assert ctx.solo_first == 0 and len(flushes) == n_fl + 1
     net(x)
-    assert ops._SOLO_FIRST[0] == 1 and calls[-1] == (0, 1, True)
+    assert ctx.solo_first == 1 and calls[-1] == (0, 1, True)
     net(x)
     ops.join()
     # a first forward that raises does not leave the mark behind
@@ -106,14 +107,14 @@ def test_auto_branch_keeps_eager_pair_forwards_on_the_callers_stream(monkeypatch
     except RuntimeError:
       pass
     net.boom = False
-    assert ops._SOLO_FIRST[0] == 0
+    assert ctx.solo_first == 0
     # graph replay on: warm-up occurrences of (position 0, branch 1) run on the caller's stream in namespace 1
     ops.GRAPH_FORWARD[0] = True
     monkeypatch.setattr(graphed, "eligible", lambda mod, x_, a, k: True)
     for step in range(2):
       graphed._cl.bump_weights_epoch()
       net(x)
-      assert calls[-1] == (1, 1, True) and 1 in ops._NO_PROXY_BRANCHES
+      assert calls[-1] == (1, 1, True) and 1 in ctx.no_proxy_branches
       net(x)
       assert calls[-1] == (0, 1, True)
       ops.join()
@@ -124,7 +125,7 @@ def test_auto_branch_keeps_eager_pair_forwards_on_the_callers_stream(monkeypatch
     assert graphed.plan(net, x, {}, 1).mode == "capture"
   finally:
     ops.AUTO_BRANCH[0], ops.GRAPH_FORWARD[0] = prev
-    ops._SOLO_FIRST[0] = 0
+    ctx.solo_first = 0
 
 
 def test_sig_changed_notices_a_buffer_replaced_through_a_submodule():
@@ -147,36 +148,38 @@ def test_sig_changed_notices_a_buffer_replaced_through_a_submodule():
 
 def test_branch_state_is_one_context_per_thread():
   """Round 6: the fork / join state of the two-stream execution -- current branch, pending joins,
-  postponed running-statistic updates, leaf aliases, the solo-pair mark -- lives in ONE BranchContext per thread; the
-  module-level names are views of the calling thread's context, so a second thread (a DataParallel-style worker, the
-  autograd engine's backward thread) starts clean and cannot disturb the first."""
+  postponed running-statistic updates, leaf aliases, the solo-pair mark -- lives in ONE BranchContext per thread, so a
+  second thread (a DataParallel-style worker, the autograd engine's backward thread) starts clean and cannot disturb
+  the first."""
   import threading
   main = ops.context()
-  assert ops.context() is main
-  prev = ops.BRANCH[0]
+  assert ops.context() is main and branches.context() is main
+  prev = main.branch
   seen = {}
   try:
-    ops.BRANCH[0] = 2
-    ops._PENDING_JOIN.append(("main", "side"))
-    ops._DEFERRED_RUNNING.append("update")
-    ops._NO_PROXY_BRANCHES.add(7)
-    ops._SOLO_FIRST[0] = 1
+    main.branch = 2
+    pending = main.pending_join
+    pending.append(("main", "side"))
+    main.deferred_running.append("update")
+    main.no_proxy_branches.add(7)
+    main.solo_first = 1
 
     def worker():
-      seen["ctx_is_other"] = ops.context() is not main
-      seen["state"] = (ops.BRANCH[0], len(ops._PENDING_JOIN), len(ops._DEFERRED_RUNNING), 7 in ops._NO_PROXY_BRANCHES,
-                       ops._SOLO_FIRST[0], ops._BRANCH_MAIN[0], ops._CAPTURE_PROXIES[0])
-      ops.BRANCH[0] = 5
-      ops._PENDING_JOIN.append(("w", "w"))
+      c = ops.context()
+      seen["ctx_is_other"] = c is not main
+      seen["state"] = (ops.current_branch(), len(c.pending_join), len(c.deferred_running), 7 in c.no_proxy_branches,
+                       c.solo_first, c.branch_main, c.capture_proxies)
+      c.branch = 5
+      c.pending_join.append(("w", "w"))
     t = threading.Thread(target=worker)
     t.start()
     t.join()
     assert seen["ctx_is_other"] and seen["state"] == (0, 0, 0, False, 0, None, None)
-    assert ops.BRANCH[0] == 2 and list(ops._PENDING_JOIN) == [("main", "side")] and main.branch == 2
-    assert main.pending_join is ops._PENDING_JOIN._o() and main.solo_first == 1
+    assert ops.current_branch() == 2 and list(ops.context().pending_join) == [("main", "side")] and main.branch == 2
+    assert main.pending_join is pending and main.solo_first == 1
   finally:
-    ops.BRANCH[0] = prev
-    del ops._PENDING_JOIN[:]
-    del ops._DEFERRED_RUNNING[:]
-    ops._NO_PROXY_BRANCHES.discard(7)
-    ops._SOLO_FIRST[0] = 0
+    main.branch = prev
+    del main.pending_join[:]
+    del main.deferred_running[:]
+    main.no_proxy_branches.discard(7)
+    main.solo_first = 0

@@ -1,9 +1,11 @@
-"""Host logic of the activation-buffer pool (iic_amd.ops.PTPool): ownership by the pool rather than
-by address, idempotent release, the evaluation sweep, and the second-backward guard."""
+"""Host logic of the activation-buffer pool (iic_amd.pool.PTPool): ownership by the pool rather than
+by address, idempotent release, the evaluation sweep, and the second-backward guard; the per-branch
+scratch buffers (iic_amd.pool.Scratch)."""
 import pytest
 import torch
 
-from iic_amd import ops
+from iic_amd import branches, ops
+from iic_amd import pool as pool_mod
 
 
 def test_pool_recycles_and_ignores_foreign_and_double_release():
@@ -53,7 +55,7 @@ def test_sweep_returns_only_buffers_since_the_mark():
 
 def test_auto_branch_wrapper_sweeps_under_no_grad(monkeypatch):
   pool = ops.PTPool()
-  monkeypatch.setattr(ops, "POOL", pool)
+  monkeypatch.setattr(pool_mod, "POOL", pool)
 
   class M(torch.nn.Module):
     @ops.auto_branch
@@ -102,3 +104,31 @@ def test_recycled_buffer_is_a_fresh_tensor_object():
   b = pool.alloc((1, 4, 4, 8), "cpu", 1)
   assert b.data_ptr() == a.data_ptr() and b is not a
   assert not b.requires_grad and b._backward_hooks is None and b.grad_fn is None
+
+
+def test_scratch_is_per_branch_and_retires_what_it_outgrows():
+  sc = pool_mod.Scratch()
+  a = sc.get("cpu", 100, minimum=256)
+  assert a.dtype == torch.float32 and a.numel() == 256            # the new buffer honours `minimum`
+  assert sc.get("cpu", 256, minimum=256) is a and sc.get("cpu", 1) is a and not sc.retired
+  with ops.context().as_branch(1):
+    b = sc.get("cpu", 100, minimum=256)
+    assert b is not a and b.data_ptr() != a.data_ptr()
+    assert sc.get("cpu", 100) is b
+  assert sc.get("cpu", 100) is a                                  # back on branch 0
+  p0 = a.data_ptr()
+  big = sc.get("cpu", 1000, minimum=256)
+  assert big is not a and big.numel() == 1000 and sc.get("cpu", 1000) is big
+  # the superseded buffer stays referenced (a captured graph may have its address baked in) and is not moved
+  assert any(t is a for t in sc.retired) and a.data_ptr() == p0 and a.numel() == 256
+  grown = sc.get("cpu", 1001, minimum=1 << 12)
+  assert grown.numel() == 1 << 12 and [t.data_ptr() for t in sc.retired] == [p0, big.data_ptr()]
+  with ops.context().as_branch(1):
+    assert sc.get("cpu", 100) is b                                # the other branch's buffer was left alone
+
+
+def test_ops_reexports_are_the_owning_modules_objects():
+  assert ops.AUTO_BRANCH is branches.AUTO_BRANCH
+  assert ops.GRAPH_FORWARD is branches.GRAPH_FORWARD
+  assert ops.POOL is pool_mod.POOL
+  assert ops.PT_DTYPE is pool_mod.PT_DTYPE and ops.context is branches.context

@@ -86,7 +86,7 @@ def multi_run(net, state, imgs, imgs_tf, heads, steps, sync_each, opt_kind):
     if "D" in at:
       torch.cuda.synchronize()                      # after backward, before the optimiser
     if "d" in at:                                   # only the side streams
-      for st_ in list(ops._BRANCH_STREAM.values()):
+      for st_ in list(ops.context().streams.values()):
         st_.synchronize()
     if s_ == steps - 1:
       for n_, p in net.named_parameters():
@@ -103,7 +103,7 @@ def multi_run(net, state, imgs, imgs_tf, heads, steps, sync_each, opt_kind):
     if "m" in at:                                   # only the caller's stream
       torch.cuda.current_stream().synchronize()
     if "e" in at:
-      for st_ in list(ops._BRANCH_STREAM.values()):
+      for st_ in list(ops.context().streams.values()):
         st_.synchronize()
     if sync_each:
       torch.cuda.synchronize()
