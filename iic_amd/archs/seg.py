@@ -27,33 +27,49 @@ F32 = torch.float32
 FUSED_HEAD = [os.environ.get("IIC_SEG_FUSED_HEAD", "1") != "0"]
 
 
+def _head_probs(x, w, P):
+  """The head up to the low-resolution softmax, shared by _SegHeadFn.forward and predict_labels: window GEMM (fused on
+  the bf16 PT window, or gather -> generic fp32 GEMM) and Softmax2d.  Returns probs [N*Hw*Ww, k] fp32 (pixel-major), the
+  gathered window matrix (None on the fused path), the [k, C] weight, the path taken and (N, Hw, Ww, off, k)."""
+  N, Hp, Wp, C = x.shape
+  Hw, Ww, off = Hp - 2 * P + 2, Wp - 2 * P + 2, P - 1
+  k = w.shape[0]
+  M = N * Hw * Ww
+  L, s = lib(), stream_ptr()
+  W2 = w.detach().reshape(k, C).contiguous()
+  logits = torch.empty((M, k), dtype=F32, device=x.device)
+  # fused path: the GEMMs read / write the bf16 window in place (csrc/seg_head.hip)
+  fused = FUSED_HEAD[0] and x.dtype != F32 and bool(L.iic_seg_head_supported(C, k))
+  Fm = None
+  if fused:
+    check(L.iic_seg_head_fwd(ptr(x), ptr(W2), ptr(logits), N, Hw, Ww, Hp, Wp, off, C, k, s), "iic_seg_head_fwd")
+  else:
+    Fm = torch.empty((M, C), dtype=F32, device=x.device)
+    if x.dtype == F32:      # exact-fp32 parity path
+      check(L.iic_f32_window_gather(ptr(x), ptr(Fm), N, Hw, Ww, Hp, Wp, off, C, s), "iic_f32_window_gather")
+    else:
+      check(L.iic_seg_window_gather(ptr(x), ptr(Fm), N, Hw, Ww, Hp, Wp, off, C, s), "iic_seg_window_gather")
+    ops.gemm_f32(Fm, C, 1, W2, 1, C, logits, k, M, k, C)
+  return ops.softmax_fwd(logits, M, k), Fm, W2, fused, (N, Hw, Ww, off, k)
+
+
+def _head_label_map(x, w, P, S):
+  """uint8 [N, S, S]: arg-max over classes of what _SegHeadFn.forward returns, without writing the [N, k, S, S] fp32
+  maps (csrc/seg_eval.hip: every class value is the number iic_bilinear_fwd stores; lowest index on a tie)."""
+  probs, _, _, _, (N, Hw, Ww, _, k) = _head_probs(x, w, P)
+  labels = torch.empty((N, S, S), dtype=torch.uint8, device=x.device)
+  check(lib().iic_seg_label_map(ptr(probs), ptr(labels), N, Hw, Ww, k, S, stream_ptr()), "iic_seg_label_map")
+  return labels
+
+
 class _SegHeadFn(torch.autograd.Function):
   """x: PT bf16 [N, Hf+2P, Wf+2P, C]; w: [k, C, 1, 1] -> probabilities [N, k, S, S] fp32."""
 
   @staticmethod
   def forward(ctx, x, w, P, S):
-    N, Hp, Wp, C = x.shape
-    Hw, Ww, off = Hp - 2 * P + 2, Wp - 2 * P + 2, P - 1
-    k = w.shape[0]
-    M = N * Hw * Ww
-    L, s = lib(), stream_ptr()
-    W2 = w.detach().reshape(k, C).contiguous()
-    logits = torch.empty((M, k), dtype=F32, device=x.device)
-    # fused path: the GEMMs read / write the bf16 window in place (csrc/seg_head.hip)
-    fused = FUSED_HEAD[0] and x.dtype != F32 and bool(L.iic_seg_head_supported(C, k))
-    Fm = None
-    if fused:
-      check(L.iic_seg_head_fwd(ptr(x), ptr(W2), ptr(logits), N, Hw, Ww, Hp, Wp, off, C, k, s), "iic_seg_head_fwd")
-    else:
-      Fm = torch.empty((M, C), dtype=F32, device=x.device)
-      if x.dtype == F32:      # exact-fp32 parity path
-        check(L.iic_f32_window_gather(ptr(x), ptr(Fm), N, Hw, Ww, Hp, Wp, off, C, s), "iic_f32_window_gather")
-      else:
-        check(L.iic_seg_window_gather(ptr(x), ptr(Fm), N, Hw, Ww, Hp, Wp, off, C, s), "iic_seg_window_gather")
-      ops.gemm_f32(Fm, C, 1, W2, 1, C, logits, k, M, k, C)
-    probs = ops.softmax_fwd(logits, M, k)
+    probs, Fm, W2, fused, (N, Hw, Ww, off, k) = _head_probs(x, w, P)
     out = torch.empty((N, k, S, S), dtype=F32, device=x.device)
-    check(L.iic_bilinear_fwd(ptr(probs), ptr(out), N, Hw, Ww, k, S, s), "iic_bilinear_fwd")
+    check(lib().iic_bilinear_fwd(ptr(probs), ptr(out), N, Hw, Ww, k, S, stream_ptr()), "iic_bilinear_fwd")
     ctx.save_for_backward(x if fused else Fm, W2, probs)
     ctx.fused = fused
     ctx.meta = (tuple(x.shape), P, S, Hw, Ww, off, k)
@@ -126,6 +142,10 @@ class SegmentationNet10aHead(nn.Module):
     return [_SegHeadFn.apply(x, ops.pv(self.heads[i][0].weight), SegmentationNet10aTrunk.P, self.input_sz)
             for i in range(self.num_sub_heads)]
 
+  def label_maps(self, x):
+    return [_head_label_map(x, ops.pv(self.heads[i][0].weight), SegmentationNet10aTrunk.P, self.input_sz)
+            for i in range(self.num_sub_heads)]
+
 
 class SegmentationNet10a(_ApplyCounter, nn.Module):
   cfg = [(64, 1), (128, 1), ("M", None), (256, 1), (256, 1), (512, 2), (512, 2)]
@@ -140,6 +160,17 @@ class SegmentationNet10a(_ApplyCounter, nn.Module):
   @ops.auto_branch
   def forward(self, x):
     return self.head(self.trunk(x))
+
+  def predict_labels(self, x):
+    """One uint8 [N, input_sz, input_sz] label map per sub-head: ``[o.argmax(1) for o in self(x)]`` without the fp32
+    probability maps (segmentation_eval.py:84, :100).  Inference only; follows the module's train / eval BatchNorm state
+    as forward does."""
+    assert not torch.is_grad_enabled(), "predict_labels is inference only: call it under torch.no_grad()"
+    return self._label_maps(x)
+
+  @ops.auto_branch
+  def _label_maps(self, x):
+    return self.head.label_maps(self.trunk(x))
 
 
 class SegmentationNet10aTwoHead(_ApplyCounter, nn.Module):
@@ -162,3 +193,13 @@ class SegmentationNet10aTwoHead(_ApplyCounter, nn.Module):
     elif head == "B":
       return self.head_B(x)
     raise AssertionError("head must be A or B")
+
+  def predict_labels(self, x, head="B"):
+    """SegmentationNet10a.predict_labels for the chosen head."""
+    assert not torch.is_grad_enabled(), "predict_labels is inference only: call it under torch.no_grad()"
+    assert head in ("A", "B"), "head must be A or B"
+    return self._label_maps(x, head=head)
+
+  @ops.auto_branch
+  def _label_maps(self, x, head="B"):
+    return (self.head_A if head == "A" else self.head_B).label_maps(self.trunk(x))

@@ -438,6 +438,32 @@ int iic_contingency(const long long* preds, const long long* targets, long n, in
 int iic_count_equal(const long long* a, const long long* b, long n, long long* count, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Segmentation evaluation on the device (csrc/seg_eval.hip).
+ *
+ * iic_seg_label_map -- replaces, for evaluation, the full-resolution probability maps of
+ * code/utils/segmentation/segmentation_eval.py:84 (x_outs = net(imgs), [N][k][S][S] fp32) and their
+ * torch.argmax at :100.  probs_nhwc: the low-resolution softmax [N][Hl][Wl][k] fp32 (what the head has
+ * before iic_bilinear_fwd); labels_u8: uint8 [N][S][S], the arg-max over classes of the bilinear
+ * up-sampling (F.interpolate, align_corners=False), lowest class index on a tie.  Every class value is
+ * the fp32 number iic_bilinear_fwd stores, so the labels equal the arg-max of its output bit for bit.
+ * 1 <= k <= 255 (segmentation_eval.py:49); any Hl, Wl, S.
+ *
+ * iic_seg_contingency_acc -- replaces the flat test-set arrays and their masked_select
+ * (segmentation_eval.py:101-106, :126-128), the widening to int64 in front of iic_contingency, the
+ * reorder loop of code/utils/cluster/cluster_eval.py:128-131, :216-217 and _acc (:132, :227): all of
+ * these are functions of one count matrix.  preds / targets / mask: uint8 [n], mask may be NULL (every
+ * sample selected).  counts: int64 [k_pred * k_gt + 1], ACCUMULATED (the caller zeroes it once): for
+ * every i with mask[i] != 0, counts[k_pred * k_gt] += 1 and, if preds[i] < k_pred and
+ * targets[i] < k_gt, counts[preds[i] * k_gt + targets[i]] += 1.  k_pred * k_gt <= 16384.  n = 0: no-op.
+ * Integer atomics: the result does not depend on arrival order.
+ * ------------------------------------------------------------------------------- */
+int iic_seg_label_map(const float* probs_nhwc, unsigned char* labels_u8, int N, int Hl, int Wl, int k, int S,
+                      void* stream);
+int iic_seg_contingency_acc(const unsigned char* preds_u8, const unsigned char* targets_u8,
+                            const unsigned char* mask_u8, long n, int k_pred, int k_gt, long long* counts,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Paired augmentation on the GPU -- replaces the per-sample PIL pipelines
  * of code/utils/cluster/transforms.py that the DataLoaders of code/utils/cluster/data.py:223-335
  * run on the host:
