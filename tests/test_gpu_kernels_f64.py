@@ -17,70 +17,10 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-U32 = 2.0 ** -24
-U16 = 2.0 ** -8
-SENTINEL = 7.0
+from tests.parity import (SENTINEL, U16, U32, _mask_act, _masked_g, _pow2_coef, assert_bits, assert_border,  # noqa: F401
+                          assert_within, bits, call, dev, interior, ok, pt_of, rnd)
+
 IIC_ERR_ARG = -1
-
-
-def dev():
-  assert torch.cuda.is_available(), "no GPU visible"
-  return torch.device("cuda:0")
-
-
-def call(name, *args):
-  from iic_amd import _lib
-  rc = getattr(_lib.lib(), name)(*[a.data_ptr() if torch.is_tensor(a) else a for a in args], _lib.stream_ptr())
-  torch.cuda.synchronize()
-  return rc
-
-
-def ok(name, *args):
-  from iic_amd import _lib
-  _lib.check(call(name, *args), name)
-
-
-def bits(t):
-  t = t.detach().cpu().contiguous()
-  return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def assert_bits(got, want, what):
-  got, want = bits(got), bits(want)
-  assert got.shape == want.shape, (what, got.shape, want.shape)
-  bad = got != want
-  assert not bool(bad.any()), "%s: %d elements differ, first at %s" % (what, int(bad.sum()), tuple(int(i) for i in bad.nonzero()[0]))
-
-
-def assert_within(got, ref, tol, what):
-  got, ref, tol = got.detach().cpu().double(), ref.double(), torch.as_tensor(tol).double()
-  err = (got - ref).abs()
-  bad = ~(err <= tol)
-  assert not bool(bad.any()), "%s: %d elements outside the bound; worst |err| / bound = %g" % (
-    what, int(bad.sum()), float((err / tol.clamp_min(1e-300)).nan_to_num(nan=float("inf")).max()))
-
-
-def rnd(rng, *shape):
-  return torch.from_numpy(rng.standard_normal(shape).astype(np.float32))
-
-
-def pt_of(x_nhwc, P, dtype, fill=0.0):
-  """[N, H, W, C] interior -> PT tensor [N, H+2P, W+2P, C] on the GPU, border = fill."""
-  n, h, w, c = x_nhwc.shape
-  out = torch.full((n, h + 2 * P, w + 2 * P, c), fill, dtype=dtype)
-  out[:, P:P + h, P:P + w] = x_nhwc.to(dtype)
-  return out.to(dev())
-
-
-def interior(pt, P):
-  return pt[:, P:pt.shape[1] - P, P:pt.shape[2] - P].cpu()
-
-
-def assert_border(pt, P, value, what):
-  m = torch.ones(pt.shape[1:3], dtype=torch.bool)
-  m[P:pt.shape[1] - P, P:pt.shape[2] - P] = False
-  b = pt.cpu().float()[:, m]
-  assert bool((b == value).all()), "%s: the PT border was written" % what
 
 
 POOL_SHAPES = [(5, 7, 7, 1, 512), (3, 3, 5, 2, 64), (1, 1, 1, 1, 64), (2, 13, 9, 1, 130)]
@@ -89,15 +29,6 @@ POOL_SHAPES = [(5, 7, 7, 1, 512), (3, 3, 5, 2, 64), (1, 1, 1, 1, 64), (2, 13, 9,
 # --------------------------------------------------------------------------------------
 # iic_avgpool_fwd / iic_avgpool_bwd (bf16 PT -> fp32 features) and their fp32 twins
 # --------------------------------------------------------------------------------------
-def _mask_act(rng, N, H, W, C):
-  act = rnd(rng, N, H, W, C)
-  flat = act.view(-1)
-  flat[0::7] = 0.0
-  flat[1::7] = -0.0
-  flat[2::7] = -abs(flat[2::7]) - 0.5
-  return act
-
-
 @pytest.mark.parametrize("fp32", [False, True])
 @pytest.mark.parametrize("N,H,W,P,C", POOL_SHAPES)
 def test_avgpool_forward_backward_vs_float64(N, H, W, P, C, fp32):
@@ -283,13 +214,6 @@ def test_f32_nchw_to_pt_is_the_permute(C, P):
 BN_SHAPES = [(6, 13, 13, 1, 128), (3, 3, 5, 2, 512), (1, 1, 1, 1, 64), (2, 20, 36, 2, 64)]
 
 
-def _pow2_coef(rng, C):
-  """scale, shift on powers of two / small dyadics: with y on multiples of 1/8 the mask expression scale*y + shift is
-  exact in fp32, fused or not."""
-  return torch.stack([torch.from_numpy(rng.choice([0.5, 1.0, 2.0, -1.0, -0.5], C)),
-                      torch.from_numpy(rng.choice([0.0, 0.25, -0.25, 0.5, -1.0], C))]).float()
-
-
 def _bn_inputs(N, H, W, P, C):
   rng = np.random.default_rng(N * 7 + C)
   y = torch.round(rnd(rng, N, H, W, C) * 8) / 8
@@ -318,14 +242,6 @@ def test_f32_bn_apply_vs_float64(N, H, W, P, C):
       v, A = v + y2.double() * c2[0] + c2[1], A + (y2.double() * c2[0]).abs() + c2[1].abs()
     assert_within(interior(out, P), v.clamp_min(0) if relu else v, 6 * U32 * A, "bn_apply relu=%d res=%d y2=%d" % (relu, use_res, use_y2))
     assert_border(out, P, SENTINEL, "bn_apply")
-
-
-def _masked_g(dout, act, y, mcoef, mode):
-  if mode == "act":
-    return torch.where(act > 0, dout, torch.zeros_like(dout))
-  if mode == "mask_coef":
-    return torch.where(y * mcoef[0] + mcoef[1] > 0, dout, torch.zeros_like(dout))
-  return dout
 
 
 @pytest.mark.parametrize("N,H,W,P,C", BN_SHAPES)
