@@ -199,26 +199,15 @@ int iic_augment(const void* imgs_u8, int B, int H, int W, int channels, const in
   const size_t lds = ((size_t)(max_crop * S * channels + 15) & ~(size_t)15) + (size_t)S * S * channels;
   if (lds > 150 * 1024) return IIC_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
+  // (the kernel's static s_red comes on top of the dynamic LDS: lds stays below the workgroup's total, see above)
 #define AUG_LAUNCH(CH_, RGB_)                                                                     \
-  do {                                                                                           \
-    static bool attr = false; /* one-time: raise the dynamic LDS limit (static s_red on top) */   \
-    if (!attr) {                                                                                 \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&augment_kernel<CH_, RGB_>),         \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) !=         \
-          hipSuccess) {                                                                          \
-        (void)hipGetLastError();                                                                 \
-        return IIC_ERR_UNSUPPORTED;                                                              \
-      }                                                                                          \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL((augment_kernel<CH_, RGB_>), dim3(N), dim3(256), lds, s,                   \
-                       (const uint8_t*)imgs_u8, H, W, iparams, fparams, tabs, bounds, kk, S, lut, \
-                       out, norm);                                                               \
-  } while (0)
+  rc = iic_launch_lds<augment_kernel<CH_, RGB_>>(dim3(N), dim3(256), lds, s, (const uint8_t*)imgs_u8, H, W, \
+                                                 iparams, fparams, tabs, bounds, kk, S, lut, out, norm)
   if (channels == 1) AUG_LAUNCH(1, false);
   else if (include_rgb) AUG_LAUNCH(3, true);
   else AUG_LAUNCH(3, false);
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }
 
 }  // extern "C"

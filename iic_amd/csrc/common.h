@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <mutex>
+#include <utility>
+
 #define IIC_OK 0
 #define IIC_ERR_ARG (-1)
 #define IIC_ERR_LAUNCH (-2)
@@ -38,6 +42,37 @@ typedef uint16_t bf16_t;  // storage type for bf16 in HBM / LDS
 static inline int iic_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? IIC_OK : IIC_ERR_LAUNCH;
+}
+
+// LDS of one gfx950 workgroup: the ceiling of every launch's static + dynamic LDS
+static constexpr long IIC_LDS_BYTES = 160 * 1024;
+
+// The one way to launch a kernel whose dynamic LDS may exceed the 48 KB a kernel gets by default.  Every
+// instantiation remembers the largest limit it has been given and raises it only when a launch needs more (to that
+// launch's size: kernels with static LDS on top stay below the workgroup total), so the usual launch costs one
+// load and no runtime call.  Raising is serialised and re-checked under a lock: the record only grows, hence a
+// thread that reads it without the lock never launches above the limit in force.  Returns IIC_ERR_UNSUPPORTED,
+// with nothing launched and the error cleared, when the device refuses the size; IIC_OK otherwise -- the launch
+// itself is reported by the caller's iic_launch_status(), as for every other kernel.
+// `inline`, not `static`: one record per kernel in the library, whichever files launch it.  The record is per process
+// while the limit belongs to the kernel on the current device: a process drives one GPU.
+template <auto Kernel, typename... Args>
+inline int iic_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args&&... args) {
+  static std::atomic<size_t> limit{48 * 1024};
+  if (lds > limit.load(std::memory_order_acquire)) {
+    static std::mutex raise;
+    std::lock_guard<std::mutex> lock(raise);
+    if (lds > limit.load(std::memory_order_relaxed)) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return IIC_ERR_UNSUPPORTED;
+      }
+      limit.store(lds, std::memory_order_release);
+    }
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, std::forward<Args>(args)...);
+  return IIC_OK;
 }
 
 // Zero-fill as a KERNEL node rather than hipMemsetAsync: inside a captured HIP graph, ROCm 7.0's

@@ -333,23 +333,14 @@ int iic_conv_igemm(const iic_conv_geom* g, const void* in, const void* w, void* 
   const int mt = (int)((M + BMv - 1) / BMv);
   const int grid = mt * (g->Cout / BN);
   const long lds = lds_total(g, BN, BMv);
-  if (lds > 160 * 1024) return IIC_ERR_UNSUPPORTED;
+  if (lds > IIC_LDS_BYTES) return IIC_ERR_UNSUPPORTED;
   const int la = (int)lds_a_bytes_for(g, BN, BMv);
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
 #define IGEMM_LAUNCH3(BN_, GA_, AB_, BM_)                                                         \
-  do {                                                                                           \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      (void)hipFuncSetAttribute(                                                                 \
-          reinterpret_cast<const void*>(&conv_igemm_kernel<BN_, GA_, AB_, BM_>),                 \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                               \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL((conv_igemm_kernel<BN_, GA_, AB_, BM_>), dim3(grid), dim3(BM_ * 2), lds,  \
-                       s, *g, (const bf16_t*)in, (const bf16_t*)w, (bf16_t*)out, stats,          \
-                       (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, mt, la,      \
-                       g_ablate);                                                                \
-  } while (0)
+  rc = iic_launch_lds<conv_igemm_kernel<BN_, GA_, AB_, BM_>>(                                    \
+      dim3(grid), dim3(BM_ * 2), lds, s, *g, (const bf16_t*)in, (const bf16_t*)w, (bf16_t*)out,  \
+      stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, mt, la, g_ablate)
 #define IGEMM_LAUNCH(BN_, GA_)                                                                   \
   do {                                                                                           \
     if (g_ablate) IGEMM_LAUNCH3(BN_, GA_, true, 128);                                            \
@@ -362,7 +353,7 @@ int iic_conv_igemm(const iic_conv_geom* g, const void* in, const void* w, void* 
   } else {
     if (ga) IGEMM_LAUNCH(64, true); else IGEMM_LAUNCH(64, false);
   }
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }
 
 int iic_weight_prep(const float* w_oihw, void* w_fwd, void* w_bwd, int Cout, int Cin, int T,

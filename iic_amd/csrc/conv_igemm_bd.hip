@@ -535,15 +535,15 @@ static long bd_lds_total(const iic_conv_geom* g, int ms, int wn = 2) {
 IIC_SWITCH(g_bd_w1, 1, iic_debug_bd_w1)
 static bool bd_w1_ok(const iic_conv_geom* g) {
   return g_bd_w1 && g->Cout % 64 == 0 && g->Cout % BD_BN != 0 && g->ntaps > 1 && g->NP256 > 0 &&
-         bd_lds_total(g, 2, 1) <= 160 * 1024;
+         bd_lds_total(g, 2, 1) <= IIC_LDS_BYTES;
 }
 // Tile height per geometry.  g_bd_ms: 0 = heuristic, 2 / 4 = forced (A/B runs, tests).
 IIC_SWITCH(g_bd_ms, 0, iic_debug_bd_ms)
 static int bd_pick_ms(const iic_conv_geom* g) {
   // (256-row tiles also where only one workgroup fits a CU: large-image segmentation layers, still 15-20 % faster
   // than conv_igemm_kernel)
-  const bool ok4 = (g->ntaps == 1 || g->NP256 > 0) && bd_lds_total(g, 4) <= 160 * 1024;
-  const bool ok2 = (g->ntaps == 1 || g->NP > 0) && bd_lds_total(g, 2) <= 160 * 1024;
+  const bool ok4 = (g->ntaps == 1 || g->NP256 > 0) && bd_lds_total(g, 4) <= IIC_LDS_BYTES;
+  const bool ok2 = (g->ntaps == 1 || g->NP > 0) && bd_lds_total(g, 2) <= IIC_LDS_BYTES;
   if (g_bd_ms == 4) return ok4 ? 4 : (ok2 ? 2 : 0);
   if (g_bd_ms == 2) return ok2 ? 2 : (ok4 ? 4 : 0);
   // small launches (a rank's share of the batch under strong scaling: tools/pairs_sweep.sh): when the 256-row tiles
@@ -668,23 +668,15 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
       lds1 = la1 + 2L * BD_BM * 4 + 4L * BD_BN * 4 + ((B1.npix + 15) & ~15L);
     }
     hipStream_t s1 = (hipStream_t)stream;
+    int rc1 = IIC_OK;
 #define BD_LAUNCH_W1(RD_)                                                                              \
-  do {                                                                                                 \
-    static bool attr = false;                                                                          \
-    if (!attr) {                                                                                       \
-      (void)hipFuncSetAttribute(                                                                       \
-          reinterpret_cast<const void*>(&conv_igemm_bd_kernel<false, 0, 2, RD_, 1>),          \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                     \
-      attr = true;                                                                                     \
-    }                                                                                                  \
-    hipLaunchKernelGGL((conv_igemm_bd_kernel<false, 0, 2, RD_, 1>), dim3(grid1),              \
-                       dim3(BD_THREADS), lds1, s1, *g, (const bf16_t*)in, (const unsigned char*)wfrag, \
-                       (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act,           \
-                       accumulate, mt1, la1, (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2,    \
-                       red_stats, red_stats2, (unsigned long long*)nullptr, B1);                       \
-  } while (0)
+  rc1 = iic_launch_lds<conv_igemm_bd_kernel<false, 0, 2, RD_, 1>>(                                     \
+      dim3(grid1), dim3(BD_THREADS), lds1, s1, *g, (const bf16_t*)in, (const unsigned char*)wfrag,     \
+      (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, mt1, la1,      \
+      (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2, red_stats, red_stats2,                    \
+      (unsigned long long*)nullptr, B1)
     if (red == 0) BD_LAUNCH_W1(0); else if (red == 1) BD_LAUNCH_W1(1); else BD_LAUNCH_W1(2);
-    return iic_launch_status();
+    return rc1 ? rc1 : iic_launch_status();
   }
   bd_blk BB = {0, 0, 0, 0, 0, 0, 0};
   const bool blocked = iic_debug_get_ablate() == 0 && bd_block_config(g, &BB, 2) != 0;
@@ -702,21 +694,12 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
     lds = la + 2L * BD_BM * 4 + 4L * BD_BN * 4 + ((BB.npix + 15) & ~15L);
   }
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
 #define BD_LAUNCH4(GA_, AB_, MS_, RD_)                                                            \
-  do {                                                                                           \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      (void)hipFuncSetAttribute(                                                                 \
-          reinterpret_cast<const void*>(&conv_igemm_bd_kernel<GA_, AB_, MS_, RD_>),              \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                               \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL((conv_igemm_bd_kernel<GA_, AB_, MS_, RD_>), dim3(grid),                   \
-                       dim3(BD_THREADS), lds, s, *g, (const bf16_t*)in,                          \
-                       (const unsigned char*)wfrag, (bf16_t*)out, stats, (const bf16_t*)res_grad, \
-                       (const bf16_t*)res_act, accumulate, mt, la, (const bf16_t*)red_y,         \
-                       red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_bd_prof, BB);   \
-  } while (0)
+  rc = iic_launch_lds<conv_igemm_bd_kernel<GA_, AB_, MS_, RD_>>(                                 \
+      dim3(grid), dim3(BD_THREADS), lds, s, *g, (const bf16_t*)in, (const unsigned char*)wfrag,  \
+      (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, mt, la,  \
+      (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_bd_prof, BB)
 #define BD_LAUNCH3(GA_, AB_, MS_)                                                                 \
   do {                                                                                           \
     if ((AB_ != 0 && AB_ != 128 && AB_ != 256) || GA_ || red == 0) {                             \
@@ -751,7 +734,7 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
 #endif
     default: BD_LAUNCH(false, 0); break;
   }
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }
 
 // All weight operands of a network in ONE launch (jobs in device memory, see iic_weight_prep_job): a train step

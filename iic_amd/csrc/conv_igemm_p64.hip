@@ -367,7 +367,7 @@ static long p64_pb_bytes(const iic_conv_geom* g, int bm = P64_BM) {
 int iic_p64_supported(const iic_conv_geom* g) {
   if (g->Cin != 64 || g->Cout != 64 || g->ntaps != P64_NT || g->NP256 <= 0 || g->NP256 > 65535) return 0;
   if (!igemm_dense_host(g)) return 0;       // the row walkers assume the dense row numbering
-  return 2 * p64_pb_bytes(g) + P64_SC_BYTES(P64_BM) + P64_TAB_BYTES(P64_BM) <= 160 * 1024;
+  return 2 * p64_pb_bytes(g) + P64_SC_BYTES(P64_BM) + P64_TAB_BYTES(P64_BM) <= IIC_LDS_BYTES;
 }
 
 int iic_p64_launch(const iic_conv_geom* g, const void* in, const void* wfrag, void* out, float* stats,
@@ -386,34 +386,29 @@ int iic_p64_launch(const iic_conv_geom* g, const void* in, const void* wfrag, vo
   for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
   const int ncu = p64_num_cus();
   const int grid = nt < ncu ? nt : ncu;
+  int rc = IIC_OK;
 #define P64_LAUNCH2(AB_, RD_)                                                                          \
-  do {                                                                                                 \
-    static bool attr = false;                                                                          \
-    if (!attr) {                                                                                       \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_p64_kernel<AB_, RD_>),       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);               \
-      attr = true;                                                                                     \
-    }                                                                                                  \
-    hipLaunchKernelGGL((conv_igemm_p64_kernel<AB_, RD_>), dim3(grid), dim3(512), lds,                  \
-                       (hipStream_t)stream, *g, (const bf16_t*)in, (const unsigned char*)wfrag,   \
-                       (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act,      \
-                       accumulate, nt, pb, mto, (const bf16_t*)red_y, red_coef,                   \
-                       (const bf16_t*)red_y2, red_stats, red_stats2, g_p64_prof);                 \
-  } while (0)
+  rc = iic_launch_lds<conv_igemm_p64_kernel<AB_, RD_>>(                                                \
+      dim3(grid), dim3(512), lds, (hipStream_t)stream, *g, (const bf16_t*)in,                          \
+      (const unsigned char*)wfrag, (bf16_t*)out, stats, (const bf16_t*)res_grad,                       \
+      (const bf16_t*)res_act, accumulate, nt, pb, mto, (const bf16_t*)red_y, red_coef,                 \
+      (const bf16_t*)red_y2, red_stats, red_stats2, g_p64_prof)
 #define P64_LAUNCH(AB_) P64_LAUNCH2(AB_, 0)
-  if (red == 1) { P64_LAUNCH2(0, 1); return iic_launch_status(); }
-  if (red == 2) { P64_LAUNCH2(0, 2); return iic_launch_status(); }
-  switch (iic_debug_get_ablate()) {
+  if (red == 1) P64_LAUNCH2(0, 1);
+  else if (red == 2) P64_LAUNCH2(0, 2);
+  else {
+    switch (iic_debug_get_ablate()) {
 #ifdef IIC_BD_ABLATIONS
-    // timing-ablation / phase-profile instantiations (tools/p64_phases.py): `make -C iic_amd/csrc ABL=1` only
-    case 1: P64_LAUNCH(1); break;
-    case 2: P64_LAUNCH(2); break;
-    case 3: P64_LAUNCH(3); break;
-    case 4: P64_LAUNCH(4); break;
-    case 7: P64_LAUNCH(7); break;
-    case 8: P64_LAUNCH(8); break;
+      // timing-ablation / phase-profile instantiations (tools/p64_phases.py): `make -C iic_amd/csrc ABL=1` only
+      case 1: P64_LAUNCH(1); break;
+      case 2: P64_LAUNCH(2); break;
+      case 3: P64_LAUNCH(3); break;
+      case 4: P64_LAUNCH(4); break;
+      case 7: P64_LAUNCH(7); break;
+      case 8: P64_LAUNCH(8); break;
 #endif
-    default: P64_LAUNCH(0); break;
+      default: P64_LAUNCH(0); break;
+    }
   }
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }

@@ -692,25 +692,18 @@ int iic_pw_launch(const iic_conv_geom* g, const void* in, const void* wfrag, voi
   const int grid = pw_grid(g, lds);
   const int red = red_y ? (red_y2 ? 2 : 1) : 0;
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
 #define PW_LAUNCH(RD_, PR_)                                                                                   \
-  do {                                                                                                        \
-    static bool attr = false;                                                                                 \
-    if (!attr) {                                                                                              \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_pw_kernel<RD_, PR_>),               \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                      \
-      attr = true;                                                                                            \
-    }                                                                                                         \
-    hipLaunchKernelGGL((conv_igemm_pw_kernel<RD_, PR_>), dim3(grid), dim3(PW_THREADS), lds, s, *g, A,         \
-                       (const bf16_t*)in, (const unsigned char*)wfrag, (bf16_t*)out, stats,                   \
-                       (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, (const bf16_t*)red_y,     \
-                       red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_pw_prof);                    \
-  } while (0)
+  rc = iic_launch_lds<conv_igemm_pw_kernel<RD_, PR_>>(                                                        \
+      dim3(grid), dim3(PW_THREADS), lds, s, *g, A, (const bf16_t*)in, (const unsigned char*)wfrag,            \
+      (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, (const bf16_t*)red_y, \
+      red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_pw_prof)
 #ifdef IIC_DEBUG_HOOKS
   if (g_pw_prof) {
     if (red == 0) PW_LAUNCH(0, true); else if (red == 1) PW_LAUNCH(1, true); else PW_LAUNCH(2, true);
-    return iic_launch_status();
+    return rc ? rc : iic_launch_status();
   }
 #endif
   if (red == 0) PW_LAUNCH(0, false); else if (red == 1) PW_LAUNCH(1, false); else PW_LAUNCH(2, false);
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }

@@ -377,28 +377,21 @@ int iic_conv_wgrad(const iic_conv_geom* g, const void* x, const void* dy, float*
   const int cot = wgrad_cot(g);
   const int lx = ((ga ? BM : g->NP) * ROWB + 15) & ~15;
   const long lds = (long)lx + BM * (cot == 64 ? 144 : 288) + 4 * BM * 4;
-  if (lds > 160 * 1024) return IIC_ERR_UNSUPPORTED;
+  if (lds > IIC_LDS_BYTES) return IIC_ERR_UNSUPPORTED;
   dim3 grid((g->Cout / cot) * (g->Cin / 64), nsplit, ga ? g->ntaps : (g->ntaps + NTG * TPG - 1) / (NTG * TPG));
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
 #define WGRAD_LAUNCH(TR_, GA_, COT_)                                                            \
-  do {                                                                                          \
-    static bool attr = false;                                                                   \
-    if (!attr) {                                                                                \
-      (void)hipFuncSetAttribute(                                                                \
-          reinterpret_cast<const void*>(&conv_wgrad_kernel<TR_, GA_, COT_>),                    \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                              \
-      attr = true;                                                                              \
-    }                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_kernel<TR_, GA_, COT_>), grid, dim3(GA_ ? 256 : 768), lds,   \
-                       s, *g, (const bf16_t*)x, (const bf16_t*)dy, partials, nsplit, kt, lx);   \
-  } while (0)
+  rc = iic_launch_lds<conv_wgrad_kernel<TR_, GA_, COT_>>(grid, dim3(GA_ ? 256 : 768), lds, s,   \
+                                                         *g, (const bf16_t*)x, (const bf16_t*)dy, \
+                                                         partials, nsplit, kt, lx)
 #define WGRAD_LAUNCH2(TR_, GA_)                                                                 \
   do {                                                                                          \
     if (cot == 128) WGRAD_LAUNCH(TR_, GA_, 128); else WGRAD_LAUNCH(TR_, GA_, 64);               \
   } while (0)
   if (use_tr) { if (ga) WGRAD_LAUNCH2(true, true); else WGRAD_LAUNCH2(true, false); }
   else        { if (ga) WGRAD_LAUNCH2(false, true); else WGRAD_LAUNCH2(false, false); }
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }
 
 int iic_conv_wgrad_reduce(const float* partials, int nsplit, int T, int Cout, int Cin, float* dW,

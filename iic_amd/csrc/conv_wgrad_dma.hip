@@ -1168,7 +1168,7 @@ static int wd_config(const iic_conv_geom* g, int* bmk, int* nbuf) {
   if (g->ntaps != 9 || g->Cin % 64 != 0 || g->Cout % 64 != 0 || g->NP <= 0 || g->NP > 65535) return 0;
   if (g->MP > 0 && g->MP % 128 != 0) return 0;         // padded numbering: K-tiles must not straddle images
   const int cot = (g->Cout % 128 == 0) ? 128 : 64;
-  if (g_wd_enabled != 3 && wd_lds(g->NP, cot, 128, 2) <= 160 * 1024) {
+  if (g_wd_enabled != 3 && wd_lds(g->NP, cot, 128, 2) <= IIC_LDS_BYTES) {
     *bmk = 128;
     *nbuf = 2;
     return 1;
@@ -1180,7 +1180,7 @@ static int wd_config(const iic_conv_geom* g, int* bmk, int* nbuf) {
   if (g->NP64 > 0) {
     // (2 buffers: the stride-2 layers, whose 64-row patch spans 330-440 input pixels)
     for (int nb = 4; nb >= 2; --nb)
-      if (wd_lds(g->NP64, cot, 64, nb) <= 160 * 1024) {
+      if (wd_lds(g->NP64, cot, 64, nb) <= IIC_LDS_BYTES) {
         *bmk = 64;
         *nbuf = nb;
         return 1;
@@ -1221,7 +1221,7 @@ static int wdp_config(const iic_conv_geom* g, int* bmk, int* nbuf, int* ntab, in
   if (!txs) return 0;
   if ((long)g->N * g->out_Hp * g->out_Wp * g->Cout * 2 >= (1L << 32)) return 0;
   const int cot = (g->Cout % 128 == 0) ? 128 : 64;
-  const long lim = 160 * 1024;
+  const long lim = IIC_LDS_BYTES;
   if (g_wd_enabled != 3 && (g->MP <= 0 || g->MP % 128 == 0)) {
     for (int nt = 8; nt >= 4; nt >>= 1)
       if (wdp_lds(g->NP, cot, 128, 2, nt) <= lim) { *bmk = 128; *nbuf = 2; *ntab = nt; return 1; }
@@ -1279,7 +1279,7 @@ static int wdb_config(const iic_conv_geom* g, wdb_args* A) {
     const int patch = (bw + 2 * txs) * (bh + 2 * drow);
     const long plane = wdp_plane_bytes(patch);
     if ((2 * ((patch + 15) >> 4) + 32 + 11) / 12 > WDB_MAXNI) continue;
-    if (2L * (2L * plane + 128 * 256) > 160 * 1024) continue;
+    if (2L * (2L * plane + 128 * 256) > IIC_LDS_BYTES) continue;
     const double cost = (double)tiles * (1.0 + 0.5 * ((double)patch * 128.0 + 32768.0) / 65536.0);
     if (best < 0 || cost < best) { best = cost; best_tiles = tiles; best_bw = bw; }
   }
@@ -1325,22 +1325,15 @@ int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, 
   for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
   dim3 grid((g->Cout / cot) * (g->Cin / 64), nsplit);
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
   wdb_args BA;
   if (wdb_config(g, &BA)) {                            // block-tiled kernel (large images)
     const long ldsb = 2L * (2L * BA.plane_bytes + 128 * 256);
-#define WDB_LAUNCH(TXS_)                                                                          \
-  do {                                                                                          \
-    static bool attr = false;                                                                   \
-    if (!attr) {                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_b2d_kernel<TXS_>),    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
-      attr = true;                                                                              \
-    }                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_b2d_kernel<TXS_>), grid, dim3(WD_THREADS), ldsb, s, *g,      \
-                       (const bf16_t*)x, (const bf16_t*)dy, partials, nsplit, BA, g_wd_ablate); \
-  } while (0)
+#define WDB_LAUNCH(TXS_)                                                                         \
+  rc = iic_launch_lds<conv_wgrad_b2d_kernel<TXS_>>(grid, dim3(WD_THREADS), ldsb, s, *g, (const bf16_t*)x, \
+                                                   (const bf16_t*)dy, partials, nsplit, BA, g_wd_ablate)
     if (wdp_txs(g) == 1) WDB_LAUNCH(1); else WDB_LAUNCH(2);
-    return iic_launch_status();
+    return rc ? rc : iic_launch_status();
   }
   int pbmk = 0, pnbuf = 0, pntab = 0, pband = 0;
   if (wdp_config(g, &pbmk, &pnbuf, &pntab, &pband)) {  // planar-patch kernels
@@ -1351,31 +1344,13 @@ int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, 
     const int plane = (int)wdp_plane_bytes(np);
     const long ldsp = wdp_lds(np, cot, pbmk, pnbuf, pntab);
 #define WDP_LAUNCH3(COT_, BMK_, NBUF_, TXS_, ASM_, NTAB_)                                        \
-  do {                                                                                          \
-    static bool attr = false;                                                                   \
-    if (!attr) {                                                                                \
-      (void)hipFuncSetAttribute(                                                                \
-          reinterpret_cast<const void*>(&conv_wgrad_pl_kernel<COT_, BMK_, NBUF_, TXS_, ASM_, NTAB_>), \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                              \
-      attr = true;                                                                              \
-    }                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_pl_kernel<COT_, BMK_, NBUF_, TXS_, ASM_, NTAB_>), grid,      \
-                       dim3(WD_THREADS), ldsp, s, *g, (const bf16_t*)x, (const bf16_t*)dy,      \
-                       partials, nsplit, kt, plane, mto, g_wd_ablate, pband, bstride);          \
-  } while (0)
+  rc = iic_launch_lds<conv_wgrad_pl_kernel<COT_, BMK_, NBUF_, TXS_, ASM_, NTAB_>>(              \
+      grid, dim3(WD_THREADS), ldsp, s, *g, (const bf16_t*)x, (const bf16_t*)dy, partials, nsplit, kt, plane, mto, \
+      g_wd_ablate, pband, bstride)
 #define WDP2_LAUNCH3(COT_, BMK_, NBUF_, TXS_, NTAB_)                                             \
-  do {                                                                                          \
-    static bool attr = false;                                                                   \
-    if (!attr) {                                                                                \
-      (void)hipFuncSetAttribute(                                                                \
-          reinterpret_cast<const void*>(&conv_wgrad_pl2_kernel<COT_, BMK_, NBUF_, TXS_, NTAB_>), \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                              \
-      attr = true;                                                                              \
-    }                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_pl2_kernel<COT_, BMK_, NBUF_, TXS_, NTAB_>), grid,           \
-                       dim3(WD_THREADS), ldsp, s, *g, (const bf16_t*)x, (const bf16_t*)dy,      \
-                       partials, nsplit, kt, plane, mto, g_wd_ablate, pband, bstride);          \
-  } while (0)
+  rc = iic_launch_lds<conv_wgrad_pl2_kernel<COT_, BMK_, NBUF_, TXS_, NTAB_>>(                   \
+      grid, dim3(WD_THREADS), ldsp, s, *g, (const bf16_t*)x, (const bf16_t*)dy, partials, nsplit, kt, plane, mto, \
+      g_wd_ablate, pband, bstride)
 #ifdef IIC_DEBUG_HOOKS
 #define WDP_LAUNCH2(COT_, BMK_, NBUF_, TXS_, NTAB_)                                              \
   do {                                                                                          \
@@ -1400,7 +1375,7 @@ int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, 
     else if (pnbuf == 3) WDP_LAUNCH(64, 3, 8);
     else if (pntab == 8) WDP_LAUNCH(64, 2, 8);
     else WDP_LAUNCH(64, 2, 4);
-    return iic_launch_status();
+    return rc ? rc : iic_launch_status();
   }
   int bmk = 0, nbuf = 0;
   if (!wd_config(g, &bmk, &nbuf)) return IIC_ERR_UNSUPPORTED;
@@ -1409,16 +1384,9 @@ int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, 
   const int xb = (int)wd_xb_bytes(np);
   const long lds = wd_lds(np, cot, bmk, nbuf);
 #define WD_LAUNCH(COT_, BMK_, NBUF_)                                                             \
-  do {                                                                                          \
-    static bool attr = false;                                                                   \
-    if (!attr) {                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_dma_kernel<COT_, BMK_, NBUF_>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
-      attr = true;                                                                              \
-    }                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_dma_kernel<COT_, BMK_, NBUF_>), grid, dim3(WD_THREADS), lds, s, *g, \
-                       (const bf16_t*)x, (const bf16_t*)dy, partials, nsplit, kt, xb, mto, g_wd_ablate); \
-  } while (0)
+  rc = iic_launch_lds<conv_wgrad_dma_kernel<COT_, BMK_, NBUF_>>(grid, dim3(WD_THREADS), lds, s, *g, (const bf16_t*)x, \
+                                                                (const bf16_t*)dy, partials, nsplit, kt, xb, mto,     \
+                                                                g_wd_ablate)
   if (bmk == 64 && nbuf == 4) {
     if (cot == 128) WD_LAUNCH(128, 64, 4); else WD_LAUNCH(64, 64, 4);
   } else if (bmk == 64 && nbuf == 3) {
@@ -1428,5 +1396,5 @@ int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, 
   } else {
     if (cot == 128) WD_LAUNCH(128, 128, 2); else WD_LAUNCH(64, 128, 2);
   }
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }

@@ -473,16 +473,6 @@ static int fc2_setup(fc2_args* a, const void* p0, const void* p1, int N, int Cin
   return 1;
 }
 
-#define FC2_ATTR(KERNEL)                                                                          \
-  do {                                                                                            \
-    static bool attr = false;                                                                     \
-    if (!attr) {                                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL),                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);          \
-      attr = true;                                                                                \
-    }                                                                                             \
-  } while (0)
-
 // IIC_ERR_UNSUPPORTED: the caller (vgg.hip) runs the first-generation kernel
 int fc2_fwd_launch(const float* x, const float* w, void* out_pt, float* stats, int N, int Cin, int H, int W, int K,
                    int pad, int P, int max_blocks, void* stream) {
@@ -500,12 +490,10 @@ int fc2_fwd_launch(const float* x, const float* w, void* out_pt, float* stats, i
   if (max_blocks > 512) max_blocks = 512;
   const int grid = (int)(nb < max_blocks ? nb : max_blocks);
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
 #define FC2F2(KS_, NPF_)                                                                          \
-  do {                                                                                            \
-    FC2_ATTR((firstconv_fwd2_kernel<KS_, NPF_>));                                                 \
-    hipLaunchKernelGGL((firstconv_fwd2_kernel<KS_, NPF_>), dim3(grid), dim3(256), lds, s, a, x, w, \
-                       (bf16_t*)out_pt, stats);                                                   \
-  } while (0)
+  rc = iic_launch_lds<firstconv_fwd2_kernel<KS_, NPF_>>(dim3(grid), dim3(256), lds, s, a, x, w,   \
+                                                        (bf16_t*)out_pt, stats)
 #define FC2F(KS_)                                                                                 \
   do {                                                                                            \
     if (npf == 2) FC2F2(KS_, 2); else if (npf <= 4) FC2F2(KS_, 4); else if (npf == 5) FC2F2(KS_, 5); \
@@ -520,7 +508,7 @@ int fc2_fwd_launch(const float* x, const float* w, void* out_pt, float* stats, i
   }
 #undef FC2F
 #undef FC2F2
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }
 
 // *grid_out workgroups wrote partials [block][64][*ld_out]; the caller folds them (fc_wgrad_reduce_kernel, vgg.hip)
@@ -539,12 +527,10 @@ int fc2_wgrad_launch(const float* x, const void* dy_pt, float* partials, int N, 
   const long nb = (long)N * a.bpi;
   const int grid = (int)(nb < max_blocks ? nb : max_blocks);
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
 #define FC2W2(NK, NPF_)                                                                           \
-  do {                                                                                            \
-    FC2_ATTR((firstconv_wgrad2_kernel<NK, NPF_>));                                                \
-    hipLaunchKernelGGL((firstconv_wgrad2_kernel<NK, NPF_>), dim3(grid), dim3(256), lds, s, a, x,  \
-                       (const bf16_t*)dy_pt, partials);                                           \
-  } while (0)
+  rc = iic_launch_lds<firstconv_wgrad2_kernel<NK, NPF_>>(dim3(grid), dim3(256), lds, s, a, x,     \
+                                                         (const bf16_t*)dy_pt, partials)
 #define FC2W(NK)                                                                                  \
   do {                                                                                            \
     if (npf == 2) FC2W2(NK, 2); else if (npf <= 4) FC2W2(NK, 4); else if (npf <= 6) FC2W2(NK, 6); \
@@ -563,6 +549,7 @@ int fc2_wgrad_launch(const float* x, const void* dy_pt, float* partials, int N, 
   }
 #undef FC2W
 #undef FC2W2
+  if (rc) return rc;
   *grid_out = grid;
   *ld_out = LD;
   return iic_launch_status();

@@ -548,27 +548,19 @@ int iic_gemm_f32_ws(const float* A, long sam, long sak, const float* B, long sbk
     const int T = big ? 128 : 64;
     dim3 tg((M + T - 1) / T, (Nn + T - 1) / T, S);
     const size_t lds128 = (size_t)4 * 32 * 129 * sizeof(float);
-    if (big) {
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_tiled128_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_tiled128_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_tiled128_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_tiled128_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128);
-        attr = true;
-      }
-    }
+    int rc = IIC_OK;
 #define GT_LAUNCH(AK_, BK_)                                                                          \
     do {                                                                                             \
       if (big)                                                                                       \
-        hipLaunchKernelGGL((gemm_f32_tiled128_kernel<AK_, BK_>), tg, dim3(256), lds128, (hipStream_t)stream, \
-                           A, sam, sak, B, sbk, sbn, bias, C, scm, M, Nn, K, accumulate, ws);        \
+        rc = iic_launch_lds<gemm_f32_tiled128_kernel<AK_, BK_>>(tg, dim3(256), lds128, (hipStream_t)stream, A, sam, \
+                                                                sak, B, sbk, sbn, bias, C, scm, M, Nn, K, accumulate, ws); \
       else                                                                                           \
         hipLaunchKernelGGL((gemm_f32_tiled_kernel<AK_, BK_>), tg, dim3(256), 0, (hipStream_t)stream, \
                            A, sam, sak, B, sbk, sbn, bias, C, scm, M, Nn, K, accumulate, ws);        \
     } while (0)
     if (sak == 1) { if (sbk == 1) GT_LAUNCH(true, true); else GT_LAUNCH(true, false); }
     else { if (sbk == 1) GT_LAUNCH(false, true); else GT_LAUNCH(false, false); }
+    if (rc) return rc;
     if (S > 1) {
       const long mn = (long)M * Nn;
       hipLaunchKernelGGL(gemm_f32_fold_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0,

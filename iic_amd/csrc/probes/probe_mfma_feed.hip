@@ -232,19 +232,17 @@ extern "C" int iic_debug_mfma_feed(int stage_var, int grid, int nit, int chunk_i
                                    const void* wfrag, long wfrag_bytes, const void* patch, void* out,
                                    void* clk, void* stream) {
   if (grid <= 0 || nit <= 0 || chunk_its <= 0 || npix < 256 + 32 || lds_bytes < npix * 128 ||
-      lds_bytes < 256 * 136 * 2 || lds_bytes > 160 * 1024 || wfrag_bytes < 65536 || (wfrag_bytes & (wfrag_bytes - 1)))
+      lds_bytes < 256 * 136 * 2 || lds_bytes > IIC_LDS_BYTES || wfrag_bytes < 65536 || (wfrag_bytes & (wfrag_bytes - 1)))
     return IIC_ERR_ARG;
   if (nit & 1) return IIC_ERR_ARG;        // (the two-deep ring variant steps two iterations at a time)
   const int stage = stage_var & 15, var = stage_var >> 4;
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
 #define MF_LAUNCH(ST_, VA_)                                                                          \
-  do {                                                                                               \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mfma_feed_kernel<ST_, VA_>),            \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);               \
-    hipLaunchKernelGGL((mfma_feed_kernel<ST_, VA_>), dim3(grid), dim3(MF_THREADS), lds_bytes, s,     \
-                       (const unsigned char*)wfrag, wfrag_bytes, (const bf16_t*)patch, (bf16_t*)out, \
-                       nit, chunk_its, npix, (unsigned long long*)clk);                              \
-  } while (0)
+  rc = iic_launch_lds<mfma_feed_kernel<ST_, VA_>>(dim3(grid), dim3(MF_THREADS), lds_bytes, s,        \
+                                                  (const unsigned char*)wfrag, wfrag_bytes,          \
+                                                  (const bf16_t*)patch, (bf16_t*)out, nit, chunk_its, \
+                                                  npix, (unsigned long long*)clk)
 #define MF_STAGES(VA_)                                                                               \
   switch (stage) {                                                                                   \
     case 0: MF_LAUNCH(0, VA_); break;                                                                \
@@ -266,5 +264,5 @@ extern "C" int iic_debug_mfma_feed(int stage_var, int grid, int nit, int chunk_i
     case 32: MF_STAGES(32); break;
     default: return IIC_ERR_ARG;
   }
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }

@@ -236,15 +236,13 @@ int iic_seg_contingency_acc(const unsigned char* preds_u8, const unsigned char* 
   const uintptr_t al = (uintptr_t)preds_u8 | (uintptr_t)targets_u8 | (uintptr_t)mask_u8;
   const long nvec = (al & 15) ? 0 : n / 16;
   const size_t lds = sizeof(unsigned int) * (size_t)k_pred * k_gt;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_contingency_acc_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const long work = nvec + (n - nvec * 16);
   long blocks = (work + 255) / 256;
   const int grid = (int)(blocks < 1024 ? blocks : 1024);
-  hipLaunchKernelGGL(seg_contingency_acc_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, preds_u8, targets_u8,
-                     mask_u8, n, nvec, k_pred, k_gt, (unsigned long long*)counts);
-  return iic_launch_status();
+  const int rc = iic_launch_lds<seg_contingency_acc_kernel>(dim3(grid), dim3(256), lds, (hipStream_t)stream, preds_u8,
+                                                            targets_u8, mask_u8, n, nvec, k_pred, k_gt,
+                                                            (unsigned long long*)counts);
+  return rc ? rc : iic_launch_status();
 }
 
 }  // extern "C"

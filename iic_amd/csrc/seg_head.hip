@@ -399,12 +399,9 @@ int iic_bilinear_fwd(const float* in_nhwc, float* out_nchw, int N, int Hl, int W
   if (!in_nhwc || !out_nchw || N <= 0 || Hl <= 0 || Wl <= 0 || k <= 0 || S <= 0) return IIC_ERR_ARG;
   const size_t lds = (size_t)2 * Wl * k * sizeof(float);
   if (lds > 64 * 1024) return IIC_ERR_UNSUPPORTED;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bilinear_fwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(bilinear_fwd_kernel, dim3(N * S), dim3(256), lds, (hipStream_t)stream, in_nhwc,
-                     out_nchw, N, Hl, Wl, k, S);
-  return iic_launch_status();
+  const int rc = iic_launch_lds<bilinear_fwd_kernel>(dim3(N * S), dim3(256), lds, (hipStream_t)stream, in_nhwc,
+                                                     out_nchw, N, Hl, Wl, k, S);
+  return rc ? rc : iic_launch_status();
 }
 
 int iic_bilinear_bwd(const float* dout_nchw, float* din_nhwc, int N, int Hl, int Wl, int k, int S,
@@ -414,12 +411,9 @@ int iic_bilinear_bwd(const float* dout_nchw, float* din_nhwc, int N, int Hl, int
   if (lds > 64 * 1024) return IIC_ERR_UNSUPPORTED;
   // (the kernel tabulates 12 candidate rows / columns per input pixel: up-sampling factors up to 3.5)
   if (2 * S > 7 * Hl || 2 * S > 7 * Wl) return IIC_ERR_UNSUPPORTED;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bilinear_bwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(N * Hl), dim3(256), lds, (hipStream_t)stream,
-                     dout_nchw, din_nhwc, N, Hl, Wl, k, S);
-  return iic_launch_status();
+  const int rc = iic_launch_lds<bilinear_bwd_kernel>(dim3(N * Hl), dim3(256), lds, (hipStream_t)stream, dout_nchw,
+                                                     din_nhwc, N, Hl, Wl, k, S);
+  return rc ? rc : iic_launch_status();
 }
 
 /* Fused 10a head on the bf16 PT window (see the kernels): C = 256 or 512, k <= 32.
@@ -438,16 +432,12 @@ int iic_seg_head_fwd(const void* pt, const float* w, float* logits, int N, int H
   const int tk = (k + 15) / 16;
   const size_t lds = (size_t)16 * tk * (C + 4) * sizeof(float);
   const int grid = (int)((M + SH_ROWS - 1) / SH_ROWS);
+  int rc = IIC_OK;
 #define SH_FWD(TK_)                                                                              \
-  do {                                                                                           \
-    if (lds > 48 * 1024)                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_head_fwd_kernel<TK_>),        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-    hipLaunchKernelGGL((seg_head_fwd_kernel<TK_>), dim3(grid), dim3(256), lds, (hipStream_t)stream, \
-                       (const bf16_t*)pt, w, logits, M, Hw, Ww, Hp, Wp, off, C, k);              \
-  } while (0)
+  rc = iic_launch_lds<seg_head_fwd_kernel<TK_>>(dim3(grid), dim3(256), lds, (hipStream_t)stream, \
+                                                (const bf16_t*)pt, w, logits, M, Hw, Ww, Hp, Wp, off, C, k)
   if (tk == 1) SH_FWD(1); else SH_FWD(2);
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }
 
 int iic_seg_head_bwd_dx(const float* dlog, const float* w, void* pt_dx, int N, int Hw, int Ww, int Hp,
@@ -457,12 +447,10 @@ int iic_seg_head_bwd_dx(const float* dlog, const float* w, void* pt_dx, int N, i
   if (!iic_seg_head_supported(C, k)) return IIC_ERR_UNSUPPORTED;
   const long M = (long)N * Hw * Ww;
   const size_t lds = (size_t)((k + 3) & ~3) * (C + 16) * sizeof(float);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_head_bwd_dx_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(seg_head_bwd_dx_kernel, dim3((int)((M + 63) / 64)), dim3(256), lds,
-                     (hipStream_t)stream, dlog, w, (bf16_t*)pt_dx, M, Hw, Ww, Hp, Wp, off, C, k);
-  return iic_launch_status();
+  const int rc = iic_launch_lds<seg_head_bwd_dx_kernel>(dim3((int)((M + 63) / 64)), dim3(256), lds,
+                                                        (hipStream_t)stream, dlog, w, (bf16_t*)pt_dx, M, Hw, Ww, Hp,
+                                                        Wp, off, C, k);
+  return rc ? rc : iic_launch_status();
 }
 
 int iic_seg_head_wgrad(const float* dlog, const void* pt, float* partials, int N, int Hw, int Ww,

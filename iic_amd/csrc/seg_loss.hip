@@ -1176,23 +1176,13 @@ int iic_seg_joint_raw(const float* x1, const float* x2, const float* mask, const
   const size_t lds = rows_b > red_b ? rows_b : red_b;
   dim3 grid(nq, (nq + qg - 1) / qg, nsplit);
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
 #define SEGJ(TK_, QG_)                                                                          \
-  do {                                                                                          \
-    if (lds > 48 * 1024)                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_joint_kernel<TK_, QG_>),     \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-    hipLaunchKernelGGL((seg_joint_kernel<TK_, QG_>), grid, dim3(256), lds, s, x1, x2, mask,     \
-                       flips, partials, bn, k, h, w, T);                                        \
-  } while (0)
+  rc = iic_launch_lds<seg_joint_kernel<TK_, QG_>>(grid, dim3(256), lds, s, x1, x2, mask, flips, \
+                                                  partials, bn, k, h, w, T)
 #define SEGJS(TK_, MT_, LW_)                                                                    \
-  do {                                                                                          \
-    if (lds > 48 * 1024)                                                                        \
-      (void)hipFuncSetAttribute(                                                                \
-          reinterpret_cast<const void*>(&seg_joint_stream_kernel<TK_, MT_, LW_>),               \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-    hipLaunchKernelGGL((seg_joint_stream_kernel<TK_, MT_, LW_>), sgrid, dim3(256), lds, s, x1,  \
-                       x2, mask, flips, partials, bn, k, h, w, T, sqg);                         \
-  } while (0)
+  rc = iic_launch_lds<seg_joint_stream_kernel<TK_, MT_, LW_>>(sgrid, dim3(256), lds, s, x1, x2, \
+                                                              mask, flips, partials, bn, k, h, w, T, sqg)
 #define SEGJS_LW(TK_, MT_)                                                                      \
   do {                                                                                          \
     if (w > 128) SEGJS(TK_, MT_, 64); else SEGJS(TK_, MT_, 32);                                 \
@@ -1206,14 +1196,8 @@ int iic_seg_joint_raw(const float* x1, const float* x2, const float* mask, const
     const int sgroups = seg_stream_groups(k, nq, &sqg);
     dim3 sgrid(nq, sgroups, nsplit);
 #define SEGJB(TK_, MT_, LW_)                                                                    \
-  do {                                                                                          \
-    if (lds > 48 * 1024)                                                                        \
-      (void)hipFuncSetAttribute(                                                                \
-          reinterpret_cast<const void*>(&seg_joint_bf16_kernel<TK_, MT_, LW_>),                 \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-    hipLaunchKernelGGL((seg_joint_bf16_kernel<TK_, MT_, LW_>), sgrid, dim3(256), lds, s, x1,    \
-                       x2, mask, flips, partials, bn, k, h, w, T, sqg);                         \
-  } while (0)
+  rc = iic_launch_lds<seg_joint_bf16_kernel<TK_, MT_, LW_>>(sgrid, dim3(256), lds, s, x1, x2,   \
+                                                            mask, flips, partials, bn, k, h, w, T, sqg)
     if (tk == 1) { if (w > 128) SEGJB(1, SEG_MT1, 64); else SEGJB(1, SEG_MT1, 32); }
     else { if (w > 128) SEGJB(2, SEG_MT2, 64); else SEGJB(2, SEG_MT2, 32); }
   } else if (seg_stream_ok(k, w, x1, x2, mask)) {
@@ -1227,7 +1211,7 @@ int iic_seg_joint_raw(const float* x1, const float* x2, const float* mask, const
   } else if (tk == 1) SEGJ(1, 21);
   else if (tk == 2) SEGJ(2, 7);
   else SEGJ(3, 3);
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }
 
 long iic_seg_grad_workspace_bytes(int k, int T) {
@@ -1246,6 +1230,7 @@ int iic_seg_grad(const float* src, const float* mask, const int* flips, const fl
   const int w16 = (w + 15) & ~15;
   const int src_is_x2 = which == 0 ? 1 : 0;   // d/dx1 reads x2m ; d/dx2 reads x1m
   hipStream_t s = (hipStream_t)stream;
+  int rc = IIC_OK;
   if (g_seg_stream && workspace && seg_stream_ok(k, w, src, mask, out) && ((uintptr_t)workspace & 15) == 0 &&
       seg_bf16_grad_ok()) {
     // bf16-split path: as the streaming path below, classes padded to 8 per shift
@@ -1259,19 +1244,15 @@ int iic_seg_grad(const float* src, const float* mask, const int* flips, const fl
     const int PS = seg_pitch16(w16 + 2 * T);
     const size_t lds = ((((size_t)k8 * PS + 3) & ~(size_t)3) + (size_t)QC * k8 * PG) * sizeof(float);
 #define SEGGB(TK_, LW_)                                                                         \
-  do {                                                                                          \
-    if (lds > 48 * 1024)                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_grad_bf16_kernel<TK_, LW_>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-    hipLaunchKernelGGL((seg_grad_bf16_kernel<TK_, LW_>), dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, \
-                       mask, flips, workspace, out, bn, k, h, w, T, which, src_is_x2, QC, rowsP); \
-  } while (0)
+  rc = iic_launch_lds<seg_grad_bf16_kernel<TK_, LW_>>(dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, mask, \
+                                                      flips, workspace, out, bn, k, h, w, T, which, src_is_x2, QC, \
+                                                      rowsP)
 #define SEGGB_LW(TK_)                                                                           \
   do {                                                                                          \
     if (w > 128) SEGGB(TK_, 64); else if (w > 64) SEGGB(TK_, 32); else SEGGB(TK_, 16);          \
   } while (0)
     if (tk == 1) SEGGB_LW(1); else SEGGB_LW(2);
-    return iic_launch_status();
+    return rc ? rc : iic_launch_status();
   }
   if (g_seg_stream && workspace && seg_stream_ok(k, w, src, mask, out) && ((uintptr_t)workspace & 15) == 0) {
     // streaming path: G laid out once per launch (workspace), then one workgroup per output row
@@ -1285,13 +1266,9 @@ int iic_seg_grad(const float* src, const float* mask, const int* flips, const fl
     const int PS = seg_pitch16(w16 + 2 * T);
     const size_t lds = ((((size_t)k4 * PS + 3) & ~(size_t)3) + (size_t)QC * k4 * PG) * sizeof(float);
 #define SEGGS(TK_, LW_)                                                                         \
-  do {                                                                                          \
-    if (lds > 48 * 1024)                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_grad_stream_kernel<TK_, LW_>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-    hipLaunchKernelGGL((seg_grad_stream_kernel<TK_, LW_>), dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, \
-                       mask, flips, workspace, out, bn, k, h, w, T, which, src_is_x2, QC, rowsP); \
-  } while (0)
+  rc = iic_launch_lds<seg_grad_stream_kernel<TK_, LW_>>(dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, mask, \
+                                                        flips, workspace, out, bn, k, h, w, T, which, src_is_x2,   \
+                                                        QC, rowsP)
 #define SEGGS_LW(TK_)                                                                           \
   do {                                                                                          \
     if (w > 128) SEGGS(TK_, 64); else if (w > 64) SEGGS(TK_, 32); else SEGGS(TK_, 16);          \
@@ -1300,16 +1277,12 @@ int iic_seg_grad(const float* src, const float* mask, const int* flips, const fl
     else if (tk == 2) SEGGS_LW(2);
     else {
 #define SEGG3(LW_)                                                                              \
-  do {                                                                                          \
-    if (lds > 48 * 1024)                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_grad_stream3_kernel<LW_>),   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-    hipLaunchKernelGGL((seg_grad_stream3_kernel<LW_>), dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, \
-                       mask, flips, workspace, out, bn, k, h, w, T, which, src_is_x2, QC, rowsP); \
-  } while (0)
+  rc = iic_launch_lds<seg_grad_stream3_kernel<LW_>>(dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, mask, \
+                                                    flips, workspace, out, bn, k, h, w, T, which, src_is_x2, QC, \
+                                                    rowsP)
       if (w > 128) SEGG3(64); else if (w > 64) SEGG3(32); else SEGG3(16);
     }
-    return iic_launch_status();
+    return rc ? rc : iic_launch_status();
   }
   const int PS = (w16 + 2 * T) | 1, PG = 16 * tk + 1;
   int QC = (40 * 1024) / (k * PG * 4);        // G slice kept in LDS per chunk of column shifts
@@ -1317,18 +1290,13 @@ int iic_seg_grad(const float* src, const float* mask, const int* flips, const fl
   if (QC > nq) QC = nq;
   const size_t lds = ((size_t)k * PS + (size_t)((QC * k + 3) & ~3) * PG) * sizeof(float);
 #define SEGG(TK_)                                                                               \
-  do {                                                                                          \
-    if (lds > 48 * 1024)                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_grad_kernel<TK_>),           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-    hipLaunchKernelGGL((seg_grad_kernel<TK_>), dim3(bn * h), dim3(256), lds, s, src, mask,      \
-                       flips, dR_loss, dR_loss_no_lamb, g_loss, g_loss_no_lamb, out, bn, k, h,  \
-                       w, T, which, collapsed ? 0 : 1, src_is_x2, QC);                          \
-  } while (0)
+  rc = iic_launch_lds<seg_grad_kernel<TK_>>(dim3(bn * h), dim3(256), lds, s, src, mask, flips, dR_loss, \
+                                            dR_loss_no_lamb, g_loss, g_loss_no_lamb, out, bn, k, h, w, T, which, \
+                                            collapsed ? 0 : 1, src_is_x2, QC)
   if (tk == 1) SEGG(1);
   else if (tk == 2) SEGG(2);
   else SEGG(3);
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }
 
 }  // extern "C"

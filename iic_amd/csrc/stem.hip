@@ -572,13 +572,13 @@ __global__ void sobel_kernel(const float* __restrict__ in, float* __restrict__ o
   }
 }
 
-#define STEM_DISPATCH(CIN_, CALL)            \
+#define STEM_DISPATCH(CIN_, ...)             \
   switch (CIN_) {                            \
-    case 1: { constexpr int CI = 1; CALL; } break; \
-    case 2: { constexpr int CI = 2; CALL; } break; \
-    case 3: { constexpr int CI = 3; CALL; } break; \
-    case 4: { constexpr int CI = 4; CALL; } break; \
-    case 5: { constexpr int CI = 5; CALL; } break; \
+    case 1: { constexpr int CI = 1; __VA_ARGS__; } break; \
+    case 2: { constexpr int CI = 2; __VA_ARGS__; } break; \
+    case 3: { constexpr int CI = 3; __VA_ARGS__; } break; \
+    case 4: { constexpr int CI = 4; __VA_ARGS__; } break; \
+    case 5: { constexpr int CI = 5; __VA_ARGS__; } break; \
     default: return IIC_ERR_UNSUPPORTED;     \
   }
 
@@ -646,19 +646,10 @@ int iic_stem_bwd_reduce(const float* x, const float* w, const float* coef, const
   long items = (long)N * Ho;
   int grid = (int)(items < STEM_PERSIST_BLOCKS ? items : STEM_PERSIST_BLOCKS);
   const size_t lds = stem_bwd_lds(Cin, W, nseg, 0);
-  STEM_DISPATCH(Cin, {
-    if (lds > 48 * 1024) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_bwd_kernel<CI, 0>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return IIC_ERR_UNSUPPORTED;
-      }
-    }
-    hipLaunchKernelGGL((stem_bwd_kernel<CI, 0>), dim3(grid), dim3(64 * nseg), lds,
-                       (hipStream_t)stream, x, w, coef, (const float*)nullptr,
-                       (const bf16_t*)dpool_pt, sums, (float*)nullptr, N, H, W);
-  });
-  return iic_launch_status();
+  STEM_DISPATCH(Cin, rc = iic_launch_lds<stem_bwd_kernel<CI, 0>>(
+                         dim3(grid), dim3(64 * nseg), lds, (hipStream_t)stream, x, w, coef, (const float*)nullptr,
+                         (const bf16_t*)dpool_pt, sums, (float*)nullptr, N, H, W));
+  return rc ? rc : iic_launch_status();
 }
 
 #define STEM_G3_BLOCKS 512
@@ -683,19 +674,10 @@ int iic_stem_bwd_fused(const float* x, const float* w, const float* coef, const 
   if (g_stem_bwd2 && iic_stem_bwd2_supported(Cin, W))      // register-resident routing (stem_bwd2.hip)
     return iic_stem_bwd2_launch(x, w, coef, dpool_pt, sums, partials, nblocks_out, N, Cin, H, W, stream);
   const size_t lds = stem_bwd_lds(Cin, W, nseg, 2);
-  STEM_DISPATCH(Cin, {
-    if (lds > 48 * 1024) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_bwd_kernel<CI, 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return IIC_ERR_UNSUPPORTED;
-      }
-    }
-    hipLaunchKernelGGL((stem_bwd_kernel<CI, 2>), dim3(grid), dim3(64 * nseg), lds,
-                       (hipStream_t)stream, x, w, coef, (const float*)nullptr,
-                       (const bf16_t*)dpool_pt, partials, sums, N, H, W);
-  });
-  return iic_launch_status();
+  STEM_DISPATCH(Cin, rc = iic_launch_lds<stem_bwd_kernel<CI, 2>>(
+                         dim3(grid), dim3(64 * nseg), lds, (hipStream_t)stream, x, w, coef, (const float*)nullptr,
+                         (const bf16_t*)dpool_pt, partials, sums, N, H, W));
+  return rc ? rc : iic_launch_status();
 }
 
 /* dW (fp32 OIHW [64][Cin][3][3]) from the partials of iic_stem_bwd_fused and the BatchNorm
@@ -719,18 +701,11 @@ int iic_stem_bwd_wgrad(const float* x, const float* w, const float* coef, const 
   long items = (long)N * Ho;
   int grid = (int)(items < STEM_PERSIST_BLOCKS ? items : STEM_PERSIST_BLOCKS);
   const size_t lds = stem_bwd_lds(Cin, W, nseg, 1);
-  STEM_DISPATCH(Cin, {
-    if (lds > 48 * 1024) {   // static s_cf (1.25 KB) + dynamic must stay <= 160 KB
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_bwd_kernel<CI, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return IIC_ERR_UNSUPPORTED;
-      }
-    }
-    hipLaunchKernelGGL((stem_bwd_kernel<CI, 1>), dim3(grid), dim3(64 * nseg), lds,
-                       (hipStream_t)stream, x, w, coef, bcoef, (const bf16_t*)dpool_pt, partials,
-                       (float*)nullptr, N, H, W);
-  });
+  // (static s_cf, 1.25 KB, on top of the dynamic LDS: together they stay within the workgroup's LDS)
+  STEM_DISPATCH(Cin, rc = iic_launch_lds<stem_bwd_kernel<CI, 1>>(
+                         dim3(grid), dim3(64 * nseg), lds, (hipStream_t)stream, x, w, coef, bcoef,
+                         (const bf16_t*)dpool_pt, partials, (float*)nullptr, N, H, W));
+  if (rc) return rc;
   const int K = Cin * 9, LD = ((K + 31) / 32) * 32;
   hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3(64 * K), dim3(256), 0,
                      (hipStream_t)stream, partials, grid, LD, K, dW);

@@ -406,13 +406,8 @@ int iic_firstconv_wgrad(const float* x, const void* dy_pt, float* partials, floa
   const size_t lds = (size_t)4 * 64 * NKT * 32 * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
 #define FCW(NK)                                                                                  \
-  do {                                                                                           \
-    if (lds > 48 * 1024)                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&firstconv_wgrad_kernel<NK>),      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-    hipLaunchKernelGGL((firstconv_wgrad_kernel<NK>), dim3(grid), dim3(256), lds, s, x,           \
-                       (const bf16_t*)dy_pt, partials, N, Cin, H, W, K, pad, P);                 \
-  } while (0)
+  rc = iic_launch_lds<firstconv_wgrad_kernel<NK>>(dim3(grid), dim3(256), lds, s, x,              \
+                                                  (const bf16_t*)dy_pt, partials, N, Cin, H, W, K, pad, P)
   switch (NKT) {
     case 1: FCW(1); break;
     case 2: FCW(2); break;
@@ -420,6 +415,7 @@ int iic_firstconv_wgrad(const float* x, const void* dy_pt, float* partials, floa
     case 4: FCW(4); break;
     default: return IIC_ERR_UNSUPPORTED;
   }
+  if (rc) return rc;
   hipLaunchKernelGGL(fc_wgrad_reduce_kernel, dim3(64 * KT), dim3(256), 0, s, partials, grid,
                      NKT * 32, KT, dW);
   return iic_launch_status();

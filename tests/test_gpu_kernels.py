@@ -938,8 +938,7 @@ def test_sobel_matches_reference_golden():
   assert np.abs(o.cpu().numpy() - g["sobel_out4"]).max() <= 1e-6
 
 
-@pytest.mark.parametrize("cin,S", [(2, 32), (2, 96), (1, 24), (3, 64), (5, 32)])
-def test_stem_forward_backward(cin, S):
+def _stem_forward_backward(cin, S):
   from iic_amd import ops
   N = 3
   rng = np.random.default_rng(11)
@@ -993,6 +992,25 @@ def test_stem_forward_backward(cin, S):
     assert torch.allclose(dg2.cpu(), gt.grad, rtol=1e-3, atol=1e-3 * gt.grad.abs().max().item())
     assert (dW2.cpu() - wt.grad).abs().max() <= 4e-3 * wt.grad.abs().max().item(), \
         (dW2.cpu() - wt.grad).abs().max().item() / wt.grad.abs().max().item()
+
+
+# (5, 104): iic_stem_bwd_reduce keeps two conv rows of W * 64 floats in LDS -- 512 * 104 = 53 248 bytes, above the 48 KB a
+# kernel may use without its limit raised (49 152 exactly at W = 96); a ragged last 32-pixel segment as well
+@pytest.mark.parametrize("cin,S", [(2, 32), (2, 96), (1, 24), (3, 64), (5, 32), (5, 104)])
+def test_stem_forward_backward(cin, S):
+  _stem_forward_backward(cin, S)
+
+
+@pytest.mark.hooks
+def test_stem_fused_backward_without_the_register_resident_routing():
+  """iic_debug_enable_stem_bwd2(0): iic_stem_bwd_fused runs stem_bwd_kernel<CIN, 2> (the one-pass backward before
+  stem_bwd2.hip, still what the entry point falls back to) -- 78 144 bytes of dynamic LDS at Cin = 2, W = 96.  Same
+  references and bounds as test_stem_forward_backward."""
+  hook("iic_debug_enable_stem_bwd2", 0)
+  try:
+    _stem_forward_backward(2, 96)
+  finally:
+    hook("iic_debug_enable_stem_bwd2", 1)
 
 
 # --------------------------------------------------------------------------------------

@@ -84,6 +84,20 @@ def test_seg_loss_larger_vs_oracle(bn, k, h, w, T, collapsed):
   _check(fh, fr, x1, x2, aff, mask, 1.5, T)
 
 
+def test_lds_limit_follows_the_launches_of_the_generic_joint_kernel():
+  """iic_launch_lds (csrc/common.h) on a kernel whose dynamic LDS goes past 64 KB: seg_joint_kernel<3, 3> (k = 33, widths
+  that are no multiple of 4) stages 192 rows of about 2 w floats -- 36 864 bytes at w = 30, 51 456 at w = 130, 79 104 at
+  w = 202 -- launched in that order and at w = 30 again, in one process, every loss and gradient against the float64
+  oracle with test_seg_loss_larger_vs_oracle's bounds.  No other test of this process launches that instantiation above
+  48 KB, and a limit left at an earlier launch's size fails the third launch wherever the runtime draws its line."""
+  from iic_amd import seg_losses
+  from oracle import iid_oracle
+  from oracle.gen_golden import make_seg_inputs
+  for w in (30, 130, 202, 30):
+    x1, x2, aff, mask = make_seg_inputs(1, 33, 4, w, 0.5, 0.8, 7)
+    _check(seg_losses.IID_segmentation_loss, iid_oracle.IID_segmentation_loss, x1, x2, aff, mask, 1.5, 1)
+
+
 def test_seg_loss_shift_range_beyond_the_image_is_nan_like_the_reference():
   """half_T_side_dense >= the image side: shifts without any overlap have an all-zero joint, the uncollapsed loss
   normalises every shift by its own sum (IID_losses.py:130-157) => 0 / 0: the reference returns NaN, so do we (no published

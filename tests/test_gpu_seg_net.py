@@ -22,24 +22,51 @@ def _cos(a, b):
   return float((a @ b) / (a.norm() * b.norm() + 1e-30))
 
 
-@pytest.mark.parametrize("Hl,S,k", [(10, 24, 3), (62, 128, 15), (98, 200, 24), (7, 16, 5)])
-def test_bilinear_forward_backward(Hl, S, k):
+def _bilinear_check(N, Hl, Wl, S, k, fwd=True, bwd=True):
+  """iic_bilinear_fwd / iic_bilinear_bwd on [N][Hl][Wl][k] -> [N][k][S][S] against torch's bilinear interpolation and its
+  autograd, fp32 on the CPU."""
   from iic_amd._lib import check, lib, stream_ptr
-  N = 2
   rng = np.random.default_rng(Hl)
-  x = torch.from_numpy(rng.standard_normal((N, k, Hl, Hl)).astype(np.float32)).requires_grad_(True)
+  x = torch.from_numpy(rng.standard_normal((N, k, Hl, Wl)).astype(np.float32)).requires_grad_(True)
   y = F.interpolate(x, size=S, mode="bilinear", align_corners=False)
   dy = torch.from_numpy(rng.standard_normal(tuple(y.shape)).astype(np.float32))
   y.backward(dy)
   d = dev()
   xin = x.detach().permute(0, 2, 3, 1).contiguous().to(d)       # [N][Hl][Wl][k]
-  out = torch.empty((N, k, S, S), device=d)
-  check(lib().iic_bilinear_fwd(xin.data_ptr(), out.data_ptr(), N, Hl, Hl, k, S, stream_ptr()))
-  din = torch.empty_like(xin)
-  check(lib().iic_bilinear_bwd(dy.to(d).data_ptr(), din.data_ptr(), N, Hl, Hl, k, S, stream_ptr()))
-  torch.cuda.synchronize()
-  assert float((out.cpu() - y.detach()).abs().max()) <= 1e-5
-  assert float((din.cpu().permute(0, 3, 1, 2) - x.grad).abs().max()) <= 1e-4 * float(x.grad.abs().max())
+  if fwd:
+    out = torch.empty((N, k, S, S), device=d)
+    check(lib().iic_bilinear_fwd(xin.data_ptr(), out.data_ptr(), N, Hl, Wl, k, S, stream_ptr()))
+    torch.cuda.synchronize()
+    assert float((out.cpu() - y.detach()).abs().max()) <= 1e-5
+  if bwd:
+    din = torch.empty_like(xin)
+    check(lib().iic_bilinear_bwd(dy.to(d).data_ptr(), din.data_ptr(), N, Hl, Wl, k, S, stream_ptr()))
+    torch.cuda.synchronize()
+    assert float((din.cpu().permute(0, 3, 1, 2) - x.grad).abs().max()) <= 1e-4 * float(x.grad.abs().max())
+
+
+@pytest.mark.parametrize("Hl,S,k", [(10, 24, 3), (62, 128, 15), (98, 200, 24), (7, 16, 5)])
+def test_bilinear_forward_backward(Hl, S, k):
+  _bilinear_check(2, Hl, Hl, S, k)
+
+
+def test_bilinear_backward_above_the_default_lds_limit():
+  """iic_bilinear_bwd keeps one input row of Wl * k floats in LDS: 49 * 251 * 4 = 49 196 bytes, just above the 48 KB a
+  kernel may use without its limit raised (the forward needs twice that, above its 64 KB cap: not run here; its
+  large-LDS launches are those of test_gpu_seg_eval.py's k = 255 / k = 200 cases and of the test below)."""
+  _bilinear_check(1, 16, 49, 56, 251, fwd=False)
+
+
+def test_lds_limit_follows_the_launches_of_one_kernel():
+  """iic_launch_lds (csrc/common.h) raises a kernel's dynamic-LDS limit when a launch needs more than any before it.
+  One kernel (iic_bilinear_fwd: 2 * Wl * k floats of LDS), one process: a launch below 48 KB, one above (64 512 bytes),
+  a larger one still (65 472 bytes), the small one again -- each result against torch.  Both large sizes are above the
+  64 000 bytes of the largest launch any other test makes, so both raise the limit wherever in a run this test comes.
+  (This kernel is capped at 64 KB; whether the runtime refuses a launch between 48 and 64 KB above a stale limit has not
+  been observed here, so the same sequence runs past 64 KB on the segmentation joint: test_gpu_seg_loss.py,
+  test_lds_limit_follows_the_launches_of_the_generic_joint_kernel.)"""
+  for Wl in (10, 336, 341, 10):
+    _bilinear_check(1, 4, Wl, 8, 24, bwd=False)
 
 
 @pytest.mark.parametrize("k,Hf,fused,C", [(6, 8, True, 512), (6, 8, False, 512), (24, 9, True, 512), (3, 7, True, 512),
