@@ -17,6 +17,8 @@ _LAZY = {
   "Adam": ("optim", "Adam"),
   "SegPairedAugmenter": ("seg_augment", "SegPairedAugmenter"),
   "seg_paired_dataloaders": ("seg_augment", "seg_paired_dataloaders"),
+  "SegTestPreparer": ("seg_augment", "SegTestPreparer"),
+  "seg_mapping_dataloader": ("seg_augment", "seg_mapping_dataloader"),
 }
 
 

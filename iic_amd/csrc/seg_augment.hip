@@ -29,6 +29,10 @@
 // contrast mean (the rounded mean of the L image the preceding ops produced), which needs one
 // extra pass over the crop for the samples whose op list holds contrast.  No atomics: two calls
 // with the same parameters give identical bytes.
+//
+// seg_prepare_test_kernel (below the training kernel) is the test-time twin, `_prepare_test`
+// (potsdam.py:295-350, cocostuff.py:309-358): the centre crop, one view, no jitter, plus the
+// filtered label map; it shares seg_load, seg_grey and seg_pad_offset with the training kernel.
 #include "common.h"
 #include "aug_jitter.h"
 #include "../../include/iic_hip.h"
@@ -47,6 +51,13 @@
 #define SEG_GREY_SHIFT 14
 __device__ __forceinline__ int seg_grey(int r, int g, int b) {
   return (r * SEG_GREY_R + g * SEG_GREY_G + b * SEG_GREY_B + (1 << (SEG_GREY_SHIFT - 1))) >> SEG_GREY_SHIFT;
+}
+
+// pad_if_too_small (transforms.py:34-41): offset of a source side of `len` pixels inside the padded side of
+// max(len, S), int(x / 2.) arithmetic; 0 for a side that is not padded
+__host__ __device__ __forceinline__ int seg_pad_offset(int len, int S) {
+  const int padded = len > S ? len : S;
+  return padded / 2 - len / 2;
 }
 
 // ops [first, last) of the shuffled ColorJitter list on one pixel; opsw holds op o in bits 4o..4o+3
@@ -188,7 +199,96 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_augment_kernel(
   }
 }
 
+// ---- test-time batches: `_prepare_test`, one thread per four consecutive output x of one row, no LDS
+#define SEG_TEST_THREADS 256
+
+// pad_and_or_crop(mode="centre") (transforms.py:61-63, :81-82): first source row / column of the crop.  The crop
+// starts at int(padded / 2.) - int(S / 2.) in the padded side; the source starts at seg_pad_offset inside it.
+__device__ __forceinline__ int seg_centre_origin(int len, int S) {
+  const int padded = len > S ? len : S;
+  return padded / 2 - S / 2 - seg_pad_offset(len, S);
+}
+
+// MODE as above.  sizes: (h, w) of every image, stored top-left in its [H][W] slab, or nullptr (all H x W).
+template <int CS, int MODE>
+__global__ __launch_bounds__(SEG_TEST_THREADS) void seg_prepare_test_kernel(
+    const uint8_t* __restrict__ imgs, const uint8_t* __restrict__ labels, const int* __restrict__ sizes,
+    const uint8_t* __restrict__ ttable, const uint8_t* __restrict__ rtable, int B, int H, int W,
+    const int* __restrict__ idx, int S, const float* __restrict__ lut, float* __restrict__ out,
+    uint8_t* __restrict__ targets, uint8_t* __restrict__ mask) {
+  constexpr int C = (MODE == 0 ? 3 : (MODE == 1 ? 4 : 1)) + (CS == 4 ? 1 : 0);
+  constexpr int CG = MODE == 1 ? 3 : 0;
+  const int n = blockIdx.y, Q = S >> 2;
+  const int q = blockIdx.x * SEG_TEST_THREADS + threadIdx.x;
+  if (q >= S * Q) return;
+  const int src = idx[n];
+  const bool valid = src >= 0 && src < B;           // an index outside the dataset reads as a black image, label 0
+  int h = H, w = W;
+  if (valid && sizes != nullptr) {                  // an extent outside the slab is clamped to it
+    h = sizes[2 * src], w = sizes[2 * src + 1];
+    h = h < 0 ? 0 : (h > H ? H : h);
+    w = w < 0 ? 0 : (w > W ? W : w);
+  }
+  const uint8_t* im = valid ? imgs + (long)src * H * W * CS : nullptr;
+  const uint8_t* lb = valid ? labels + (long)src * H * W : nullptr;
+  const int y = q / Q, xq = (q - y * Q) << 2;
+  const int sy = seg_centre_origin(h, S) + y, sx0 = seg_centre_origin(w, S) + xq;
+  const bool row_in = sy >= 0 && sy < h;
+  f32x4 v[C];
+  uint32_t tg = 0, mk = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int sx = sx0 + j;
+    const bool in = row_in && sx >= 0 && sx < w;    // inside the image's own extent (h <= H, w <= W)
+    int r, g, b, ir;
+    seg_load<CS>(in ? im : nullptr, sy, sx, H, W, r, g, b, ir);
+    const int l = (in && lb != nullptr) ? (int)lb[(long)sy * W + sx] : 0;       // padded label pixels: fine label 0
+    tg |= (uint32_t)ttable[l] << (8 * j);
+    mk |= (uint32_t)(rtable != nullptr ? rtable[l] : 1) << (8 * j);
+    if (MODE != 2) {
+      v[0][j] = lut[r]; v[1][j] = lut[g]; v[2][j] = lut[b];
+    }
+    if (MODE != 0) v[CG][j] = lut[seg_grey(r, g, b)];
+    if (CS == 4) v[C - 1][j] = lut[ir];
+  }
+  const long plane = (long)S * S, off = (long)y * S + xq;
+  float* o = out + (long)n * C * plane + off;
+#pragma unroll
+  for (int c = 0; c < C; ++c) *reinterpret_cast<f32x4*>(o + c * plane) = v[c];
+  *reinterpret_cast<uint32_t*>(targets + (long)n * plane + off) = tg;
+  *reinterpret_cast<uint32_t*>(mask + (long)n * plane + off) = mk;
+}
+
 extern "C" {
+
+int iic_seg_prepare_test(const void* imgs_u8, int B, int H, int W, int Cs, const void* labels_u8, const int* sizes,
+                         const void* target_table, const void* relevance, const int* idx, int N, int S,
+                         int no_sobel, int include_rgb, const float* lut, float* imgs, void* targets, void* mask,
+                         void* stream) {
+  if (!imgs_u8 || !labels_u8 || !target_table || !idx || !lut || !imgs || !targets || !mask) return IIC_ERR_ARG;
+  if (B <= 0 || N <= 0 || S <= 0 || H <= 0 || W <= 0) return IIC_ERR_ARG;
+  if (Cs != 3 && Cs != 4) return IIC_ERR_UNSUPPORTED;
+  if (S % 4 != 0 || S > 4096 || H > 16384 || W > 16384 || N > 65535) return IIC_ERR_UNSUPPORTED;
+  const int mode = no_sobel ? 0 : (include_rgb ? 1 : 2);
+  const int nquads = S * (S >> 2);
+  const dim3 grid((nquads + SEG_TEST_THREADS - 1) / SEG_TEST_THREADS, N);
+  hipStream_t s = (hipStream_t)stream;
+#define SEG_LAUNCH(CS_, MODE_)                                                                              \
+  hipLaunchKernelGGL((seg_prepare_test_kernel<CS_, MODE_>), grid, dim3(SEG_TEST_THREADS), 0, s,             \
+                     (const uint8_t*)imgs_u8, (const uint8_t*)labels_u8, sizes, (const uint8_t*)target_table, \
+                     (const uint8_t*)relevance, B, H, W, idx, S, lut, imgs, (uint8_t*)targets, (uint8_t*)mask)
+  if (Cs == 3) {
+    if (mode == 0) SEG_LAUNCH(3, 0);
+    else if (mode == 1) SEG_LAUNCH(3, 1);
+    else SEG_LAUNCH(3, 2);
+  } else {
+    if (mode == 0) SEG_LAUNCH(4, 0);
+    else if (mode == 1) SEG_LAUNCH(4, 1);
+    else SEG_LAUNCH(4, 2);
+  }
+#undef SEG_LAUNCH
+  return iic_launch_status();
+}
 
 int iic_seg_augment(const void* imgs_u8, int B, int H, int W, int Cs, const void* labels_u8,
                     const void* relevance, const int* iparams, const float* fparams, int N, int S,
@@ -199,9 +299,7 @@ int iic_seg_augment(const void* imgs_u8, int B, int H, int W, int Cs, const void
   if ((labels_u8 == nullptr) != (relevance == nullptr)) return IIC_ERR_ARG;
   if (Cs != 3 && Cs != 4) return IIC_ERR_UNSUPPORTED;
   if (S % 4 != 0 || S > 4096 || H > 16384 || W > 16384) return IIC_ERR_UNSUPPORTED;
-  // pad_if_too_small (transforms.py:34-41): centre of the padded image minus half the source, int(x / 2.)
-  const int new_h = H > S ? H : S, new_w = W > S ? W : S;
-  const int pad_y = new_h / 2 - H / 2, pad_x = new_w / 2 - W / 2;     // 0 for a side that is not padded
+  const int pad_y = seg_pad_offset(H, S), pad_x = seg_pad_offset(W, S);
   const int mode = no_sobel ? 0 : (include_rgb ? 1 : 2);
   hipStream_t s = (hipStream_t)stream;
 #define SEG_LAUNCH(CS_, MODE_)                                                                            \

@@ -24,6 +24,15 @@ Grey is OpenCV's 8-bit COLOR_RGB2GRAY in its 3.x fixed-point form, (R 4899 + G 9
 restated from OpenCV's source and NOT compared against a cv2 binary (cv2 is not available where this
 is built and tested; newer OpenCV builds use a 15-bit variant that can differ by one grey level).
 Every published Potsdam command is --no_sobel and never reaches it; the COCO commands do.
+
+Test time.  `SegTestPreparer` is the evaluation twin: what `_prepare_test` (potsdam.py:295-350,
+cocostuff.py:309-358) returns per image -- the centre crop in the same channel layout, `_filter_label`'s label map
+and its mask -- for a whole batch in one launch (csrc/seg_augment.hip::seg_prepare_test_kernel), and
+`seg_mapping_dataloader` what `_create_mapping_loader` (code/utils/segmentation/data.py:129-149) yields.  Labels and
+mask leave the kernel as uint8, the form seg_eval.SegEvalAccumulator consumes without a copy.  One more caveat on
+grey: `_prepare_test` hands cv2.cvtColor the float32 image (it never truncates to uint8 as the training path does),
+so a real OpenCV takes its float path there, 0.299 R + 0.587 G + 0.114 B unrounded; the kernel and the fixture's
+stand-in use the rounded fixed-point grey above, within half a grey level of it.
 """
 import math
 
@@ -302,3 +311,158 @@ def seg_paired_dataloaders(augmenter, batch_sz, num_dataloaders):
   samples, each yielding the four tensors of `_prepare_train` per batch, already on the GPU."""
   assert int(num_dataloaders) >= 1
   return [_SegPairedLoader(augmenter, batch_sz) for _ in range(int(num_dataloaders))]
+
+
+# ------------------------------------------------------------------------------------------
+# test time: _prepare_test
+# ------------------------------------------------------------------------------------------
+def _fine_labels():
+  fine = np.arange(256, dtype=np.int32)
+  fine[182:] = -1                          # 255 is -1; 182..254 are not fine labels: treated as unlabelled
+  return fine
+
+
+def label_table(filter_label):
+  """Companion of `relevance_table`: `_filter_label`'s returned LABEL (potsdam.py:429-439, cocostuff.py:629-657,
+  :734-760) as the 256-entry uint8 table the test kernel reads.  Entry l is the low 8 bits of the reference's int32
+  value for fine label l (entry 255: for -1), so a map looked up here equals `ref_label.astype(np.uint8)` in masked-out
+  pixels too, negatives included.  filter_label: the bound method (or any callable) taking an int32 label array and
+  returning the labels alone (Potsdam) or (labels, mask) (COCO-Stuff); it may work in place.  The table is whatever
+  the method returns, quirks included: _CocoFew starts its map from zeros, so -1 comes back as class 0 with mask 1.
+  A method that refuses the whole range (Potsdam fine: `assert label.max() < gt_k`) is asked one label at a time;
+  the labels it refuses get 255."""
+  def labels_of(fine):
+    res = filter_label(fine.copy())
+    return np.asarray(res[0] if isinstance(res, tuple) else res).astype(np.int64).reshape(-1)
+  fine = _fine_labels()
+  try:
+    lab = labels_of(fine.reshape(1, 256))
+  except AssertionError:
+    lab = np.full(256, -1, np.int64)
+    for i in range(256):
+      try:
+        lab[i] = labels_of(fine[i:i + 1].reshape(1, 1))[0]
+      except AssertionError:
+        pass
+  return np.ascontiguousarray((lab & 255).astype(np.uint8))
+
+
+def prepare_test_host(img, label, input_sz, no_sobel, include_rgb, targets, relevance=None):
+  """`_prepare_test` (potsdam.py:295-350, cocostuff.py:309-358) for one image, in numpy: the host restatement for
+  tests and tools.  img uint8 [h, w, 3 or 4], label uint8 [h, w] fine labels (255 for -1), targets / relevance the
+  tables of `label_table` / `relevance_table` (relevance None: Potsdam, mask of ones).
+  Returns (img float32 [C, S, S], targets uint8 [S, S], mask uint8 [S, S])."""
+  S = int(input_sz)
+  h, w, cs = img.shape
+  assert label.shape == (h, w) and img.dtype == np.uint8 and label.dtype == np.uint8
+  new_h, new_w, oy, ox = pad_offsets(h, w, S)
+  pad = np.zeros((new_h, new_w, cs), np.uint8)
+  pad[oy:oy + h, ox:ox + w] = img
+  lpad = np.zeros((new_h, new_w), np.uint8)                # pad_if_too_small zero-fills: fine label 0
+  lpad[oy:oy + h, ox:ox + w] = label
+  y0, x0 = int(new_h / 2.) - int(S / 2.), int(new_w / 2.) - int(S / 2.)       # pad_and_or_crop mode "centre"
+  crop, lab = pad[y0:y0 + S, x0:x0 + S], lpad[y0:y0 + S, x0:x0 + S]
+  v = crop[:, :, :3]
+  if not no_sobel:
+    grey = cv_grey(v)[:, :, None]
+    v = np.concatenate([v, grey], axis=2) if include_rgb else grey
+  v = v.astype(np.float32) / 255.
+  if cs == 4:
+    v = np.concatenate([v, (crop[:, :, 3].astype(np.float32) / 255.)[:, :, None]], axis=2)
+  mask = np.ones((S, S), np.uint8) if relevance is None else np.asarray(relevance, np.uint8)[lab]
+  return np.ascontiguousarray(v.transpose(2, 0, 1)), np.asarray(targets, np.uint8)[lab], np.ascontiguousarray(mask)
+
+
+def _table(t, device):
+  t = np.ascontiguousarray(np.asarray(t.cpu() if torch.is_tensor(t) else t, dtype=np.uint8).reshape(-1))
+  assert t.shape == (256,)
+  return torch.from_numpy(t).to(device)
+
+
+class SegTestPreparer(object):
+  """images_u8: uint8 [B, H, W, Cs] and labels_u8: uint8 [B, H, W] (fine labels, 255 for -1) on the GPU -- the
+  partitions of a mapping loader concatenated by the caller; targets: the table of `label_table`; relevance: the table
+  of `relevance_table`, or None (Potsdam: mask of ones).  sizes: int [B, 2], the (h, w) of every image when they differ
+  (COCO-Stuff): image i occupies the top-left h x w of its slab and is centre-cropped by its own extent, as the
+  reference crops each image; None: every image is H x W.  config is read for input_sz, include_rgb, no_sobel,
+  pre_scale_all and mask_input (asserted false).  pre_scale_all as for SegPairedAugmenter: the resident arrays ARE the
+  pre-scaled images and NEAREST-pre-scaled labels (and sizes their extents); prescaled=False asks for the resize
+  inside the kernel, which is not built.
+
+  batch(idx) -> (imgs float32 [n, C, S, S], targets uint8 [n, S, S], mask uint8 [n, S, S]) on the device."""
+
+  def __init__(self, images_u8, labels_u8, config, targets, relevance=None, sizes=None, prescaled=True):
+    assert not _flag(config, "mask_input"), "cocostuff.py:348"
+    if _flag(config, "pre_scale_all") and not prescaled:
+      raise NotImplementedError("pre_scale_all inside the kernel is not built: keep the pre-scaled, truncated "
+                                "images (labels: NEAREST) resident and pass those")
+    assert images_u8.dtype == torch.uint8 and images_u8.is_contiguous()
+    assert images_u8.dim() == 4 and images_u8.shape[3] in (3, 4), "[B, H, W, 3] (RGB) or [B, H, W, 4] (RGB + IR) uint8"
+    self.images = images_u8
+    self.B, self.H, self.W, self.Cs = (int(v) for v in images_u8.shape)
+    self.S = int(config.input_sz)
+    if self.S % 4 != 0:
+      raise NotImplementedError("input_sz must be a multiple of 4 (16-byte stores); the published runs use 128 and 200")
+    if not (1 <= self.H <= 16384 and 1 <= self.W <= 16384):
+      raise ValueError("implausible image size %d x %d" % (self.H, self.W))
+    assert labels_u8.dtype == torch.uint8 and labels_u8.is_contiguous()
+    assert tuple(labels_u8.shape) == (self.B, self.H, self.W) and labels_u8.device == images_u8.device
+    self.labels = labels_u8
+    dev = images_u8.device
+    self.targets = _table(targets, dev)
+    self.relevance = None if relevance is None else _table(relevance, dev)
+    self.sizes = None
+    if sizes is not None:
+      sz = np.ascontiguousarray(np.asarray(sizes.cpu() if torch.is_tensor(sizes) else sizes).astype(np.int64))
+      if sz.shape != (self.B, 2):
+        raise ValueError("sizes must be [%d, 2], one (h, w) per image" % self.B)
+      if (sz < 1).any() or (sz[:, 0] > self.H).any() or (sz[:, 1] > self.W).any():
+        raise ValueError("sizes out of range: every (h, w) must lie within 1..%d x 1..%d" % (self.H, self.W))
+      self.sizes = torch.from_numpy(sz.astype(np.int32)).to(dev)
+    self.no_sobel, self.include_rgb = bool(config.no_sobel), bool(config.include_rgb)
+    self.lut = (torch.arange(256, dtype=torch.float32) / 255).to(dev)                  # astype(float32) / 255.
+
+  @property
+  def out_channels(self):
+    return (3 if self.no_sobel else (4 if self.include_rgb else 1)) + (1 if self.Cs == 4 else 0)
+
+  def batch(self, idx):
+    idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int32)
+    n = int(idx.shape[0])
+    assert n > 0 and idx.min() >= 0 and idx.max() < self.B, "source index out of range"
+    assert self.images.is_cuda, "the dataset must be resident on the GPU (there is no CPU path)"
+    dev = self.images.device
+    S = self.S
+    didx = torch.from_numpy(idx).to(dev, non_blocking=True)
+    imgs = torch.empty(n, self.out_channels, S, S, device=dev, dtype=torch.float32)
+    targets = torch.empty(n, S, S, device=dev, dtype=torch.uint8)
+    mask = torch.empty(n, S, S, device=dev, dtype=torch.uint8)
+    _lib.check(_lib.lib().iic_seg_prepare_test(
+      self.images.data_ptr(), self.B, self.H, self.W, self.Cs, self.labels.data_ptr(), _lib.ptr(self.sizes),
+      self.targets.data_ptr(), _lib.ptr(self.relevance), didx.data_ptr(), n, S, int(self.no_sobel),
+      int(self.include_rgb), self.lut.data_ptr(), imgs.data_ptr(), targets.data_ptr(), mask.data_ptr(),
+      _lib.stream_ptr()), "iic_seg_prepare_test")
+    return imgs, targets, mask
+
+
+class _SegMappingLoader(object):
+  """What `_create_mapping_loader` returns (code/utils/segmentation/data.py:129-149, shuffle=False, drop_last=False):
+  iterating yields (imgs, flat_targets, mask) batches in sequential sample order, the last one ragged."""
+
+  def __init__(self, preparer, batch_sz):
+    self.prep, self.batch_sz, self.n = preparer, int(batch_sz), int(preparer.B)
+    assert self.batch_sz > 0
+
+  def __len__(self):
+    return (self.n + self.batch_sz - 1) // self.batch_sz
+
+  def __iter__(self):
+    for lo in range(0, self.n, self.batch_sz):
+      yield self.prep.batch(np.arange(lo, min(self.n, lo + self.batch_sz)))
+
+
+def seg_mapping_dataloader(preparer, batch_sz):
+  """Drop-in for mapping_assignment_dataloader / mapping_test_dataloader of the segmentation scripts
+  (code/utils/segmentation/data.py:58-83, code/scripts/segmentation/segmentation_twohead.py:163): consumed by iic_amd.seg_eval.segmentation_eval and by
+  the reference's own _segmentation_get_data alike, every tensor already on the GPU."""
+  return _SegMappingLoader(preparer, batch_sz)

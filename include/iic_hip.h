@@ -530,6 +530,32 @@ int iic_seg_augment(const void* imgs_u8, int B, int H, int W, int Cs, const void
                     int no_sobel, int include_rgb, const float* lut, float* img1, float* img2,
                     void* mask_img1, float* affine2_to_1, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Test-time batches of the segmentation datasets on the GPU -- replaces the per-sample host pipeline of
+ * the evaluation __getitem__:
+ *   code/datasets/segmentation/potsdam.py:295-350   (_Potsdam._prepare_test)
+ *   code/datasets/segmentation/cocostuff.py:309-358 (_Coco._prepare_test)
+ * with pad_and_or_crop(mode="centre") over pad_if_too_small and custom_greyscale_numpy of
+ * code/utils/segmentation/transforms.py:7-88, the per-class loop of _filter_label (potsdam.py:429-439,
+ * cocostuff.py:629-657, :734-760), and the DataLoader + host-to-device copy of
+ * code/utils/segmentation/data.py:129-149, for a whole batch in one launch.
+ * imgs_u8, labels_u8, lut, no_sobel, include_rgb and the channel layout: as for iic_seg_augment; labels_u8
+ *            is required here.
+ * sizes      int32 [B][2]: (h, w) of every image, stored top-left in its [H][W] slab, each centre-cropped by
+ *            its own extent; NULL: every image is H x W.
+ * target_table uint8 [256]: the low 8 bits of _filter_label's returned label as a function of the fine label
+ *            (entry 255: of -1).
+ * relevance  uint8 [256] as for iic_seg_augment, or NULL: mask of ones (Potsdam, potsdam.py:342).
+ * idx        int32 [N] source images; one outside [0, B) reads as a black image with fine label 0.
+ * imgs       float [N][C][S][S]; targets, mask uint8 [N][S][S].  The source is centred in zeros of
+ *            max(h, S) x max(w, S) and cut around (int(new_h / 2.), int(new_w / 2.)); padded label pixels are
+ *            fine label 0.  S % 4 == 0, N <= 65535.  No atomics: two calls give identical bytes.
+ * ------------------------------------------------------------------------------- */
+int iic_seg_prepare_test(const void* imgs_u8, int B, int H, int W, int Cs, const void* labels_u8,
+                         const int* sizes, const void* target_table, const void* relevance,
+                         const int* idx, int N, int S, int no_sobel, int include_rgb, const float* lut,
+                         float* imgs, void* targets, void* mask, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
