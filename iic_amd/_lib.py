@@ -81,6 +81,7 @@ _SIGNATURES = {
   "iic_stem_bwd_wgrad": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
   "iic_contingency": (c_int, [_P, _P, c_long, c_int, c_int, _P, _P]),
   "iic_count_equal": (c_int, [_P, _P, c_long, _P, _P]),
+  "iic_cluster_argmax_acc": (c_int, [_P, c_long, c_long, c_long, c_int, c_int, _P, c_int, _P, _P, c_long, _P]),
   "iic_seg_label_map": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_seg_contingency_acc": (c_int, [_P, _P, _P, c_long, c_int, c_int, _P, _P]),
   "iic_augment": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, c_int, _P, _P]),

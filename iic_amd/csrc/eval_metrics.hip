@@ -7,6 +7,17 @@
 //   kernel, and `int((preds == targets).sum())` of _acc (:69) by a counting kernel.
 // Integer work: per-workgroup LDS histogram (k_pred * k_gt <= 16384 bins) merged with 64-bit
 // global atomics; labels outside [0, k) match no pair, exactly like the reference's comparisons.
+//
+// cluster_argmax_acc_kernel is the other half of that survey entry, for the clustering scripts
+// (code/utils/cluster/cluster_eval.py): it replaces
+//   :55-63   torch.argmax of every sub-head (int64 out) and the slice assignments into flat int32 arrays that span
+//            the whole data set
+//   :128-132 and :212-228  the reorder loops `reordered_preds[flat_preds == pred_i] = target_i` (2 launches per
+//            output cluster and sub-head) and _acc: all of it is a function of one k x gt_k count matrix per sub-head
+// by ONE launch per batch.  One wave per (sample, sub-head) row: the lanes stride over the k probabilities, a 64-lane
+// butterfly on (value, index) finds torch.argmax's answer -- NaN is maximal, the first maximal index wins -- and lane 0
+// stores the label and issues the 64-bit integer atomics into bins that live in global memory (no LDS histogram, no
+// k * gt_k cap: a batch is a few thousand rows).  Integer adds commute: the result does not depend on arrival order.
 #include "common.h"
 #include "../../include/iic_hip.h"
 
@@ -41,7 +52,73 @@ __global__ __launch_bounds__(256) void count_equal_kernel(const long long* __res
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, (unsigned long long)c);
 }
 
+// does (av, ai) come before (bv, bi) in torch.argmax's order?  NaN above every number, then the larger value, then the
+// lower index (-0.0 == 0.0, all NaNs alike).  ai != bi for any two candidates, so this is a strict total order.
+__device__ __forceinline__ bool ca_before(float av, int ai, float bv, int bi) {
+  const bool an = av != av, bn = bv != bv;
+  if (an != bn) return an;
+  if (!an && av != bv) return av > bv;
+  return ai < bi;
+}
+
+#define CA_WAVES 4
+
+__global__ __launch_bounds__(64 * CA_WAVES) void cluster_argmax_acc_kernel(
+    const float* __restrict__ probs, long ld, long head_stride, long rows, int H, int k,
+    const long long* __restrict__ targets, int gt_k, unsigned long long* __restrict__ counts, int* __restrict__ labels,
+    long label_stride) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * CA_WAVES + (threadIdx.x >> 6);      // row = sample * H + sub-head: uniform per wave
+  if (r >= rows) return;
+  const long i = r / H;
+  const int h = (int)(r - i * H);
+  const float* row = probs + i * ld + (long)h * head_stride;
+  // a lane without an element holds (-inf, INT_MAX): it loses to every real element, an all -inf row included
+  float bv = -__builtin_inff();
+  int bi = 0x7fffffff;
+  for (int c = lane; c < k; c += 64) {
+    const float v = row[c];
+    if (ca_before(v, c, bv, bi)) {
+      bv = v;
+      bi = c;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ca_before(ov, oi, bv, bi)) {
+      bv = ov;
+      bi = oi;
+    }
+  }
+  if (lane != 0) return;
+  if (labels) labels[(long)h * label_stride + i] = bi;
+  if (counts) {
+    const long nb = (long)k * gt_k;
+    unsigned long long* c = counts + (long)h * (nb + 1);
+    atomicAdd(&c[nb], 1ull);
+    const long long t = targets[i];
+    if (t >= 0 && t < gt_k) atomicAdd(&c[(long)bi * gt_k + t], 1ull);
+  }
+}
+
 extern "C" {
+
+int iic_cluster_argmax_acc(const float* probs, long ld, long head_stride, long n, int H, int k,
+                           const long long* targets, int gt_k, long long* counts, int* labels, long label_stride,
+                           void* stream) {
+  if (!probs || n < 0 || H <= 0 || k <= 0) return IIC_ERR_ARG;
+  if (!counts && !labels) return IIC_ERR_ARG;
+  if (counts && (!targets || gt_k <= 0)) return IIC_ERR_ARG;
+  if (n == 0) return IIC_OK;
+  const long rows = n * (long)H;
+  const long grid = (rows + CA_WAVES - 1) / CA_WAVES;
+  if (grid > 0x7fffffffL) return IIC_ERR_ARG;
+  hipLaunchKernelGGL(cluster_argmax_acc_kernel, dim3((unsigned)grid), dim3(64 * CA_WAVES), 0, (hipStream_t)stream, probs,
+                     ld, head_stride, rows, H, k, targets, gt_k, (unsigned long long*)counts, labels, label_stride);
+  return iic_launch_status();
+}
 
 int iic_contingency(const long long* preds, const long long* targets, long n, int k_pred, int k_gt,
                     long long* counts, void* stream) {

@@ -438,6 +438,28 @@ int iic_contingency(const long long* preds, const long long* targets, long n, in
 int iic_count_equal(const long long* a, const long long* b, long n, long long* count, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Clustering evaluation on the device (csrc/eval_metrics.hip) -- replaces, in
+ * code/utils/cluster/cluster_eval.py, the per-sub-head torch.argmax and the copies into flat int32
+ * arrays of the whole data set (:55-63), and everything :128-132 and :212-228 derive from those
+ * arrays (the reorder loops, 2 launches per output cluster and sub-head, and _acc).  One launch per
+ * batch, all sub-heads.
+ * probs: fp32; row i of sub-head h is the k consecutive floats at probs + i*ld + h*head_stride (the
+ * packed softmax output [n][H][k] has ld = H*k, head_stride = k; a padded ld works).
+ * targets: int64 [n], may be NULL when counts is.
+ * pred = torch.argmax of the row for EVERY input: the first maximal index wins, a NaN counts as
+ * maximal and the first NaN wins.
+ * counts: int64 [H][k*gt_k + 1], may be NULL, ACCUMULATED (the caller zeroes it once): for every
+ * sample counts[h][k*gt_k] += 1 and, if 0 <= targets[i] < gt_k, counts[h][pred*gt_k + targets[i]] += 1.
+ * labels: int32, may be NULL: labels[h*label_stride + i] = pred.
+ * counts without targets, or both outputs NULL: IIC_ERR_ARG.  n = 0: no-op.  Any k >= 1; no cap on
+ * k * gt_k (the bins live in global memory).  Integer atomics: the result does not depend on
+ * arrival order.
+ * ------------------------------------------------------------------------------- */
+int iic_cluster_argmax_acc(const float* probs, long ld, long head_stride, long n, int H, int k,
+                           const long long* targets, int gt_k, long long* counts, int* labels,
+                           long label_stride, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Segmentation evaluation on the device (csrc/seg_eval.hip).
  *
  * iic_seg_label_map -- replaces, for evaluation, the full-resolution probability maps of
