@@ -19,15 +19,20 @@
 // symbol exists.  `make dbg` builds the same sources with -DIIC_DEBUG_HOOKS into libiic_hip_dbg.so, where
 // the switches are variables with exported setters (tests marked `hooks`, tools/*.py; IIC_HIP_LIB=dbg).
 // ------------------------------------------------------------------------------------------
+// The adopted patch form of the weights-direct conv kernels (conv_igemm_bd.hip g_bd_pitch144): 1 = rows at a 144-byte
+// pitch where the geometry keeps its workgroups per CU, 0 = XOR-swizzled 128-byte rows everywhere
+#define IIC_BD_PITCH144 1
 #ifdef IIC_DEBUG_HOOKS
 #define IIC_HOOK extern "C" __attribute__((visibility("default")))
 #define IIC_SWITCH(var, dflt, setter) \
   static int var = dflt;              \
   IIC_HOOK void setter(int v) { var = v; }
 IIC_HOOK int iic_debug_get_ablate(void);
+IIC_HOOK int iic_debug_get_bd_pitch144(void);
 #else
 #define IIC_SWITCH(var, dflt, setter) static constexpr int var = dflt;
 static inline constexpr int iic_debug_get_ablate(void) { return 0; }
+static inline constexpr int iic_debug_get_bd_pitch144(void) { return IIC_BD_PITCH144; }
 #endif
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

@@ -57,7 +57,7 @@ struct bd_blk {
 // ABL: timing-ablation build (tools/conv_perf.py --ablate; results are WRONG by design):
 //   1 = no patch reload at chunk boundaries, 2 = B fragments always from the same address
 //   (L2-hot), 4 = no epilogue, 8 = no chunk-boundary barriers either, 16 = no A-fragment LDS reads,
-//   32 = no global stores of the tile, 64 = no BatchNorm statistics.
+//   32 = no global stores of the tile, 64 = no BatchNorm statistics.  (Ablation builds run the swizzled form.)
 // The patch is fetched by LDS-DMA (global_load_lds_dwordx4: no staging VGPRs, every piece of
 // a chunk in flight at once instead of 4-piece batches that each wait a full memory latency) into
 // unpadded 128-byte rows whose 16-byte slot is XOR-ed with a 3-bit key of the row -- the swizzle is
@@ -75,7 +75,12 @@ struct bd_blk {
 // WN: 64-cout column groups of the workgroup tile.  2: 128 couts, waves 2 (rows) x 2 (cols), MS*64 rows;
 // 1: 64 couts (layers with Cout = 64: the backward-data of a 64 -> 128 convolution, SegmentationNet10a c2), the
 // four waves stacked along the rows, MS*128 rows -- the wave tile stays MS x 2 MFMA blocks either way.
-template <bool GATHER, int ABL, int MS, int RED, int WN = 2>
+// PAD: the patch rows at a 144-byte pitch (conv_tile.h ROWB, PT144_*) instead of the swizzled 128-byte rows: an
+// A-fragment address is the lane's row base + the tap's scalar offset (one add per tap and sub-tile) + an immediate
+// per k-step, where the swizzle costs ~70 VALU per tap; no key table; the DMA lays 7-row pieces whose lane -> (row,
+// slot) map is a constant of the launch.  Row-major stride-1 multi-tap tiles only (the host decides: bd_pad_ok);
+// same MFMA sequence and operands => bit-identical outputs (LAB.md S7).
+template <bool GATHER, int ABL, int MS, int RED, int WN = 2, bool PAD = false>
 __device__ __forceinline__ void bd_tile(
     const iic_conv_geom& g, const bf16_t* __restrict__ in, const unsigned char* __restrict__ wfrag,
     bf16_t* __restrict__ out, float* __restrict__ stats, const bf16_t* __restrict__ res_grad,
@@ -85,14 +90,12 @@ __device__ __forceinline__ void bd_tile(
     unsigned long long* __restrict__ prof, int blk_in_class, int nwg_class, const bd_blk& B) {
   constexpr int BNT = WN * 64, NWM = 4 / WN;   // tile couts, wave row groups
   constexpr bool CANBLK = !GATHER && MS * 32 * (4 / WN) == 256;      // 256-row tiles of either width
-  const bool blk = CANBLK && B.bw > 0;         // uniform
+  const bool blk = CANBLK && !PAD && B.bw > 0;         // uniform
   constexpr int CLD = BNT + 8;
   constexpr bool PROF = (ABL & 128) != 0;
   constexpr bool NEWORD = (ABL & 256) == 0;     // ABL bit 256: the round-2 K-loop order (A/B runs)
-  // ABL bit 512 (timing only, WRONG results): A-fragment addresses as for a 144-byte row pitch -- one add per tap and
-  // sub-tile, immediate k-step offsets -- while the DMA still writes the swizzled 128-byte rows: what the K loop would
-  // cost without its ~70 VALU of swizzle arithmetic per tap (LAB.md R6.9)
-  constexpr bool SWZ = (ABL & 512) == 0;
+  static_assert(!(PAD && GATHER), "the padded patch is a multi-tap form");
+  constexpr bool SWZ = !PAD;
   // PROF (ABL bit 128, results CORRECT): wave 0 stamps s_memtime at the phase boundaries of its tile
   // into prof[blockIdx][BD_PROF_SLOTS] (tools/bd_timeline.py decodes them)
   unsigned long long t_stamp[8];
@@ -158,7 +161,7 @@ __device__ __forceinline__ void bd_tile(
   const int jskip = blk ? B.PW - B.bw
                         : ((!GATHER && g.sx == 1 && ((g.in_Wp - g.MX) & 1) == 0) ? g.in_Wp - g.MX : 0);
   auto dense_of = [&](int p) { return p - jskip * (p / keyw); };
-  int arow[MS];     // patch row index (ABL bit 512: byte offset of the lane's row at a 144-byte pitch + k-chunk)
+  int arow[MS];     // patch row index (PAD: byte offset of the lane's half of the row's first k-step)
   int drow[MS];     // D of the lane's row at tap offset 0
 #pragma unroll
   for (int ms = 0; ms < MS; ++ms) {
@@ -167,7 +170,7 @@ __device__ __forceinline__ void bd_tile(
     arow[ms] = SWZ ? pr : pr * ROWB + g5 * 16;
     drow[ms] = (SWZ && !GATHER) ? dense_of(s_pin[row]) : pr;
   }
-  if (!GATHER && jskip != 0) {     // (without a skip the key is a function of r alone: no table)
+  if (SWZ && !GATHER && jskip != 0) {     // (without a skip the key is a function of r alone: no table)
     for (int r = tid; r < npix; r += BD_THREADS) s_key[r] = (unsigned char)((dense_of(p_lo + r) >> 1) & 7);
     __syncthreads();
   }
@@ -176,7 +179,22 @@ __device__ __forceinline__ void bd_tile(
   // patch loader: 1-KB blocks over the 4 waves; piece q -> LDS byte q*16 (row q>>3, physical
   // slot q&7), source = logical slot (q&7) ^ ((row>>1)&7) of the row's pixel
   const int nblk = (npix * 128 + 1023) >> 10;
+  // PAD: piece j = patch rows 7j ... 7j + 6 at LDS byte 1008 j; lane l holds (row l / 9, slot l % 9) of every piece (slot 8
+  // = the pad: re-reads slot 7's line), lane 63 slot 0 of row 7j + 7 (written again, with the same data, by piece j + 1)
+  const int dma_rl = lane / 9, dma_pc = min(lane - dma_rl * 9, 7) * 8;
   auto dma_patch = [&](int c0) {
+    if (PAD) {
+      const int nj = (npix + PT144_ROWS - 1) / PT144_ROWS;
+      for (int j = wave; j < nj; j += BD_THREADS / 64) {
+        long p = (long)p_lo + j * PT144_ROWS + dma_rl;
+        p = p < in_pixels ? p : in_pixels - 1;
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(in + (p * g.Cin + c0 + dma_pc)),
+            (__attribute__((address_space(3))) void*)(sA + j * PT144_PIECE), 16, 0, 0);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      return;
+    }
     for (int kb = wave; kb < nblk; kb += BD_THREADS / 64) {
       const int q = kb * 64 + lane;
       const int r = q >> 3;
@@ -455,7 +473,7 @@ __device__ __forceinline__ void bd_tile(
 // (2 per CU): 1 612 layer-2 tiles take 4 rounds for 3.15 rounds of work, 872 layer-3 tiles 2 for 1.70
 // (tools/bd_timeline.py: slot occupancy 0.79 / 0.85).  Smaller tiles for the last, partial round measured -5 % per
 // launch alone, but inside the two-stream step the other view already fills those tails (38.0 vs 37.7 ms/step).
-template <bool GATHER, int ABL, int MS, int RED, int WN = 2>
+template <bool GATHER, int ABL, int MS, int RED, int WN = 2, bool PAD = false>
 __global__ __launch_bounds__(BD_THREADS, ((MS == 4 || WN == 1) ? 2 : 3)) void conv_igemm_bd_kernel(
     const iic_conv_geom g, const bf16_t* __restrict__ in, const unsigned char* __restrict__ wfrag,
     bf16_t* __restrict__ out, float* __restrict__ stats, const bf16_t* __restrict__ res_grad,
@@ -463,7 +481,7 @@ __global__ __launch_bounds__(BD_THREADS, ((MS == 4 || WN == 1) ? 2 : 3)) void co
     const bf16_t* __restrict__ red_y, const float* __restrict__ red_coef,
     const bf16_t* __restrict__ red_y2, float* __restrict__ red_stats, float* __restrict__ red_stats2,
     unsigned long long* __restrict__ prof, const bd_blk B) {
-  bd_tile<GATHER, ABL, MS, RED, WN>(g, in, wfrag, out, stats, res_grad, res_act, accumulate, lds_a_bytes, red_y,
+  bd_tile<GATHER, ABL, MS, RED, WN, PAD>(g, in, wfrag, out, stats, res_grad, res_act, accumulate, lds_a_bytes, red_y,
                                     red_coef, red_y2, red_stats, red_stats2, prof, (int)blockIdx.x,
                                     num_mtiles * (g.Cout / (WN * 64)), B);
 }
@@ -515,10 +533,10 @@ static constexpr unsigned long long* g_bd_prof = nullptr;
 
 // ms: 4 = 256-row tiles, 2 = 128-row tiles (the kernel's MS)
 // (wn: the kernel's WN -- 1 = 64-cout tiles of ms*128 rows)
-static long bd_lds_a(const iic_conv_geom* g, int ms, int wn = 2) {
+static long bd_lds_a(const iic_conv_geom* g, int ms, int wn = 2, bool pad = false) {
   const long bm = ms * 32 * (4 / wn);
   const long npix = g->ntaps == 1 ? bm : (bm >= 192 ? g->NP256 : g->NP);
-  long a = (npix * 128 + 1023) & ~1023L;
+  long a = pad ? pt144_bytes(npix) : (npix * 128 + 1023) & ~1023L;
   long c = bm * (wn * 64 + 8) * 2;
   long m = a > c ? a : c;
   return (m + 15) & ~15L;
@@ -528,8 +546,21 @@ static long bd_key_bytes(const iic_conv_geom* g, int ms, int wn = 2) {    // swi
   const int jskip = (g->ntaps > 1 && g->sx == 1 && ((g->in_Wp - g->MX) & 1) == 0) ? g->in_Wp - g->MX : 0;
   return jskip != 0 ? (((long)(ms * 32 * (4 / wn) >= 192 ? g->NP256 : g->NP) + 15) & ~15L) : 0;
 }
-static long bd_lds_total(const iic_conv_geom* g, int ms, int wn = 2) {
-  return bd_lds_a(g, ms, wn) + 2L * ms * 32 * (4 / wn) * 4 + 4L * BD_BN * 4 + bd_key_bytes(g, ms, wn);
+static long bd_lds_total(const iic_conv_geom* g, int ms, int wn = 2, bool pad = false) {
+  return bd_lds_a(g, ms, wn, pad) + 2L * ms * 32 * (4 / wn) * 4 + 4L * BD_BN * 4 + (pad ? 0 : bd_key_bytes(g, ms, wn));
+}
+// The patch form (common.h IIC_BD_PITCH144: the product's constexpr; a switch in the instrumented library)
+IIC_SWITCH(g_bd_pitch144, IIC_BD_PITCH144, iic_debug_bd_pitch144)
+#ifdef IIC_DEBUG_HOOKS
+IIC_HOOK int iic_debug_get_bd_pitch144(void) { return g_bd_pitch144; }
+#endif
+// Padded patch for a row-major 128-cout launch of tile height ms: stride-1 multi-tap geometries where the + 12.5 % of
+// patch bytes cost no workgroup of a CU (256-row tiles run 2 per CU up to 80 KB, 128-row tiles 3 up to 53 KB; a patch
+// that already has a CU to itself stays as it is)
+static bool bd_pad_ok(const iic_conv_geom* g, int ms) {
+  if (!g_bd_pitch144 || g->ntaps < 2 || g->sx != 1 || g->sy != 1) return false;
+  const long cap = ms == 4 ? 80 * 1024 : 160 * 1024 / 3;
+  return bd_lds_total(g, ms, 2, true) <= cap;
 }
 // 64-cout tiles (kernel WN = 1, 256 rows): layers whose Cout is an odd multiple of 64
 IIC_SWITCH(g_bd_w1, 1, iic_debug_bd_w1)
@@ -686,8 +717,9 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
   const int mt = blocked ? g->N * BB.nbx * BB.nby : (int)((M + bm - 1) / bm);
   const int nt = g->Cout / BD_BN;
   const int grid = mt * nt;
-  int la = (int)bd_lds_a(g, ms);
-  long lds = bd_lds_total(g, ms);
+  const bool pad = !blocked && iic_debug_get_ablate() == 0 && bd_pad_ok(g, ms);
+  int la = (int)bd_lds_a(g, ms, 2, pad);
+  long lds = bd_lds_total(g, ms, 2, pad);
   if (blocked) {
     const long a = ((long)BB.npix * 128 + 1023) & ~1023L, c = (long)BD_BM * (BD_BN + 8) * 2;
     la = (int)(((a > c ? a : c) + 15) & ~15L);
@@ -695,11 +727,16 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
   }
   hipStream_t s = (hipStream_t)stream;
   int rc = IIC_OK;
-#define BD_LAUNCH4(GA_, AB_, MS_, RD_)                                                            \
-  rc = iic_launch_lds<conv_igemm_bd_kernel<GA_, AB_, MS_, RD_>>(                                 \
+#define BD_LAUNCH5(GA_, AB_, MS_, RD_, PD_)                                                       \
+  rc = iic_launch_lds<conv_igemm_bd_kernel<GA_, AB_, MS_, RD_, 2, PD_>>(                         \
       dim3(grid), dim3(BD_THREADS), lds, s, *g, (const bf16_t*)in, (const unsigned char*)wfrag,  \
       (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, mt, la,  \
       (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_bd_prof, BB)
+#define BD_LAUNCH4(GA_, AB_, MS_, RD_)                                                            \
+  do {                                                                                           \
+    if (!GA_ && AB_ == 0 && pad) BD_LAUNCH5(false, 0, MS_, RD_, true);                           \
+    else BD_LAUNCH5(GA_, AB_, MS_, RD_, false);                                                  \
+  } while (0)
 #define BD_LAUNCH3(GA_, AB_, MS_)                                                                 \
   do {                                                                                           \
     if ((AB_ != 0 && AB_ != 128 && AB_ != 256) || GA_ || red == 0) {                             \
@@ -730,12 +767,25 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
     case 96: BD_LAUNCH(false, 96); break;
     case 128: BD_LAUNCH(false, 128); break;
     case 256: BD_LAUNCH(false, 256); break;
-    case 512: BD_LAUNCH(false, 512); break;
 #endif
     default: BD_LAUNCH(false, 0); break;
   }
   return rc ? rc : iic_launch_status();
 }
+
+#ifdef IIC_DEBUG_HOOKS
+IIC_HOOK int iic_debug_pw_pitch144_used(const iic_conv_geom* g);
+// Which launch of iic_conv_igemm_frag_red reads a padded patch under the switches in force: 0 = none (swizzled rows,
+// block tiles, the 64 -> 64 kernel, 64-cout tiles), 1 = conv_igemm_bd_kernel, 2 = conv_igemm_pw_kernel (tests)
+IIC_HOOK int iic_debug_bd_pitch144_used(const iic_conv_geom* g) {
+  if (!g || !iic_conv_igemm_frag_supported(g) || (g_p64_enabled && iic_p64_supported(g))) return 0;
+  if (iic_debug_get_ablate() == 0 && g_bd_ms == 0 && iic_pw_supported(g)) return iic_debug_pw_pitch144_used(g) ? 2 : 0;
+  bd_blk B;
+  if (g->Cout % BD_BN != 0 || iic_debug_get_ablate() != 0 || bd_block_config(g, &B, 2)) return 0;
+  const int ms = bd_pick_ms(g);
+  return ms != 0 && bd_pad_ok(g, ms) ? 1 : 0;
+}
+#endif
 
 // All weight operands of a network in ONE launch (jobs in device memory, see iic_weight_prep_job): a train step
 // re-lays ~70 convolution weights into 1-2 operand layouts each after the optimiser step -- 136 launches of

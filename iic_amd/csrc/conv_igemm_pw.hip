@@ -26,6 +26,12 @@
 //     offsets (no per-load VALU), so a wave that is alone on its SIMD still issues MFMAs back to back.
 // LDS: patch (NP256 rows x 128 B) + 4 x 4.5 KB staging + 1 KB of swizzle keys  => two workgroups per CU up to
 // NP256 = 476.
+//
+// PAD (template): the patch at a 144-byte row pitch instead of XOR-swizzled 128-byte rows (conv_tile.h ROWB, PT144_*):
+// an A-fragment address is a per-tile lane base + the tap's scalar offset + an immediate per k-step -- one add per
+// (tap, sub-tile) where the swizzle costs a key, a shift and two XORs per read -- and the DMA needs no key table.
+// Same MFMA sequence, same operands: bit-identical results.  LDS: ceil(NP256 / 7) x 1008 B + 16 + staging => two
+// workgroups per CU up to NP256 = 434; the host keeps larger patches on the swizzled form (pw_pad_ok).
 #include <type_traits>
 
 #include "common.h"
@@ -68,6 +74,7 @@ struct pw_args {
   int M;               // GEMM rows
   int in_pixels;       // N * in_Hp * in_Wp
   int pad_rows;        // 1: g.MP pads the per-image row count (rows >= plane are invalid)
+  int nj;              // PAD: LDS-DMA pieces of 7 patch rows (ceil(npix / 7))
 };
 
 // B fragment: 16 bytes per lane from (scalar base + per-lane offset + immediate); inline asm so that hipcc's
@@ -89,6 +96,17 @@ __device__ __forceinline__ void pw_dma16(const void* gsrc, unsigned lds_dst) {
       "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
       : "=&s"(keep)
       : "v"(gsrc), "s"(lds_dst)
+      : "memory");
+}
+
+// PAD form of pw_dma16: the source is a wave-uniform base + a 32-bit lane offset (the lane's (row, 16-byte slot) inside
+// a 7-row piece is the same for every piece: no per-instruction address VALU)
+__device__ __forceinline__ void pw_dma16s(unsigned voff, const unsigned char* sbase, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds_dst)
       : "memory");
 }
 
@@ -207,7 +225,7 @@ __device__ __forceinline__ void pw_store_pass(const bf16_t* sW, int u0, const in
 // PROF (results correct): wave 0 sums s_memtime per phase over its tiles into prof[blockIdx][PW_PROF_SLOTS]:
 // 0 waiting for the patch (tile top), 1 K loop incl. boundaries, 2 boundaries, 3 epilogue, 4 everything, 5 tiles,
 // 6 boundary count, 7 XCC id
-template <int RED, bool PROF>
+template <int RED, bool PROF, bool PAD>
 __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
     const iic_conv_geom g, const pw_args A, const bf16_t* __restrict__ in, const unsigned char* __restrict__ wfrag,
     bf16_t* __restrict__ out, float* __restrict__ stats, const bf16_t* __restrict__ res_grad,
@@ -248,9 +266,10 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
   int mtile = mt_lo + kx;
   if (mtile >= mt_hi) return;
 
-  const int v_tapoff = g.tap_off[lane & (IIC_MAX_TAPS - 1)];
+  // (PAD: tap offsets in bytes of the padded patch; no dense count)
+  const int v_tapoff = g.tap_off[lane & (IIC_MAX_TAPS - 1)] * (PAD ? ROWB : 1);
   const int v_tapw = g.tap_w[lane & (IIC_MAX_TAPS - 1)];
-  const int v_tapd = v_tapoff - A.jskip * pw_divide(v_tapoff, A.d_wp);
+  const int v_tapd = PAD ? 0 : v_tapoff - A.jskip * pw_divide(v_tapoff, A.d_wp);
   const int nchunks = g.Cin >> 6, ntaps = g.ntaps, NIT = nchunks * ntaps;
   const int nblk = A.patch_bytes >> 10;
   const long frag_it = (long)(g.Cout >> 5) * 4096;      // bytes per (tap, chunk)
@@ -267,6 +286,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
     return __builtin_amdgcn_readfirstlane(pin);
   };
   auto write_keys = [&](int p_lo_t, int kb) {
+    if (PAD) return;
     for (int r = tid; r < PW_KEYS; r += PW_THREADS) {
       const int p = p_lo_t + r;
       const int prow = pw_divide(p, A.d_wp);
@@ -276,7 +296,25 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
     }
   };
   // piece q -> LDS byte q * 16 (row q >> 3, physical slot q & 7), source = logical slot (q & 7) ^ key(row)
+  // PAD: piece j = patch rows 7j ... 7j + 6 at LDS byte 1008 j (63 lanes: row lane / 9, slot lane % 9; slot 8 is the pad
+  // and re-reads slot 7's line) + lane 63 = the first 16 bytes of row 7j + 7, which piece j + 1 writes again with the
+  // same data.  The lane's source offset inside a piece is a constant of the launch; a piece's base is scalar.  Only a
+  // piece that reaches past the input's last pixel (the launch's last tiles) clamps its rows per lane.
+  const int dma_rl = lane / 9;
+  const unsigned dma_pc = (unsigned)min(lane - dma_rl * 9, 7) * 16u;
+  const unsigned dma_voff = (unsigned)(dma_rl * g.Cin * 2) + dma_pc;
   auto dma_patch = [&](int p_lo_t, int c0, int kb) {
+    if (PAD) {
+      const unsigned char* tb = reinterpret_cast<const unsigned char*>(in + ((long)p_lo_t * g.Cin + c0));
+      const int rmax = A.in_pixels - 1 - p_lo_t, rowb = g.Cin * 2;
+      for (int j = wave; j < A.nj; j += PW_THREADS / 64) {
+        const int r0 = j * PT144_ROWS;
+        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)(j * PT144_PIECE)));
+        if (r0 + PT144_ROWS <= rmax) pw_dma16s(dma_voff, tb + (long)r0 * rowb, dst);
+        else pw_dma16s((unsigned)(min(r0 + dma_rl, rmax) * rowb) + dma_pc, tb, dst);
+      }
+      return;
+    }
     for (int blk = wave; blk < nblk; blk += PW_THREADS / 64) {
       const int q = blk * 64 + lane;
       const int r = q >> 3;
@@ -311,24 +349,26 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
     }
 
     // ---- this lane's four rows: patch row index at tap offset 0 and dense count ----
+    // (PAD: arow = LDS byte address of the lane's half of the row's first k-step)
     int arow[4], drow[4];
 #pragma unroll
     for (int ms = 0; ms < 4; ++ms) {
       int pin, prow, pout;
       pw_row(g, A, m0 + wm * 128 + ms * 32 + l31, pin, prow, pout);
-      arow[ms] = pin - p_lo;
-      drow[ms] = pin - A.jskip * prow;
+      arow[ms] = PAD ? (int)lds0 + (pin - p_lo) * ROWB + g5 * 16 : pin - p_lo;
+      drow[ms] = PAD ? 0 : pin - A.jskip * prow;
     }
     int p_lo_next = 0;
     if (has_next) {
       p_lo_next = tile_plo(mnext);
       write_keys(p_lo_next, kb ^ 1);          // (that buffer's last reader was the previous tile's DMA issue)
     }
-    auto tap_p = [&](int ms, int toff, int td) {
+    auto tap_p = [&](int ms, int toff, int td) {       // LDS byte address of the tap's first A fragment (less ka)
+      if (PAD) return arow[ms] + toff;
       const int R = arow[ms] + toff, D = drow[ms] + td;
-      return (R << 7) + ((((D >> 1) ^ g5) & 1) << 4);
+      return (int)lds0 + (R << 7) + ((((D >> 1) ^ g5) & 1) << 4);
     };
-    auto tap_k = [&](int ms, int td) { return (((drow[ms] + td) >> 2) & 3) << 5; };
+    auto tap_k = [&](int ms, int td) { return PAD ? 0 : (((drow[ms] + td) >> 2) & 3) << 5; };
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -364,7 +404,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
       const int toff = __builtin_amdgcn_readlane(v_tapoff, 0), td = __builtin_amdgcn_readlane(v_tapd, 0);
 #pragma unroll
       for (int ms = 0; ms < 4; ++ms) {
-        pa[0][ms] = (int)lds0 + tap_p(ms, toff, td);
+        pa[0][ms] = tap_p(ms, toff, td);
         ka[0][ms] = tap_k(ms, td);
         a[0][ms] = lds16(pa[0][ms] + ka[0][ms]);
       }
@@ -403,7 +443,8 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
 #pragma unroll
         for (int ms = 0; ms < 4; ++ms) {
           acc[ms][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][ms], b0, acc[ms][0], 0, 0, 0);
-          a[nxt][ms] = (ks < 3) ? lds16(pa[P][ms] + (((ks + 1) << 5) ^ ka[P][ms])) : lds16(pa[Q][ms] + ka[Q][ms]);
+          if (PAD) a[nxt][ms] = (ks < 3) ? lds16(pa[P][ms] + ((ks + 1) << 5)) : lds16(pa[Q][ms]);
+          else a[nxt][ms] = (ks < 3) ? lds16(pa[P][ms] + (((ks + 1) << 5) ^ ka[P][ms])) : lds16(pa[Q][ms] + ka[Q][ms]);
           __builtin_amdgcn_sched_barrier(0);
         }
         pw_bwait<6>(Bc[ks][1]);
@@ -417,7 +458,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
         for (int ms = 0; ms < 4; ++ms) {
           acc[ms][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][ms], b1, acc[ms][1], 0, 0, 0);
           // the NEXT tap's addresses, one piece per MFMA gap (needed by k-step 3's reads)
-          if (ks == 0) pa[Q][ms] = (int)lds0 + tap_p(ms, toffn, tdn);
+          if (ks == 0) pa[Q][ms] = tap_p(ms, toffn, tdn);
           if (ks == 1) ka[Q][ms] = tap_k(ms, tdn);
           // the scalars of the iteration after the next
           if (ks == 2 && ms == 0) advance(tap_n, chunk_n, tap_2, chunk_2, more_2, bnd_2);
@@ -604,7 +645,8 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
   }
 }
 
-IIC_SWITCH(g_pw_enabled, 1, iic_debug_enable_pw)
+IIC_SWITCH(g_pw_enabled, 1, iic_debug_enable_pw)      // 2: wherever the shape is supported, however few tiles (tests)
+IIC_SWITCH(g_pw_gx_cap, 0, iic_debug_pw_gx_cap)       // > 0: at most this many workgroups per XCD (tests: multi-tile walks at small shapes)
 #ifdef IIC_DEBUG_HOOKS
 static unsigned long long* g_pw_prof = nullptr;
 IIC_HOOK void iic_debug_pw_prof(void* buf) { g_pw_prof = (unsigned long long*)buf; }
@@ -614,9 +656,14 @@ IIC_HOOK int iic_debug_pw_grid(const iic_conv_geom* g);
 static constexpr unsigned long long* g_pw_prof = nullptr;
 #endif
 
-static long pw_lds_bytes(const iic_conv_geom* g) {
+static long pw_lds_bytes(const iic_conv_geom* g, bool pad = false) {
+  if (pad) return pt144_bytes(g->NP256) + 4 * PW_STG_BYTES;      // (no key table)
   const long patch = ((long)g->NP256 * 128 + 1023) & ~1023L;
   return patch + 4 * PW_STG_BYTES + 2 * PW_KEYS;
+}
+// the padded patch where it keeps two workgroups per CU (stride 1: the form's scope)
+static bool pw_pad_ok(const iic_conv_geom* g) {
+  return iic_debug_get_bd_pitch144() != 0 && g->sx == 1 && g->sy == 1 && pw_lds_bytes(g, true) <= 80 * 1024;
 }
 
 static int pw_num_cus();
@@ -625,7 +672,7 @@ int iic_pw_supported(const iic_conv_geom* g) {
   if (!g || !g_pw_enabled || !pw_supported_shape(g)) return 0;
   const long M = igemm_rows_host(g);
   // take a launch only if it has at least 2.5 tiles per workgroup slot
-  if (((M + 255) / 256) * (g->Cout / 128) * 10 < 25L * 2 * pw_num_cus()) return 0;
+  if (g_pw_enabled != 2 && ((M + 255) / 256) * (g->Cout / 128) * 10 < 25L * 2 * pw_num_cus()) return 0;
   return 1;
 }
 static int pw_supported_shape(const iic_conv_geom* g) {
@@ -663,11 +710,14 @@ static int pw_grid(const iic_conv_geom* g, long lds) {
   const int slots = (lds <= 80 * 1024 ? 2 : 1) * pw_num_cus();
   int gx = slots / 8;
   if (gx > longest) gx = longest;
+  if (g_pw_gx_cap > 0 && gx > g_pw_gx_cap) gx = g_pw_gx_cap;
   if (gx < 1) gx = 1;
   return gx * 8;
 }
 #ifdef IIC_DEBUG_HOOKS
 IIC_HOOK int iic_debug_pw_grid(const iic_conv_geom* g) { return g ? pw_grid(g, pw_lds_bytes(g)) : 0; }
+// 1 if this geometry's persistent launch takes the padded patch under the switches in force
+IIC_HOOK int iic_debug_pw_pitch144_used(const iic_conv_geom* g) { return g && iic_pw_supported(g) && pw_pad_ok(g) ? 1 : 0; }
 #endif
 
 int iic_pw_launch(const iic_conv_geom* g, const void* in, const void* wfrag, void* out, float* stats,
@@ -688,16 +738,23 @@ int iic_pw_launch(const iic_conv_geom* g, const void* in, const void* wfrag, voi
   A.M = (int)M;
   A.in_pixels = g->N * g->in_Hp * g->in_Wp;
   A.pad_rows = (g->MP > 0 && g->MP != A.plane) ? 1 : 0;
-  const long lds = pw_lds_bytes(g);
+  const bool pad = pw_pad_ok(g);
+  A.nj = (int)((g->NP256 + PT144_ROWS - 1) / PT144_ROWS);
+  if (pad) A.patch_bytes = (int)pt144_bytes(g->NP256);
+  const long lds = pw_lds_bytes(g, pad);
   const int grid = pw_grid(g, lds);
   const int red = red_y ? (red_y2 ? 2 : 1) : 0;
   hipStream_t s = (hipStream_t)stream;
   int rc = IIC_OK;
-#define PW_LAUNCH(RD_, PR_)                                                                                   \
-  rc = iic_launch_lds<conv_igemm_pw_kernel<RD_, PR_>>(                                                        \
+#define PW_LAUNCH2(RD_, PR_, PD_)                                                                             \
+  rc = iic_launch_lds<conv_igemm_pw_kernel<RD_, PR_, PD_>>(                                                   \
       dim3(grid), dim3(PW_THREADS), lds, s, *g, A, (const bf16_t*)in, (const unsigned char*)wfrag,            \
       (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, (const bf16_t*)red_y, \
       red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_pw_prof)
+#define PW_LAUNCH(RD_, PR_)                                                                                   \
+  do {                                                                                                        \
+    if (pad) PW_LAUNCH2(RD_, PR_, true); else PW_LAUNCH2(RD_, PR_, false);                                    \
+  } while (0)
 #ifdef IIC_DEBUG_HOOKS
   if (g_pw_prof) {
     if (red == 0) PW_LAUNCH(0, true); else if (red == 1) PW_LAUNCH(1, true); else PW_LAUNCH(2, true);

@@ -38,6 +38,15 @@ static inline bool igemm_dense_host(const iic_conv_geom* g) { return g->MP <= 0 
                    // sixteen 16-B slots over 16 consecutive rows => the 16-lane groups of
                    // ds_read_b128 are conflict-free, and every k-step is an IMMEDIATE offset
                    // (ks*32 B) from one per-tap row address: no address VALU in the MFMA loop.
+// The pitch-144 patch filled by LDS-DMA (conv_igemm_bd.hip / conv_igemm_pw.hip, template PAD).  A wave-instruction
+// writes 64 x 16 B lane-linear: 7 rows of 9 slots (63 lanes) + 1 slot.  Pieces are laid at 1008-byte steps, so piece j
+// is rows 7j ... 7j + 6 and lane l always holds (row l / 9, slot l % 9) of its piece -- constants of the launch, no
+// division by 9 per instruction; lane 63 pre-writes slot 0 of row 7j + 7 with what piece j + 1 writes there again.
+#define PT144_ROWS 7
+#define PT144_PIECE (PT144_ROWS * ROWB)
+static inline long pt144_bytes(long npix) {      // LDS bytes of an npix-row patch (the last piece's 64th lane included)
+  return ((npix + PT144_ROWS - 1) / PT144_ROWS) * PT144_PIECE + 16;
+}
 
 // XCD-aware tile order: blocks b, b+8, b+16.. share an XCD (observed dispatch); give each XCD
 // a contiguous range of tiles so neighbouring M-tiles (shared halo, shared weights) hit the

@@ -68,6 +68,8 @@ def main():
   ap.add_argument("--no-wgrad", action="store_true")
   ap.add_argument("--frag-ablate", type=str, default="", help="comma list of ablation codes for the frag kernel")
   ap.add_argument("--cold", action="store_true", help="also time every kernel with cold caches (a 1-GB fill in front of each launch)")
+  ap.add_argument("--pitch144", type=int, default=-1, help="patch form of the weights-direct kernels: 1 = rows at a 144-byte pitch "
+                  "where the geometry allows, 0 = swizzled 128-byte rows (default: the library's)")
   ap.add_argument("--no-pw", action="store_true", help="persistent kernel off: every launch on conv_igemm_bd_kernel (the ablation codes' baseline)")
   a = ap.parse_args()
   dev = torch.device("cuda:0")
@@ -77,6 +79,15 @@ def main():
     from iic_amd import _lib
     ctypes.CDLL(_lib.LIB_PATH).iic_debug_enable_pw(0)
     print("persistent kernel off")
+  if a.pitch144 >= 0:
+    import ctypes
+    from iic_amd import _lib
+    ctypes.CDLL(_lib.LIB_PATH).iic_debug_bd_pitch144(a.pitch144)
+    print("pitch144", a.pitch144)
+  ABL_CODES = (1, 2, 3, 4, 7, 15, 16, 31, 32, 64, 96, 128, 256)      # conv_igemm_bd.hip: the instantiations of an ABL=1 build
+  bad = [c for c in a.frag_ablate.split(",") if c and int(c) not in ABL_CODES]
+  if bad:
+    ap.error("--frag-ablate: no such ablation code: %s (have %s)" % (",".join(bad), ABL_CODES))
   if a.bm:
     import ctypes
     from iic_amd import _lib
