@@ -616,11 +616,12 @@ int iic_stem_apply_pool(const float* x, const float* w, const float* coef, void*
   if (rc) return rc;
   if (!coef || !out_pt) return IIC_ERR_ARG;
   const int nseg = (W + 31) / 32, Ho = H / 2 + 1;
+  // 256 * W bytes: above the 48 KB default from W = 194 on (64 KB at W = 256)
   const size_t lds = (size_t)2 * W * STEM_CO * sizeof(bf16_t);
-  STEM_DISPATCH(Cin, hipLaunchKernelGGL(stem_apply_pool_kernel<CI>, dim3(N * Ho), dim3(64 * nseg),
-                                        lds, (hipStream_t)stream, x, w, coef, (bf16_t*)out_pt, N, H,
-                                        W));
-  return iic_launch_status();
+  STEM_DISPATCH(Cin, rc = iic_launch_lds<stem_apply_pool_kernel<CI>>(dim3(N * Ho), dim3(64 * nseg), lds,
+                                                                     (hipStream_t)stream, x, w, coef,
+                                                                     (bf16_t*)out_pt, N, H, W));
+  return rc ? rc : iic_launch_status();
 }
 
 static size_t stem_bwd_lds(int Cin, int W, int nseg, int mode) {
@@ -635,6 +636,12 @@ static size_t stem_bwd_lds(int Cin, int W, int nseg, int mode) {
   size_t b1 = (size_t)nseg * 64 * ((Cin * 9 + 31) / 32) * 32 * sizeof(float);
   size_t b = mode == 0 ? b0 : (b1 > b0 ? b1 : b0);
   return a > b ? a : b;
+}
+// stem_bwd_kernel keeps s_cf (5 x 64 floats, static) next to its dynamic LDS: both must fit the workgroup's LDS.
+// MODE 0 fits at every width stem_check admits (129 KB at W = 256); MODE 1 / 2 hold the transposed dy tile and
+// the input rows as well and stop between W = 186 (Cin = 5) and W = 204 (Cin = 1).
+static bool stem_bwd_fits(int Cin, int W, int mode) {
+  return stem_bwd_lds(Cin, W, (W + 31) / 32, mode) + 5 * STEM_CO * sizeof(float) <= (size_t)IIC_LDS_BYTES;
 }
 
 int iic_stem_bwd_reduce(const float* x, const float* w, const float* coef, const void* dpool_pt,
@@ -664,6 +671,9 @@ int iic_stem_bwd_fused(const float* x, const float* w, const float* coef, const 
   int rc = stem_check(x, w, N, Cin, H, W);
   if (rc) return rc;
   if (!coef || !dpool_pt || !sums || !partials || !nblocks_out) return IIC_ERR_ARG;
+  // register-resident routing (stem_bwd2.hip) where it applies; else stem_bwd_kernel<CIN, 2>, whose LDS bounds W
+  const bool bwd2 = g_stem_bwd2 && iic_stem_bwd2_supported(Cin, W);
+  if (!bwd2 && !stem_bwd_fits(Cin, W, 2)) return IIC_ERR_UNSUPPORTED;      // before anything is launched
   const int nseg = (W + 31) / 32, Ho = H / 2 + 1;
   long items = (long)N * Ho;
   int grid = (int)(items < STEM_PERSIST_BLOCKS ? items : STEM_PERSIST_BLOCKS);
@@ -671,7 +681,7 @@ int iic_stem_bwd_fused(const float* x, const float* w, const float* coef, const 
   float* g3 = partials + (long)STEM_PERSIST_BLOCKS * 128 * 64;
   hipLaunchKernelGGL(stem_patch_sums_kernel, dim3(STEM_G3_BLOCKS, Cin), dim3(256), 0, (hipStream_t)stream,
                      x, g3, N, Cin, H, W);
-  if (g_stem_bwd2 && iic_stem_bwd2_supported(Cin, W))      // register-resident routing (stem_bwd2.hip)
+  if (bwd2)
     return iic_stem_bwd2_launch(x, w, coef, dpool_pt, sums, partials, nblocks_out, N, Cin, H, W, stream);
   const size_t lds = stem_bwd_lds(Cin, W, nseg, 2);
   STEM_DISPATCH(Cin, rc = iic_launch_lds<stem_bwd_kernel<CI, 2>>(
@@ -697,6 +707,7 @@ int iic_stem_bwd_wgrad(const float* x, const float* w, const float* coef, const 
   int rc = stem_check(x, w, N, Cin, H, W);
   if (rc) return rc;
   if (!coef || !bcoef || !dpool_pt || !partials || !dW) return IIC_ERR_ARG;
+  if (!stem_bwd_fits(Cin, W, 1)) return IIC_ERR_UNSUPPORTED;
   const int nseg = (W + 31) / 32, Ho = H / 2 + 1;
   long items = (long)N * Ho;
   int grid = (int)(items < STEM_PERSIST_BLOCKS ? items : STEM_PERSIST_BLOCKS);

@@ -311,14 +311,16 @@ int iic_stem_bwd2_launch(const float* x, const float* w, const float* coef, cons
   const size_t xr = (size_t)Cin * 4 * (nseg * 32 + 4) * sizeof(float);
   const size_t lds = 2 * xr + (size_t)128 * 33 * sizeof(float) + (size_t)2 * ((Cin * 9 + 1) / 2) * 64 * sizeof(float) +
                      (size_t)2 * (((W / 2 + 1) * STEM_CO + 7) & ~7) * sizeof(bf16_t);
+  // (above the 48 KB default from W = 104 at Cin = 3; 80 KB at the widest image, Cin = 3, W = 254)
+  int rc = IIC_OK;
 #define BWD2_LAUNCH(CI_)                                                                          \
-  hipLaunchKernelGGL(stem_bwd2_kernel<CI_>, dim3(grid), dim3(64 * nseg), lds, (hipStream_t)stream, x, \
-                     w, coef, (const bf16_t*)dpool_pt, partials, sums, N, H, W, iic_debug_get_ablate())
+  rc = iic_launch_lds<stem_bwd2_kernel<CI_>>(dim3(grid), dim3(64 * nseg), lds, (hipStream_t)stream, x, w, coef, \
+                                             (const bf16_t*)dpool_pt, partials, sums, N, H, W, iic_debug_get_ablate())
   switch (Cin) {
     case 1: BWD2_LAUNCH(1); break;
     case 2: BWD2_LAUNCH(2); break;
     case 3: BWD2_LAUNCH(3); break;
     default: return IIC_ERR_UNSUPPORTED;
   }
-  return iic_launch_status();
+  return rc ? rc : iic_launch_status();
 }

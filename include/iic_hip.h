@@ -251,6 +251,12 @@ int iic_bn_bwd_apply(const void* dout, const void* act, const void* y, const flo
  * Stem: conv3x3(Cin<=5 -> 64, pad 1, no bias) + BN + ReLU + MaxPool(k2,s2,p1), computed
  * from the fp32 NCHW input with exact-fp32 MFMA and RECOMPUTED in every pass instead of
  * materialising the 96x96x64 tensor.  Replaces net5g.py:21-26,42-45.
+ * Shapes: 1 <= Cin <= 5, H and W even and >= 2.  Widths served (IIC_ERR_UNSUPPORTED beyond,
+ * before anything is launched):
+ *   iic_stem_stats, iic_stem_apply_pool, iic_stem_bwd_reduce: W <= 256 (8 waves of 32 columns);
+ *   iic_stem_bwd_wgrad: the two conv rows, the transposed dy tile and four input rows must fit
+ *     the workgroup's 160 KB of LDS -- W <= 204, 196, 192, 192, 186 for Cin = 1 .. 5;
+ *   iic_stem_bwd_fused: W <= 254 for Cin <= 3 (register-resident kernel), else as iic_stem_bwd_wgrad.
  * ------------------------------------------------------------------------------- */
 int iic_stem_stats(const float* x, const float* w, float* stats, int N, int Cin, int H, int W,
                    void* stream);
