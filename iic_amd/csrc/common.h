@@ -51,6 +51,28 @@ static inline int iic_launch_status() {
 
 // LDS of one gfx950 workgroup: the ceiling of every launch's static + dynamic LDS
 static constexpr long IIC_LDS_BYTES = 160 * 1024;
+// ... and the most a workgroup may take for two / three of them to share a CU
+static constexpr long IIC_LDS_WG2 = IIC_LDS_BYTES / 2;
+static constexpr long IIC_LDS_WG3 = IIC_LDS_BYTES / 3;
+
+// CUs of the current device (the persistent kernels' grids); 256 where there is no device to ask
+inline int iic_num_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+      n = v;
+    else
+      n = 256;
+  }
+  return n;
+}
+// profiling stamp of the kernels' PROF builds: HW_REG_HW_ID in the low word, XCC_ID in the high word
+__device__ __forceinline__ unsigned long long iic_hw_stamp() {
+  return (unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4) |
+         ((unsigned long long)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) << 32);
+}
 
 // The one way to launch a kernel whose dynamic LDS may exceed the 48 KB a kernel gets by default.  Every
 // instantiation remembers the largest limit it has been given and raises it only when a launch needs more (to that

@@ -18,6 +18,7 @@
 //     halved again); workgroup = 256 x 128 tile, 4 waves as 2(M) x 2(N), 2 workgroups per CU.
 // Geometry, PT layout, fused BN statistics / residual-gradient epilogue: as conv_igemm.hip.
 #include "common.h"
+#include "conv_plan.h"
 #include "conv_tile.h"
 #include "../../include/iic_hip.h"
 
@@ -41,10 +42,7 @@ __device__ __forceinline__ void bd_bwait(u32x4& d) {
 // 41-51 KB (two workgroups per CU again).  Everything behind the patch loader works in PATCH coordinates: the row
 // table holds ky * PW + kx, the tap offsets become iy * PW + ix, the swizzle key counts patch rows.  Which tile computes
 // an output row changes; the row's own accumulation order does not: outputs are bit-identical to the row-major tiles.
-struct bd_blk {
-  int bw, bh, nbx, nby;      // bw == 0: row-major tiles
-  int PW, npix, mul;         // patch width, patch pixels, ceil(65536 / PW) (patch row / PW by multiply-shift)
-};
+// (struct bd_blk: conv_plan.h)
 
 #define BD_BM 256
 #define BD_BN 128
@@ -93,7 +91,6 @@ __device__ __forceinline__ void bd_tile(
   const bool blk = CANBLK && !PAD && B.bw > 0;         // uniform
   constexpr int CLD = BNT + 8;
   constexpr bool PROF = (ABL & 128) != 0;
-  constexpr bool NEWORD = (ABL & 256) == 0;     // ABL bit 256: the round-2 K-loop order (A/B runs)
   static_assert(!(PAD && GATHER), "the padded patch is a multi-tap form");
   constexpr bool SWZ = !PAD;
   // PROF (ABL bit 128, results CORRECT): wave 0 stamps s_memtime at the phase boundaries of its tile
@@ -247,8 +244,7 @@ __device__ __forceinline__ void bd_tile(
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
       for (int ns = 0; ns < 2; ++ns)
-        if (NEWORD) bd_bload(Bc[ks][ns], p + ns * 4096 + ks * 1024);
-        else Bc[ks][ns] = *reinterpret_cast<const u32x4*>(p + ns * 4096 + ks * 1024);
+        bd_bload(Bc[ks][ns], p + ns * 4096 + ks * 1024);
   }
   dma_patch(0);
   __syncthreads();
@@ -316,45 +312,29 @@ __device__ __forceinline__ void bd_tile(
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int cur = ks & 1, nxt = cur ^ 1;
-      if (NEWORD) {
-        // Round 3 (tools/mfma_feed.py): [4 reads][8 MFMAs][2 loads] blocks leave the matrix pipe idle
-        // while a wave works through its feeder block; one LDS read between consecutive MFMAs keeps
-        // both pipes issuing (+5...14 % in the staged microbenchmark at these loop lengths).
-        // ns-major MFMA order: Bc[ks][0] is free after the first MS MFMAs and is re-filled there.
-        // In flight at the top of a k-step: the 8 loads of the next four k-steps, oldest first.
-        bd_bwait<7>(Bc[ks][0]);
-        __builtin_amdgcn_sched_barrier(0);
-        const bf16x8 b0 = __builtin_bit_cast(bf16x8, Bc[ks][0]);
-#pragma unroll
-        for (int ms = 0; ms < MS; ++ms) {
-          acc[ms][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][ms], b0, acc[ms][0], 0, 0, 0);
-          a_read(ks, nxt, cur, ms);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        bd_bwait<6>(Bc[ks][1]);
-        bd_bload(Bc[ks][0], nb + ks * 1024);
-        __builtin_amdgcn_sched_barrier(0);
-        const bf16x8 b1 = __builtin_bit_cast(bf16x8, Bc[ks][1]);
-#pragma unroll
-        for (int ms = 0; ms < MS; ++ms)
-          acc[ms][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][ms], b1, acc[ms][1], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        bd_bload(Bc[ks][1], nb + 4096 + ks * 1024);
-        __builtin_amdgcn_sched_barrier(0);
-        continue;
-      }
-#pragma unroll
-      for (int ms = 0; ms < MS; ++ms) a_read(ks, nxt, cur, ms);
-      __builtin_amdgcn_sched_barrier(0);   // reads of the NEXT k-step issue before these MFMAs
+      // Round 3 (tools/mfma_feed.py): [4 reads][8 MFMAs][2 loads] blocks leave the matrix pipe idle
+      // while a wave works through its feeder block; one LDS read between consecutive MFMAs keeps
+      // both pipes issuing (+5...14 % in the staged microbenchmark at these loop lengths).
+      // ns-major MFMA order: Bc[ks][0] is free after the first MS MFMAs and is re-filled there.
+      // In flight at the top of a k-step: the 8 loads of the next four k-steps, oldest first.
+      bd_bwait<7>(Bc[ks][0]);
+      __builtin_amdgcn_sched_barrier(0);
       const bf16x8 b0 = __builtin_bit_cast(bf16x8, Bc[ks][0]);
-      const bf16x8 b1 = __builtin_bit_cast(bf16x8, Bc[ks][1]);
 #pragma unroll
       for (int ms = 0; ms < MS; ++ms) {
         acc[ms][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][ms], b0, acc[ms][0], 0, 0, 0);
-        acc[ms][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][ms], b1, acc[ms][1], 0, 0, 0);
+        a_read(ks, nxt, cur, ms);
+        __builtin_amdgcn_sched_barrier(0);
       }
-      Bc[ks][0] = *reinterpret_cast<const u32x4*>(nb + ks * 1024);
-      Bc[ks][1] = *reinterpret_cast<const u32x4*>(nb + 4096 + ks * 1024);
+      bd_bwait<6>(Bc[ks][1]);
+      bd_bload(Bc[ks][0], nb + ks * 1024);
+      __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 b1 = __builtin_bit_cast(bf16x8, Bc[ks][1]);
+#pragma unroll
+      for (int ms = 0; ms < MS; ++ms)
+        acc[ms][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][ms], b1, acc[ms][1], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      bd_bload(Bc[ks][1], nb + 4096 + ks * 1024);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -378,7 +358,7 @@ __device__ __forceinline__ void bd_tile(
 
   // the ring re-fills unconditionally (the last iteration's loads are never used): hipcc does not know
   // about them and would hand their destination registers to the epilogue while they are in flight
-  if (NEWORD) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // ---- epilogue ------------------------------------------------------------------------
   if (PROF) t_stamp[3] = __builtin_readcyclecounter();
   if (ABL & 4) {
@@ -462,8 +442,7 @@ __device__ __forceinline__ void bd_tile(
     const unsigned long long t_end = __builtin_readcyclecounter();
     q[0] = t_stamp[0]; q[1] = t_stamp[1]; q[2] = t_stamp[2]; q[3] = t_stamp[3]; q[4] = t_stamp[4];
     q[5] = t_end; q[6] = t_bsum; q[7] = (unsigned long long)t_nb;
-    q[8] = (unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4)     // HW_REG_HW_ID
-           | ((unsigned long long)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) << 32);  // XCC_ID
+    q[8] = iic_hw_stamp();
     q[9] = (unsigned long long)tix;
     q[10] = __builtin_amdgcn_s_memrealtime();
   }
@@ -507,17 +486,6 @@ __global__ void weight_prep_frag_kernel(const float* __restrict__ w, bf16_t* __r
   }
 }
 
-// conv_igemm_p64.hip: persistent DMA-fed kernel for the 64 -> 64 channel 3x3 layers
-int iic_p64_supported(const iic_conv_geom* g);
-int iic_p64_launch(const iic_conv_geom* g, const void* in, const void* wfrag, void* out, float* stats,
-                   const void* res_grad, const void* res_act, int accumulate, const void* red_y,
-                   const float* red_coef, const void* red_y2, float* red_stats, float* red_stats2,
-                   void* stream);
-// conv_igemm_pw.hip: persistent kernel for the stride-1 multi-tap launches (round 4)
-int iic_pw_supported(const iic_conv_geom* g);
-int iic_pw_launch(const iic_conv_geom* g, const void* in, const void* wfrag, void* out, float* stats,
-                  const void* res_grad, const void* res_act, int accumulate, const void* red_y,
-                  const float* red_coef, const void* red_y2, float* red_stats, float* red_stats2, void* stream);
 IIC_SWITCH(g_p64_enabled, 1, iic_debug_enable_p64)
 IIC_SWITCH(g_p64_red, 0, iic_debug_p64_red)      // 1: allow the fused reduction in the persistent kernel (tests, A/B)
 
@@ -531,23 +499,23 @@ IIC_HOOK int iic_debug_bd_prof_slots(void) { return BD_PROF_SLOTS; }
 static constexpr unsigned long long* g_bd_prof = nullptr;
 #endif
 
-// ms: 4 = 256-row tiles, 2 = 128-row tiles (the kernel's MS)
-// (wn: the kernel's WN -- 1 = 64-cout tiles of ms*128 rows)
-static long bd_lds_a(const iic_conv_geom* g, int ms, int wn = 2, bool pad = false) {
-  const long bm = ms * 32 * (4 / wn);
-  const long npix = g->ntaps == 1 ? bm : (bm >= 192 ? g->NP256 : g->NP);
-  long a = pad ? pt144_bytes(npix) : (npix * 128 + 1023) & ~1023L;
-  long c = bm * (wn * 64 + 8) * 2;
-  long m = a > c ? a : c;
-  return (m + 15) & ~15L;
+// The LDS of a conv_igemm_bd_kernel launch: the patch of `npix` pixels (or the epilogue's rows x couts tile, which reuses
+// it, if larger), the two row tables, s_red, and the swizzle-key table (1 B per patch row) where the launch has one.
+// Returns the total; *lds_a = the bytes in front of the row tables.
+static long bd_lds(long npix, int rows, int couts, bool pad, bool keys, int* lds_a = nullptr) {
+  const long a = pad ? pt144_bytes(npix) : (npix * 128 + 1023) & ~1023L;
+  const long c = (long)rows * (couts + 8) * 2;
+  const long la = ((a > c ? a : c) + 15) & ~15L;
+  if (lds_a) *lds_a = (int)la;
+  return la + 2L * rows * 4 + 4L * BD_BN * 4 + (keys ? (npix + 15) & ~15L : 0);
 }
-
-static long bd_key_bytes(const iic_conv_geom* g, int ms, int wn = 2) {    // swizzle-key table of the DMA patch (1 B / row)
-  const int jskip = (g->ntaps > 1 && g->sx == 1 && ((g->in_Wp - g->MX) & 1) == 0) ? g->in_Wp - g->MX : 0;
-  return jskip != 0 ? (((long)(ms * 32 * (4 / wn) >= 192 ? g->NP256 : g->NP) + 15) & ~15L) : 0;
-}
-static long bd_lds_total(const iic_conv_geom* g, int ms, int wn = 2, bool pad = false) {
-  return bd_lds_a(g, ms, wn, pad) + 2L * ms * 32 * (4 / wn) * 4 + 4L * BD_BN * 4 + (pad ? 0 : bd_key_bytes(g, ms, wn));
+// ... of row-major tiles.  ms: 4 = 256-row tiles, 2 = 128-row tiles (the kernel's MS); wn: the kernel's WN -- 1 = 64-cout
+// tiles of ms*128 rows.  A key table only for swizzled rows with a row-end skip (bd_tile jskip).
+static long bd_lds_rows(const iic_conv_geom* g, int ms, int wn = 2, bool pad = false, int* lds_a = nullptr) {
+  const int rows = ms * 32 * (4 / wn);
+  const long npix = g->ntaps == 1 ? rows : (rows >= 192 ? g->NP256 : g->NP);
+  const bool skip = g->ntaps > 1 && g->sx == 1 && ((g->in_Wp - g->MX) & 1) == 0 && g->in_Wp != g->MX;
+  return bd_lds(npix, rows, wn * 64, pad, !pad && skip, lds_a);
 }
 // The patch form (common.h IIC_BD_PITCH144: the product's constexpr; a switch in the instrumented library)
 IIC_SWITCH(g_bd_pitch144, IIC_BD_PITCH144, iic_debug_bd_pitch144)
@@ -555,26 +523,25 @@ IIC_SWITCH(g_bd_pitch144, IIC_BD_PITCH144, iic_debug_bd_pitch144)
 IIC_HOOK int iic_debug_get_bd_pitch144(void) { return g_bd_pitch144; }
 #endif
 // Padded patch for a row-major 128-cout launch of tile height ms: stride-1 multi-tap geometries where the + 12.5 % of
-// patch bytes cost no workgroup of a CU (256-row tiles run 2 per CU up to 80 KB, 128-row tiles 3 up to 53 KB; a patch
-// that already has a CU to itself stays as it is)
+// patch bytes cost no workgroup of a CU (256-row tiles run 2 per CU, 128-row tiles 3; a patch that already has a CU to
+// itself stays as it is)
 static bool bd_pad_ok(const iic_conv_geom* g, int ms) {
   if (!g_bd_pitch144 || g->ntaps < 2 || g->sx != 1 || g->sy != 1) return false;
-  const long cap = ms == 4 ? 80 * 1024 : 160 * 1024 / 3;
-  return bd_lds_total(g, ms, 2, true) <= cap;
+  return bd_lds_rows(g, ms, 2, true) <= (ms == 4 ? IIC_LDS_WG2 : IIC_LDS_WG3);
 }
 // 64-cout tiles (kernel WN = 1, 256 rows): layers whose Cout is an odd multiple of 64
 IIC_SWITCH(g_bd_w1, 1, iic_debug_bd_w1)
 static bool bd_w1_ok(const iic_conv_geom* g) {
   return g_bd_w1 && g->Cout % 64 == 0 && g->Cout % BD_BN != 0 && g->ntaps > 1 && g->NP256 > 0 &&
-         bd_lds_total(g, 2, 1) <= IIC_LDS_BYTES;
+         bd_lds_rows(g, 2, 1) <= IIC_LDS_BYTES;
 }
 // Tile height per geometry.  g_bd_ms: 0 = heuristic, 2 / 4 = forced (A/B runs, tests).
 IIC_SWITCH(g_bd_ms, 0, iic_debug_bd_ms)
 static int bd_pick_ms(const iic_conv_geom* g) {
   // (256-row tiles also where only one workgroup fits a CU: large-image segmentation layers, still 15-20 % faster
   // than conv_igemm_kernel)
-  const bool ok4 = (g->ntaps == 1 || g->NP256 > 0) && bd_lds_total(g, 4) <= IIC_LDS_BYTES;
-  const bool ok2 = (g->ntaps == 1 || g->NP > 0) && bd_lds_total(g, 2) <= IIC_LDS_BYTES;
+  const bool ok4 = (g->ntaps == 1 || g->NP256 > 0) && bd_lds_rows(g, 4) <= IIC_LDS_BYTES;
+  const bool ok2 = (g->ntaps == 1 || g->NP > 0) && bd_lds_rows(g, 2) <= IIC_LDS_BYTES;
   if (g_bd_ms == 4) return ok4 ? 4 : (ok2 ? 2 : 0);
   if (g_bd_ms == 2) return ok2 ? 2 : (ok4 ? 4 : 0);
   // small launches (a rank's share of the batch under strong scaling: tools/pairs_sweep.sh): when the 256-row tiles
@@ -587,27 +554,10 @@ static int bd_pick_ms(const iic_conv_geom* g) {
   return ok4 ? 4 : (ok2 ? 2 : 0);
 }
 
-static int bd_block_config(const iic_conv_geom* g, bd_blk* B, int wn);
-/* 1 if iic_conv_igemm_frag can run this geometry (else use iic_conv_igemm). */
-int iic_conv_igemm_frag_supported(const iic_conv_geom* g) {
-  if (!g) return 0;
-  if (g_p64_enabled && iic_p64_supported(g)) return 1;
-  if (g->Cin % 64 != 0 || g->ntaps < 1 || g->ntaps > IIC_MAX_TAPS) return 0;
-  // (images too wide for any row-major patch -- > ~290 pixels at dilation 2 -- still run here on block tiles)
-  bd_blk B;
-  if (g->Cout % BD_BN != 0) return (bd_w1_ok(g) || (g->Cout % 64 == 0 && bd_block_config(g, &B, 1))) ? 1 : 0;
-  return bd_pick_ms(g) != 0 || bd_block_config(g, &B, 2) != 0;
-}
-
-int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* wfrag, void* out,
-                            float* stats, const void* res_grad, const void* res_act, int accumulate,
-                            const void* red_y, const float* red_coef, const void* red_y2,
-                            float* red_stats, float* red_stats2, void* stream);
-
-/* 1 if iic_conv_igemm_frag_red can fuse a reduction into this geometry's launch. */
 // Block tiling of the 256-row tiles (see bd_blk): stride-1 multi-tap launches on images of at least 32 pixels whose
 // row-major 256-row patch is too big for two workgroups per CU, where the sub-image patch is not.  Block shape: fewest
 // tiles x (MFMA time + half the patch bytes), over shapes whose patch keeps two workgroups per CU.
+// (images too wide for any row-major patch -- > ~290 pixels at dilation 2 -- run on block tiles only)
 IIC_SWITCH(g_bd_blk, 1, iic_debug_bd_blk)       // 0: row-major tiles only; 2: block tiles wherever they apply (A/B)
 static int bd_block_config(const iic_conv_geom* g, bd_blk* B, int wn) {      // wn: the kernel's WN (tile couts / 64)
   B->bw = 0;
@@ -629,10 +579,8 @@ static int bd_block_config(const iic_conv_geom* g, bd_blk* B, int wn) {      // 
     if (bh < 2 || bh > g->MY) continue;
     const long tiles = (long)((g->MX + bw - 1) / bw) * ((g->MY + bh - 1) / bh);
     const long npix = (long)(bw + mix) * (bh + miy);
-    const long a = (npix * 128 + 1023) & ~1023L;
-    const long c = (long)BD_BM * (wn * 64 + 8) * 2;
-    const long tot = (a > c ? a : c) + 2L * BD_BM * 4 + 4L * BD_BN * 4 + ((npix + 15) & ~15L);
-    if (tot > 80 * 1024 || npix >= 65536 / (bw + mix)) continue;       // two workgroups per CU; multiply-shift division
+    // two workgroups per CU; multiply-shift division
+    if (bd_lds(npix, BD_BM, wn * 64, false, true) > IIC_LDS_WG2 || npix >= 65536 / (bw + mix)) continue;
     const double cost = (double)tiles * (1.0 + 0.5 * (double)npix * 128.0 / 32768.0);
     if (best < 0 || cost < best) { best = cost; best_bw = bw; best_tiles = tiles; }
   }
@@ -641,18 +589,69 @@ static int bd_block_config(const iic_conv_geom* g, bd_blk* B, int wn) {      // 
   if ((double)g->MY * g->MX < 0.88 * (double)BD_BM * (double)best_tiles) return 0;      // > 12 % idle rows
   const int npix = (bw + mix) * (bh + miy);
   // worth it where the row-major patch costs the second workgroup of a CU or is much larger
-  if (g_bd_blk != 2 && !(bd_lds_total(g, wn == 2 ? 4 : 2, wn) > 80 * 1024 || npix * 10 < g->NP256 * 7)) return 0;
+  if (g_bd_blk != 2 && !(bd_lds_rows(g, wn == 2 ? 4 : 2, wn) > IIC_LDS_WG2 || npix * 10 < g->NP256 * 7)) return 0;
   B->bw = bw; B->bh = bh;
   B->nbx = (g->MX + bw - 1) / bw; B->nby = (g->MY + bh - 1) / bh;
   B->PW = bw + mix; B->npix = npix; B->mul = (65536 + B->PW - 1) / B->PW;
   return 1;
 }
 
-int iic_conv_igemm_red_supported(const iic_conv_geom* g) {
-  if (!g || !iic_conv_igemm_frag_supported(g)) return 0;
-  if (g_p64_enabled && iic_p64_supported(g)) return g_p64_red;
-  return g->ntaps > 1;
+// The plan of a geometry (conv_plan.h) under the switches in force; false (kernel CONV_NONE): no weights-direct kernel
+// takes it.  In the order of preference: the 64 -> 64 persistent kernel; the stride-1 persistent kernel (no ablation,
+// no forced tile height); conv_igemm_bd_kernel with 64-cout tiles for an odd multiple of 64 couts, on block tiles where
+// they pay, at bd_pick_ms's tile height, with the padded patch under its budget rule, as a gather for one tap.
+static bool conv_make_plan(const iic_conv_geom* g, conv_plan* p) {
+  *p = conv_plan{};
+  if (!g) return false;
+  if (g_p64_enabled && iic_p64_plan(g, p)) {
+    // the persistent kernel stores tile t-1 right before tile t's MFMA loop: loads of y there stall every wave once
+    // per tile (measured +120 us per launch) -- callers keep the separate reduction pass for the 64 -> 64 layers
+    p->red_ok = g_p64_red != 0;
+    return true;
+  }
+  if (g->Cin % 64 != 0 || g->Cout % 64 != 0 || g->ntaps < 1 || g->ntaps > IIC_MAX_TAPS) return false;
+  const int abl = iic_debug_get_ablate();
+  if (abl == 0 && g_bd_ms == 0 && iic_pw_plan(g, p)) {
+    p->red_ok = true;
+    return true;
+  }
+  p->wn = g->Cout % BD_BN != 0 ? 1 : 2;
+  // (the ablation instantiations are row-major 128-cout tiles)
+  const bool blocked = (p->wn == 1 || abl == 0) && bd_block_config(g, &p->blk, p->wn) != 0;
+  if (p->wn == 1) p->ms = (blocked || bd_w1_ok(g)) ? 2 : 0;
+  else p->ms = blocked ? 4 : bd_pick_ms(g);
+  if (p->ms == 0) {
+    *p = conv_plan{};
+    return false;
+  }
+  const int rows = p->ms * 32 * (4 / p->wn);
+  p->gather = g->ntaps == 1;
+  p->red_ok = !p->gather;
+  p->pad = p->wn == 2 && !blocked && abl == 0 && bd_pad_ok(g, p->ms);
+  p->mtiles = blocked ? g->N * p->blk.nbx * p->blk.nby : (int)((igemm_rows_host(g) + rows - 1) / rows);
+  p->grid = p->mtiles * (g->Cout / (p->wn * 64));
+  p->lds = blocked ? bd_lds(p->blk.npix, BD_BM, p->wn * 64, false, true, &p->lds_a)
+                   : bd_lds_rows(g, p->ms, p->wn, p->pad, &p->lds_a);
+  p->kernel = CONV_BD;
+  return true;
 }
+
+/* 1 if iic_conv_igemm_frag can run this geometry (else use iic_conv_igemm). */
+int iic_conv_igemm_frag_supported(const iic_conv_geom* g) {
+  conv_plan p;
+  return conv_make_plan(g, &p) ? 1 : 0;
+}
+
+/* 1 if iic_conv_igemm_frag_red can fuse a reduction into this geometry's launch. */
+int iic_conv_igemm_red_supported(const iic_conv_geom* g) {
+  conv_plan p;
+  return conv_make_plan(g, &p) && p.red_ok ? 1 : 0;
+}
+
+int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* wfrag, void* out,
+                            float* stats, const void* res_grad, const void* res_act, int accumulate,
+                            const void* red_y, const float* red_coef, const void* red_y2,
+                            float* red_stats, float* red_stats2, void* stream);
 
 int iic_conv_igemm_frag(const iic_conv_geom* g, const void* in, const void* wfrag, void* out,
                         float* stats, const void* res_grad, const void* res_act, int accumulate,
@@ -671,85 +670,51 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
     return IIC_ERR_ARG;
   const int red = red_y ? (red_y2 ? 2 : 1) : 0;
   if (!(accumulate & IIC_ACC_PREMASK) && (res_grad == nullptr) != (res_act == nullptr)) return IIC_ERR_ARG;
-  if (!iic_conv_igemm_frag_supported(g)) return IIC_ERR_UNSUPPORTED;
-  if (g_p64_enabled && iic_p64_supported(g)) {
-    // the persistent kernel stores tile t-1 right before tile t's MFMA loop: loads of y there
-    // stall every wave once per tile (measured +120 us per launch) -- callers keep the separate
-    // reduction pass for the 64 -> 64 layers (iic_conv_igemm_red_supported)
-    if (red && !g_p64_red) return IIC_ERR_UNSUPPORTED;
-    return iic_p64_launch(g, in, wfrag, out, stats, res_grad, res_act, accumulate, red_y, red_coef, red_y2,
+  conv_plan p;
+  if (!conv_make_plan(g, &p)) return IIC_ERR_UNSUPPORTED;
+  if (p.kernel == CONV_P64) {
+    if (red && !p.red_ok) return IIC_ERR_UNSUPPORTED;
+    return iic_p64_launch(g, p, in, wfrag, out, stats, res_grad, res_act, accumulate, red_y, red_coef, red_y2,
                           red_stats, red_stats2, stream);
   }
-  if (iic_debug_get_ablate() == 0 && g_bd_ms == 0 && iic_pw_supported(g))
-    return iic_pw_launch(g, in, wfrag, out, stats, res_grad, res_act, accumulate, red_y, red_coef, red_y2, red_stats,
+  if (p.kernel == CONV_PW)
+    return iic_pw_launch(g, p, in, wfrag, out, stats, res_grad, res_act, accumulate, red_y, red_coef, red_y2, red_stats,
                          red_stats2, stream);
   const long M = igemm_rows_host(g);
   if (M <= 0) return IIC_ERR_ARG;
   if (M >= (1L << 31) || (long)g->N * g->in_Hp * g->in_Wp >= (1L << 31)) return IIC_ERR_UNSUPPORTED;
-  if (g->Cout % BD_BN != 0) {       // 64-cout tiles
-    bd_blk B1 = {0, 0, 0, 0, 0, 0, 0};
-    const bool blocked1 = bd_block_config(g, &B1, 1) != 0;
-    const int mt1 = blocked1 ? g->N * B1.nbx * B1.nby : (int)((M + 255) / 256);
-    const int grid1 = mt1 * (g->Cout / 64);
-    int la1 = (int)bd_lds_a(g, 2, 1);
-    long lds1 = bd_lds_total(g, 2, 1);
-    if (blocked1) {
-      const long a = ((long)B1.npix * 128 + 1023) & ~1023L, c = (long)BD_BM * (64 + 8) * 2;
-      la1 = (int)(((a > c ? a : c) + 15) & ~15L);
-      lds1 = la1 + 2L * BD_BM * 4 + 4L * BD_BN * 4 + ((B1.npix + 15) & ~15L);
-    }
-    hipStream_t s1 = (hipStream_t)stream;
-    int rc1 = IIC_OK;
-#define BD_LAUNCH_W1(RD_)                                                                              \
-  rc1 = iic_launch_lds<conv_igemm_bd_kernel<false, 0, 2, RD_, 1>>(                                     \
-      dim3(grid1), dim3(BD_THREADS), lds1, s1, *g, (const bf16_t*)in, (const unsigned char*)wfrag,     \
-      (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, mt1, la1,      \
-      (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2, red_stats, red_stats2,                    \
-      (unsigned long long*)nullptr, B1)
-    if (red == 0) BD_LAUNCH_W1(0); else if (red == 1) BD_LAUNCH_W1(1); else BD_LAUNCH_W1(2);
-    return rc1 ? rc1 : iic_launch_status();
-  }
-  bd_blk BB = {0, 0, 0, 0, 0, 0, 0};
-  const bool blocked = iic_debug_get_ablate() == 0 && bd_block_config(g, &BB, 2) != 0;
-  const int ms = blocked ? 4 : bd_pick_ms(g);
-  if (ms == 0) return IIC_ERR_UNSUPPORTED;      // (only block tiles fit and an ablation build / switch turned them off)
-  const int bm = ms * 64;
-  const int mt = blocked ? g->N * BB.nbx * BB.nby : (int)((M + bm - 1) / bm);
-  const int nt = g->Cout / BD_BN;
-  const int grid = mt * nt;
-  const bool pad = !blocked && iic_debug_get_ablate() == 0 && bd_pad_ok(g, ms);
-  int la = (int)bd_lds_a(g, ms, 2, pad);
-  long lds = bd_lds_total(g, ms, 2, pad);
-  if (blocked) {
-    const long a = ((long)BB.npix * 128 + 1023) & ~1023L, c = (long)BD_BM * (BD_BN + 8) * 2;
-    la = (int)(((a > c ? a : c) + 15) & ~15L);
-    lds = la + 2L * BD_BM * 4 + 4L * BD_BN * 4 + ((BB.npix + 15) & ~15L);
-  }
   hipStream_t s = (hipStream_t)stream;
   int rc = IIC_OK;
-#define BD_LAUNCH5(GA_, AB_, MS_, RD_, PD_)                                                       \
-  rc = iic_launch_lds<conv_igemm_bd_kernel<GA_, AB_, MS_, RD_, 2, PD_>>(                         \
-      dim3(grid), dim3(BD_THREADS), lds, s, *g, (const bf16_t*)in, (const unsigned char*)wfrag,  \
-      (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, mt, la,  \
-      (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_bd_prof, BB)
+#define BD_LAUNCH5(GA_, AB_, MS_, RD_, WN_, PD_)                                                          \
+  rc = iic_launch_lds<conv_igemm_bd_kernel<GA_, AB_, MS_, RD_, WN_, PD_>>(                               \
+      dim3(p.grid), dim3(BD_THREADS), p.lds, s, *g, (const bf16_t*)in, (const unsigned char*)wfrag,      \
+      (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, p.mtiles,        \
+      p.lds_a, (const bf16_t*)red_y, red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_bd_prof,  \
+      p.blk)
+  if (p.wn == 1) {       // 64-cout tiles
+    if (red == 0) BD_LAUNCH5(false, 0, 2, 0, 1, false);
+    else if (red == 1) BD_LAUNCH5(false, 0, 2, 1, 1, false);
+    else BD_LAUNCH5(false, 0, 2, 2, 1, false);
+    return rc ? rc : iic_launch_status();
+  }
 #define BD_LAUNCH4(GA_, AB_, MS_, RD_)                                                            \
   do {                                                                                           \
-    if (!GA_ && AB_ == 0 && pad) BD_LAUNCH5(false, 0, MS_, RD_, true);                           \
-    else BD_LAUNCH5(GA_, AB_, MS_, RD_, false);                                                  \
+    if (!GA_ && AB_ == 0 && p.pad) BD_LAUNCH5(false, 0, MS_, RD_, 2, true);                      \
+    else BD_LAUNCH5(GA_, AB_, MS_, RD_, 2, false);                                               \
   } while (0)
 #define BD_LAUNCH3(GA_, AB_, MS_)                                                                 \
   do {                                                                                           \
-    if ((AB_ != 0 && AB_ != 128 && AB_ != 256) || GA_ || red == 0) {                             \
+    if ((AB_ != 0 && AB_ != 128) || GA_ || red == 0) {                                           \
       if (red != 0) return IIC_ERR_UNSUPPORTED;                                                  \
       BD_LAUNCH4(GA_, AB_, MS_, 0);                                                              \
-    } else if (red == 1) BD_LAUNCH4(false, (AB_ == 128 || AB_ == 256 ? AB_ : 0), MS_, 1);        \
-    else BD_LAUNCH4(false, (AB_ == 128 || AB_ == 256 ? AB_ : 0), MS_, 2);                        \
+    } else if (red == 1) BD_LAUNCH4(false, (AB_ == 128 ? AB_ : 0), MS_, 1);                      \
+    else BD_LAUNCH4(false, (AB_ == 128 ? AB_ : 0), MS_, 2);                                      \
   } while (0)
 #define BD_LAUNCH(GA_, AB_)                                                                       \
   do {                                                                                           \
-    if (ms == 4) BD_LAUNCH3(GA_, AB_, 4); else BD_LAUNCH3(GA_, AB_, 2);                          \
+    if (p.ms == 4) BD_LAUNCH3(GA_, AB_, 4); else BD_LAUNCH3(GA_, AB_, 2);                        \
   } while (0)
-  if (g->ntaps == 1) BD_LAUNCH(true, 0);
+  if (p.gather) BD_LAUNCH(true, 0);
   else switch (iic_debug_get_ablate()) {
 #ifdef IIC_BD_ABLATIONS
     // timing-ablation and phase-stamp instantiations (tools/conv_perf.py --frag-ablate, tools/bd_timeline.py): NOT in the
@@ -766,7 +731,6 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
     case 64: BD_LAUNCH(false, 64); break;
     case 96: BD_LAUNCH(false, 96); break;
     case 128: BD_LAUNCH(false, 128); break;
-    case 256: BD_LAUNCH(false, 256); break;
 #endif
     default: BD_LAUNCH(false, 0); break;
   }
@@ -774,16 +738,22 @@ int iic_conv_igemm_frag_red(const iic_conv_geom* g, const void* in, const void* 
 }
 
 #ifdef IIC_DEBUG_HOOKS
-IIC_HOOK int iic_debug_pw_pitch144_used(const iic_conv_geom* g);
+// The plan of a geometry under the switches in force, as 12 ints: kernel (0 = none of the weights-direct kernels, 1 =
+// conv_igemm_p64_kernel, 2 = conv_igemm_pw_kernel, 3 = conv_igemm_bd_kernel), ms, wn, gather, pad, bw, bh, mtiles, grid,
+// lds_a, lds, red_ok (tests/test_conv_dispatch_cpu.py; host code only: needs no device)
+IIC_HOOK void iic_debug_conv_plan(const iic_conv_geom* g, int* out) {
+  conv_plan p;
+  conv_make_plan(g, &p);
+  const int f[12] = {p.kernel, p.ms, p.wn, p.gather, p.pad, p.blk.bw, p.blk.bh, p.mtiles, p.grid, p.lds_a, (int)p.lds,
+                     p.red_ok};
+  for (int i = 0; i < 12; ++i) out[i] = f[i];
+}
 // Which launch of iic_conv_igemm_frag_red reads a padded patch under the switches in force: 0 = none (swizzled rows,
 // block tiles, the 64 -> 64 kernel, 64-cout tiles), 1 = conv_igemm_bd_kernel, 2 = conv_igemm_pw_kernel (tests)
 IIC_HOOK int iic_debug_bd_pitch144_used(const iic_conv_geom* g) {
-  if (!g || !iic_conv_igemm_frag_supported(g) || (g_p64_enabled && iic_p64_supported(g))) return 0;
-  if (iic_debug_get_ablate() == 0 && g_bd_ms == 0 && iic_pw_supported(g)) return iic_debug_pw_pitch144_used(g) ? 2 : 0;
-  bd_blk B;
-  if (g->Cout % BD_BN != 0 || iic_debug_get_ablate() != 0 || bd_block_config(g, &B, 2)) return 0;
-  const int ms = bd_pick_ms(g);
-  return ms != 0 && bd_pad_ok(g, ms) ? 1 : 0;
+  conv_plan p;
+  if (!conv_make_plan(g, &p) || !p.pad) return 0;
+  return p.kernel == CONV_PW ? 2 : 1;
 }
 #endif
 

@@ -16,6 +16,7 @@
 //   * BatchNorm statistics are accumulated in registers across all tiles, one atomic pass at the
 //     end of the kernel.
 #include "common.h"
+#include "conv_plan.h"
 #include "conv_tile.h"
 #include "../../include/iic_hip.h"
 
@@ -342,20 +343,6 @@ static constexpr unsigned long long* g_p64_prof = nullptr;
 #endif
 IIC_SWITCH(g_p64_grid, 0, iic_debug_p64_grid)       // tests: force a small persistent grid (many tiles per workgroup)
 
-static int p64_num_cus() {
-  if (g_p64_grid > 0) return g_p64_grid;
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      n = v;
-    else
-      n = 256;
-  }
-  return n;
-}
-
 static long p64_pb_bytes(const iic_conv_geom* g, int bm = P64_BM) {
   return (((long)(bm == 128 ? g->NP : g->NP256) * 128) + 1023) & ~1023L;
 }
@@ -363,14 +350,23 @@ static long p64_pb_bytes(const iic_conv_geom* g, int bm = P64_BM) {
 // workgroup's serial phases (40 % of a tile's cycles with the matrix pipe idle) run under the other's K loop, but do not fit: at layer1 of ClusterNet5g a 128-row
 // tile still spans 340 patch rows (42.5 KB; 474 rows at 256), so two double-buffered workgroups need 208 KB.
 
-// used by conv_igemm_bd.hip's dispatcher
-int iic_p64_supported(const iic_conv_geom* g) {
-  if (g->Cin != 64 || g->Cout != 64 || g->ntaps != P64_NT || g->NP256 <= 0 || g->NP256 > 65535) return 0;
-  if (!igemm_dense_host(g)) return 0;       // the row walkers assume the dense row numbering
-  return 2 * p64_pb_bytes(g) + P64_SC_BYTES(P64_BM) + P64_TAB_BYTES(P64_BM) <= IIC_LDS_BYTES;
+// this kernel's part of conv_make_plan (conv_igemm_bd.hip)
+bool iic_p64_plan(const iic_conv_geom* g, conv_plan* p) {
+  if (g->Cin != 64 || g->Cout != 64 || g->ntaps != P64_NT || g->NP256 <= 0 || g->NP256 > 65535) return false;
+  if (!igemm_dense_host(g)) return false;       // the row walkers assume the dense row numbering
+  const long lds = 2 * p64_pb_bytes(g) + P64_SC_BYTES(P64_BM) + P64_TAB_BYTES(P64_BM);
+  if (lds > IIC_LDS_BYTES) return false;
+  const long nt = ((long)g->N * g->MY * g->MX + P64_BM - 1) / P64_BM;
+  const int ncu = g_p64_grid > 0 ? g_p64_grid : iic_num_cus();
+  p->kernel = CONV_P64;
+  p->mtiles = (int)nt;
+  p->grid = nt < ncu ? (int)nt : ncu;
+  p->lds_a = (int)p64_pb_bytes(g);
+  p->lds = lds;
+  return true;
 }
 
-int iic_p64_launch(const iic_conv_geom* g, const void* in, const void* wfrag, void* out, float* stats,
+int iic_p64_launch(const iic_conv_geom* g, const conv_plan& p, const void* in, const void* wfrag, void* out, float* stats,
                    const void* res_grad, const void* res_act, int accumulate, const void* red_y,
                    const float* red_coef, const void* red_y2, float* red_stats, float* red_stats2,
                    void* stream) {
@@ -378,20 +374,14 @@ int iic_p64_launch(const iic_conv_geom* g, const void* in, const void* wfrag, vo
   const long M = (long)g->N * g->MY * g->MX;
   if (M <= 0) return IIC_ERR_ARG;
   if (M >= (1L << 31) - P64_BM || (long)g->N * g->in_Hp * g->in_Wp >= (1L << 31)) return IIC_ERR_UNSUPPORTED;
-  const int bm = P64_BM;
-  const int nt = (int)((M + bm - 1) / bm);
-  const int pb = (int)p64_pb_bytes(g, bm);
-  const long lds = 2L * pb + P64_SC_BYTES(bm) + P64_TAB_BYTES(bm);
   int mto = 0;
   for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
-  const int ncu = p64_num_cus();
-  const int grid = nt < ncu ? nt : ncu;
   int rc = IIC_OK;
 #define P64_LAUNCH2(AB_, RD_)                                                                          \
   rc = iic_launch_lds<conv_igemm_p64_kernel<AB_, RD_>>(                                                \
-      dim3(grid), dim3(512), lds, (hipStream_t)stream, *g, (const bf16_t*)in,                          \
+      dim3(p.grid), dim3(512), p.lds, (hipStream_t)stream, *g, (const bf16_t*)in,                      \
       (const unsigned char*)wfrag, (bf16_t*)out, stats, (const bf16_t*)res_grad,                       \
-      (const bf16_t*)res_act, accumulate, nt, pb, mto, (const bf16_t*)red_y, red_coef,                 \
+      (const bf16_t*)res_act, accumulate, p.mtiles, p.lds_a, mto, (const bf16_t*)red_y, red_coef,      \
       (const bf16_t*)red_y2, red_stats, red_stats2, g_p64_prof)
 #define P64_LAUNCH(AB_) P64_LAUNCH2(AB_, 0)
   if (red == 1) P64_LAUNCH2(0, 1);

@@ -31,10 +31,11 @@
 // an A-fragment address is a per-tile lane base + the tap's scalar offset + an immediate per k-step -- one add per
 // (tap, sub-tile) where the swizzle costs a key, a shift and two XORs per read -- and the DMA needs no key table.
 // Same MFMA sequence, same operands: bit-identical results.  LDS: ceil(NP256 / 7) x 1008 B + 16 + staging => two
-// workgroups per CU up to NP256 = 434; the host keeps larger patches on the swizzled form (pw_pad_ok).
+// workgroups per CU up to NP256 = 434; the host keeps larger patches on the swizzled form (pw_plan).
 #include <type_traits>
 
 #include "common.h"
+#include "conv_plan.h"
 #include "conv_tile.h"
 #include "../../include/iic_hip.h"
 
@@ -44,27 +45,10 @@
 #define PW_KEYS 512                           // swizzle keys per buffer (>= NP256)
 #define PW_PROF_SLOTS 32      // 0..7 sums, 8..23 tile stamps, 24 / 25 s_memrealtime (100 MHz) at start / end
 
-struct pw_div {      // floor(n / d) for 0 <= n < 2^31:  (n * mul) >> sh  (64-bit product)
-  unsigned mul;
-  int sh;
-};
-static inline pw_div pw_make_div(int d) {
-  pw_div r;
-  int l = 0;
-  while ((1L << l) < d) ++l;
-  r.sh = 31 + l;
-  r.mul = (unsigned)(((1ULL << r.sh) + (unsigned long long)d - 1) / (unsigned long long)d);
-  if (d == 1) { r.mul = 1u << 31; r.sh = 31; }
-  return r;
-}
-__device__ __forceinline__ int pw_divide(int n, const pw_div& d) {
-  return (int)(((unsigned long long)(unsigned)n * d.mul) >> d.sh);
-}
-
 struct pw_args {
-  pw_div d_rows;       // by rows per image (g.MP or the plane)
-  pw_div d_mx;         // by g.MX
-  pw_div d_wp;         // by g.in_Wp
+  iic_mdiv d_rows;       // by rows per image (g.MP or the plane)
+  iic_mdiv d_mx;         // by g.MX
+  iic_mdiv d_wp;         // by g.in_Wp
   int rows_per_img;    // g.MP > 0 ? g.MP : plane
   int plane;           // g.MY * g.MX
   int jskip;           // dense-count skip per image row (0: key from the raw pixel index)
@@ -114,12 +98,12 @@ __device__ __forceinline__ void pw_dma16s(unsigned voff, const unsigned char* sb
 // igemm_row_pixels with multiply-shift divisions
 __device__ __forceinline__ void pw_row(const iic_conv_geom& g, const pw_args& A, int m, int& pin, int& prow,
                                        int& pout) {
-  int n = pw_divide(m, A.d_rows);
+  int n = iic_mdivide(m, A.d_rows);
   int r = m - n * A.rows_per_img;
   const bool valid = n < g.N && r < A.plane;
   if (n >= g.N) { n = g.N - 1; r = A.plane - 1; }
   r = r < A.plane ? r : A.plane - 1;
-  const int y = pw_divide(r, A.d_mx), x = r - y * g.MX;
+  const int y = iic_mdivide(r, A.d_mx), x = r - y * g.MX;
   prow = n * g.in_Hp + y * g.sy + g.oy;
   pin = prow * g.in_Wp + x * g.sx + g.ox;
   pout = valid ? (n * g.out_Hp + y * g.ty + g.py) * g.out_Wp + x * g.tx + g.px : -1;
@@ -269,7 +253,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
   // (PAD: tap offsets in bytes of the padded patch; no dense count)
   const int v_tapoff = g.tap_off[lane & (IIC_MAX_TAPS - 1)] * (PAD ? ROWB : 1);
   const int v_tapw = g.tap_w[lane & (IIC_MAX_TAPS - 1)];
-  const int v_tapd = PAD ? 0 : v_tapoff - A.jskip * pw_divide(v_tapoff, A.d_wp);
+  const int v_tapd = PAD ? 0 : v_tapoff - A.jskip * iic_mdivide(v_tapoff, A.d_wp);
   const int nchunks = g.Cin >> 6, ntaps = g.ntaps, NIT = nchunks * ntaps;
   const int nblk = A.patch_bytes >> 10;
   const long frag_it = (long)(g.Cout >> 5) * 4096;      // bytes per (tap, chunk)
@@ -289,7 +273,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
     if (PAD) return;
     for (int r = tid; r < PW_KEYS; r += PW_THREADS) {
       const int p = p_lo_t + r;
-      const int prow = pw_divide(p, A.d_wp);
+      const int prow = iic_mdivide(p, A.d_wp);
       const int D = p - A.jskip * prow;
       const int key = (D >> 1) & 7;
       s_key[kb * PW_KEYS + r] = (unsigned char)key;
@@ -509,7 +493,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
     // (g.MP, a multiple of 256: a tile never straddles two images) -- the rows past the image's plane
     int vlimit = A.M - m0;
     if (A.pad_rows) {
-      const int r0 = m0 - pw_divide(m0, A.d_rows) * A.rows_per_img;
+      const int r0 = m0 - iic_mdivide(m0, A.d_rows) * A.rows_per_img;
       vlimit = min(vlimit, A.plane - r0);
     }
     if (stats) {
@@ -641,7 +625,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void conv_igemm_pw_kernel(
       for (int j = 0; j < 4; ++j) q[8 + i * 4 + j] = t_line[i][j];
     q[24] = rt0;
     q[25] = __builtin_amdgcn_s_memrealtime();
-    q[7] = (unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) << 32);   // HW_ID, XCC_ID
+    q[7] = iic_hw_stamp();
   }
 }
 
@@ -651,109 +635,100 @@ IIC_SWITCH(g_pw_gx_cap, 0, iic_debug_pw_gx_cap)       // > 0: at most this many 
 static unsigned long long* g_pw_prof = nullptr;
 IIC_HOOK void iic_debug_pw_prof(void* buf) { g_pw_prof = (unsigned long long*)buf; }
 IIC_HOOK int iic_debug_pw_prof_slots(void) { return PW_PROF_SLOTS; }
-IIC_HOOK int iic_debug_pw_grid(const iic_conv_geom* g);
 #else
 static constexpr unsigned long long* g_pw_prof = nullptr;
 #endif
 
-static long pw_lds_bytes(const iic_conv_geom* g, bool pad = false) {
-  if (pad) return pt144_bytes(g->NP256) + 4 * PW_STG_BYTES;      // (no key table)
-  const long patch = ((long)g->NP256 * 128 + 1023) & ~1023L;
-  return patch + 4 * PW_STG_BYTES + 2 * PW_KEYS;
+// patch + staging (+ the two key buffers of the swizzled form); *patch = the patch bytes
+static long pw_lds_bytes(const iic_conv_geom* g, bool pad, int* patch = nullptr) {
+  const long a = pad ? pt144_bytes(g->NP256) : ((long)g->NP256 * 128 + 1023) & ~1023L;
+  if (patch) *patch = (int)a;
+  return a + 4 * PW_STG_BYTES + (pad ? 0 : 2 * PW_KEYS);
 }
-// the padded patch where it keeps two workgroups per CU (stride 1: the form's scope)
-static bool pw_pad_ok(const iic_conv_geom* g) {
-  return iic_debug_get_bd_pitch144() != 0 && g->sx == 1 && g->sy == 1 && pw_lds_bytes(g, true) <= 80 * 1024;
-}
-
-static int pw_num_cus();
-static int pw_supported_shape(const iic_conv_geom* g);
-int iic_pw_supported(const iic_conv_geom* g) {
-  if (!g || !g_pw_enabled || !pw_supported_shape(g)) return 0;
-  const long M = igemm_rows_host(g);
-  // take a launch only if it has at least 2.5 tiles per workgroup slot
-  if (g_pw_enabled != 2 && ((M + 255) / 256) * (g->Cout / 128) * 10 < 25L * 2 * pw_num_cus()) return 0;
-  return 1;
-}
-static int pw_supported_shape(const iic_conv_geom* g) {
-  if (!g) return 0;
-  if (g->ntaps < 2 || g->ntaps > IIC_MAX_TAPS || g->Cin % 64 != 0 || g->Cout % 128 != 0) return 0;
+static bool pw_supported_shape(const iic_conv_geom* g) {
+  if (!g) return false;
+  if (g->ntaps < 2 || g->ntaps > IIC_MAX_TAPS || g->Cin % 64 != 0 || g->Cout % 128 != 0) return false;
   const int nt = g->Cout / 128;
-  if (nt != 1 && nt != 2 && nt != 4 && nt != 8) return 0;
-  if (g->NP256 <= 0 || g->NP256 > PW_KEYS) return 0;
-  if (pw_lds_bytes(g) > 80 * 1024) return 0;      // two workgroups per CU (larger patches: conv_igemm_bd_kernel)
+  if (nt != 1 && nt != 2 && nt != 4 && nt != 8) return false;
+  if (g->NP256 <= 0 || g->NP256 > PW_KEYS) return false;
+  if (pw_lds_bytes(g, false) > IIC_LDS_WG2) return false;      // two workgroups per CU (larger patches: conv_igemm_bd_kernel)
   const long M = igemm_rows_host(g);
-  if (M <= 0 || M + 256 >= (1L << 31) || (long)g->N * g->in_Hp * g->in_Wp >= (1L << 31)) return 0;
-  return 1;
+  if (M <= 0 || M + 256 >= (1L << 31) || (long)g->N * g->in_Hp * g->in_Wp >= (1L << 31)) return false;
+  return true;
 }
-
-static int pw_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
-// workgroups of a launch: at most two per CU, a multiple of 8, and no more per XCD than its longest run of tiles
-static int pw_grid(const iic_conv_geom* g, long lds) {
-  const long M = igemm_rows_host(g);
-  const int mt = (int)((M + 255) / 256), nt = g->Cout / 128, per = 8 / nt;
+// workgroups of a launch of mt row tiles: two per CU (every supported shape fits twice), a multiple of 8, and no more
+// per XCD than its longest run of tiles
+static int pw_grid(const iic_conv_geom* g, int mt) {
+  const int per = 8 / (g->Cout / 128);
   int longest = 0;
   for (int xr = 0; xr < per; ++xr) {
     const int len = (int)((long)mt * (xr + 1) / per) - (int)((long)mt * xr / per);
     longest = len > longest ? len : longest;
   }
-  const int slots = (lds <= 80 * 1024 ? 2 : 1) * pw_num_cus();
-  int gx = slots / 8;
+  int gx = 2 * iic_num_cus() / 8;
   if (gx > longest) gx = longest;
   if (g_pw_gx_cap > 0 && gx > g_pw_gx_cap) gx = g_pw_gx_cap;
   if (gx < 1) gx = 1;
   return gx * 8;
 }
+// this kernel's part of conv_make_plan (conv_igemm_bd.hip); `all`: without the tiles-per-slot rule (iic_debug_pw_grid)
+static bool pw_plan(const iic_conv_geom* g, conv_plan* p, bool all) {
+  if (!pw_supported_shape(g)) return false;
+  const long mt = (igemm_rows_host(g) + 255) / 256;
+  // take a launch only if it has at least 2.5 tiles per workgroup slot
+  if (!all && mt * (g->Cout / 128) * 10 < 25L * 2 * iic_num_cus()) return false;
+  p->kernel = CONV_PW;
+  p->ms = 4;
+  p->wn = 2;
+  // the padded patch where it keeps two workgroups per CU (stride 1: the form's scope)
+  p->pad = iic_debug_get_bd_pitch144() != 0 && g->sx == 1 && g->sy == 1 && pw_lds_bytes(g, true) <= IIC_LDS_WG2;
+  p->lds = pw_lds_bytes(g, p->pad, &p->lds_a);
+  p->mtiles = (int)mt;
+  p->grid = pw_grid(g, p->mtiles);
+  return true;
+}
+bool iic_pw_plan(const iic_conv_geom* g, conv_plan* p) { return g_pw_enabled && pw_plan(g, p, g_pw_enabled == 2); }
 #ifdef IIC_DEBUG_HOOKS
-IIC_HOOK int iic_debug_pw_grid(const iic_conv_geom* g) { return g ? pw_grid(g, pw_lds_bytes(g)) : 0; }
+// workgroups this kernel would launch for the geometry; 0: not a shape it runs
+IIC_HOOK int iic_debug_pw_grid(const iic_conv_geom* g) {
+  conv_plan p;
+  return pw_plan(g, &p, true) ? p.grid : 0;
+}
 // 1 if this geometry's persistent launch takes the padded patch under the switches in force
-IIC_HOOK int iic_debug_pw_pitch144_used(const iic_conv_geom* g) { return g && iic_pw_supported(g) && pw_pad_ok(g) ? 1 : 0; }
+IIC_HOOK int iic_debug_pw_pitch144_used(const iic_conv_geom* g) {
+  conv_plan p;
+  return iic_pw_plan(g, &p) && p.pad ? 1 : 0;
+}
 #endif
 
-int iic_pw_launch(const iic_conv_geom* g, const void* in, const void* wfrag, void* out, float* stats,
+int iic_pw_launch(const iic_conv_geom* g, const conv_plan& p, const void* in, const void* wfrag, void* out, float* stats,
                   const void* res_grad, const void* res_act, int accumulate, const void* red_y,
                   const float* red_coef, const void* red_y2, float* red_stats, float* red_stats2, void* stream) {
-  if (!iic_pw_supported(g)) return IIC_ERR_UNSUPPORTED;
-  const long M = igemm_rows_host(g);
   pw_args A;
   A.plane = g->MY * g->MX;
   A.rows_per_img = g->MP > 0 ? g->MP : A.plane;
-  A.d_rows = pw_make_div(A.rows_per_img);
-  A.d_mx = pw_make_div(g->MX);
-  A.d_wp = pw_make_div(g->in_Wp);
+  A.d_rows = iic_make_mdiv(A.rows_per_img);
+  A.d_mx = iic_make_mdiv(g->MX);
+  A.d_wp = iic_make_mdiv(g->in_Wp);
   A.jskip = (g->sx == 1 && ((g->in_Wp - g->MX) & 1) == 0) ? g->in_Wp - g->MX : 0;
   A.npix = g->NP256;
-  A.patch_bytes = (int)(((long)g->NP256 * 128 + 1023) & ~1023L);
-  A.mt = (int)((M + 255) / 256);
-  A.M = (int)M;
+  A.patch_bytes = p.lds_a;
+  A.mt = p.mtiles;
+  A.M = (int)igemm_rows_host(g);
   A.in_pixels = g->N * g->in_Hp * g->in_Wp;
   A.pad_rows = (g->MP > 0 && g->MP != A.plane) ? 1 : 0;
-  const bool pad = pw_pad_ok(g);
   A.nj = (int)((g->NP256 + PT144_ROWS - 1) / PT144_ROWS);
-  if (pad) A.patch_bytes = (int)pt144_bytes(g->NP256);
-  const long lds = pw_lds_bytes(g, pad);
-  const int grid = pw_grid(g, lds);
   const int red = red_y ? (red_y2 ? 2 : 1) : 0;
   hipStream_t s = (hipStream_t)stream;
   int rc = IIC_OK;
 #define PW_LAUNCH2(RD_, PR_, PD_)                                                                             \
   rc = iic_launch_lds<conv_igemm_pw_kernel<RD_, PR_, PD_>>(                                                   \
-      dim3(grid), dim3(PW_THREADS), lds, s, *g, A, (const bf16_t*)in, (const unsigned char*)wfrag,            \
+      dim3(p.grid), dim3(PW_THREADS), p.lds, s, *g, A, (const bf16_t*)in, (const unsigned char*)wfrag,        \
       (bf16_t*)out, stats, (const bf16_t*)res_grad, (const bf16_t*)res_act, accumulate, (const bf16_t*)red_y, \
       red_coef, (const bf16_t*)red_y2, red_stats, red_stats2, g_pw_prof)
 #define PW_LAUNCH(RD_, PR_)                                                                                   \
   do {                                                                                                        \
-    if (pad) PW_LAUNCH2(RD_, PR_, true); else PW_LAUNCH2(RD_, PR_, false);                                    \
+    if (p.pad) PW_LAUNCH2(RD_, PR_, true); else PW_LAUNCH2(RD_, PR_, false);                                  \
   } while (0)
 #ifdef IIC_DEBUG_HOOKS
   if (g_pw_prof) {

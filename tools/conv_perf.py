@@ -84,7 +84,7 @@ def main():
     from iic_amd import _lib
     ctypes.CDLL(_lib.LIB_PATH).iic_debug_bd_pitch144(a.pitch144)
     print("pitch144", a.pitch144)
-  ABL_CODES = (1, 2, 3, 4, 7, 15, 16, 31, 32, 64, 96, 128, 256)      # conv_igemm_bd.hip: the instantiations of an ABL=1 build
+  ABL_CODES = (1, 2, 3, 4, 7, 15, 16, 31, 32, 64, 96, 128)     # conv_igemm_bd.hip: the instantiations of an ABL=1 build
   bad = [c for c in a.frag_ablate.split(",") if c and int(c) not in ABL_CODES]
   if bad:
     ap.error("--frag-ablate: no such ablation code: %s (have %s)" % (",".join(bad), ABL_CODES))
