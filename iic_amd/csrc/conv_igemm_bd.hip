@@ -25,8 +25,21 @@
 // B-fragment loads as inline asm: invisible to hipcc's vmcnt bookkeeping, so that the K loop can keep
 // exactly 8 of them in flight behind hand-counted waits while its LDS reads sit BETWEEN the MFMAs (a
 // compiler-visible load would be waited for conservatively at the loop header, see bd_bwait).
-__device__ __forceinline__ void bd_bload(u32x4& d, const unsigned char* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(d) : "v"(p) : "memory");
+// The address is a wave-uniform base (scalar registers) + the lane's 32-bit offset + an immediate: the fragments of a
+// (tap, chunk, cout sub-tile) are one scalar pointer, the k-step is the immediate -- no 64-bit vector add per load
+// (conv_igemm_pw.hip pw_bload).
+template <int OFF>
+__device__ __forceinline__ void bd_bload_at(u32x4& d, unsigned voff, const unsigned char* sbase) {
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
+}
+// k-step ks of the 4-KB fragment block at sbase (ks is a constant after unrolling)
+__device__ __forceinline__ void bd_bload(u32x4& d, unsigned voff, const unsigned char* sbase, int ks) {
+  switch (ks) {
+    case 0: bd_bload_at<0>(d, voff, sbase); break;
+    case 1: bd_bload_at<1024>(d, voff, sbase); break;
+    case 2: bd_bload_at<2048>(d, voff, sbase); break;
+    default: bd_bload_at<3072>(d, voff, sbase); break;
+  }
 }
 // wait until at most N vector-memory operations of this wave are outstanding; `d` (the fragment the
 // wait is for) becomes opaque here, so no consumer of it can be scheduled above the wait
@@ -229,7 +242,8 @@ __device__ __forceinline__ void bd_tile(
   const int NIT = nchunks * ntaps;
   // this wave's B fragments of iteration (tw, chunk): 2 x 4 KB contiguous
   const long frag_it = (long)(g.Cout >> 5) * 4096;      // bytes per (tap, chunk)
-  const unsigned char* wb0 = wfrag + (long)((n0 + wn * 64) >> 5) * 4096 + lane * 16;
+  const unsigned char* wb0 = wfrag + (long)((n0 + wn * 64) >> 5) * 4096;     // wave-uniform; the lane adds bvoff
+  const unsigned bvoff = (unsigned)lane * 16u;
   auto frag_ptr = [&](int tap, int chunk) {
     const int tw = __builtin_amdgcn_readlane(v_tapw, tap);
     return wb0 + ((long)tw * nchunks + chunk) * frag_it;
@@ -244,7 +258,7 @@ __device__ __forceinline__ void bd_tile(
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
       for (int ns = 0; ns < 2; ++ns)
-        bd_bload(Bc[ks][ns], p + ns * 4096 + ks * 1024);
+        bd_bload(Bc[ks][ns], bvoff, p + ns * 4096, ks);
   }
   dma_patch(0);
   __syncthreads();
@@ -327,14 +341,14 @@ __device__ __forceinline__ void bd_tile(
         __builtin_amdgcn_sched_barrier(0);
       }
       bd_bwait<6>(Bc[ks][1]);
-      bd_bload(Bc[ks][0], nb + ks * 1024);
+      bd_bload(Bc[ks][0], bvoff, nb, ks);
       __builtin_amdgcn_sched_barrier(0);
       const bf16x8 b1 = __builtin_bit_cast(bf16x8, Bc[ks][1]);
 #pragma unroll
       for (int ms = 0; ms < MS; ++ms)
         acc[ms][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][ms], b1, acc[ms][1], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      bd_bload(Bc[ks][1], nb + 4096 + ks * 1024);
+      bd_bload(Bc[ks][1], bvoff, nb + 4096, ks);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll

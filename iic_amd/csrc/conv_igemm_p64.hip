@@ -55,6 +55,44 @@ __device__ __forceinline__ void p64_walk_pixels(const P64Walk& w, const iic_conv
   pout = valid ? (n * g.out_Hp + y * g.ty + g.py) * g.out_Wp + x * g.tx + g.px : -1;
 }
 
+// FORM 1: one table row per thread, advanced by one tile with adds and selects only.  256 = d_n planes + d_y rows +
+// d_x pixels with d_y < MY, d_x < MX, so each of x and y carries at most once.  `pin` / `pout` are the unclamped
+// pixels of (n, y, x); rows with n >= N repeat the last row (pin) and are never stored (pout = -1).
+struct P64Row {
+  int n, y, x, pin, pout;
+};
+struct P64Step {
+  int d_n, d_y, d_x, MY, MX, pin_step, pin_xw, pin_yw, pout_step, pout_xw, pout_yw;
+};
+__device__ __forceinline__ void p64_row_init(P64Row& r, const iic_conv_geom& g, int m) {
+  P64Walk w;
+  p64_walk_init(w, g, m);
+  r.n = w.n; r.y = w.y; r.x = w.x;
+  r.pin = (w.n * g.in_Hp + w.y * g.sy + g.oy) * g.in_Wp + w.x * g.sx + g.ox;
+  r.pout = (w.n * g.out_Hp + w.y * g.ty + g.py) * g.out_Wp + w.x * g.tx + g.px;
+}
+__device__ __forceinline__ void p64_row_advance(P64Row& r, const P64Step& s) {
+  r.n += s.d_n; r.y += s.d_y; r.x += s.d_x; r.pin += s.pin_step; r.pout += s.pout_step;
+  const bool cx = r.x >= s.MX;
+  r.x -= cx ? s.MX : 0; r.y += cx ? 1 : 0; r.pin += cx ? s.pin_xw : 0; r.pout += cx ? s.pout_xw : 0;
+  const bool cy = r.y >= s.MY;
+  r.y -= cy ? s.MY : 0; r.n += cy ? 1 : 0; r.pin += cy ? s.pin_yw : 0; r.pout += cy ? s.pout_yw : 0;
+}
+
+// One LDS-DMA block of FORM 1: 64 lanes x 16 bytes from (wave-uniform base + 32-bit lane offset) to LDS byte lds_dst +
+// lane * 16 (conv_igemm_pw.hip pw_dma16s; M0 is compiler-reserved: saved and restored inside the statement).  Inline
+// asm because hipcc waits vmcnt(0) in front of every LDS read that follows a DMA it knows about: in the first form that
+// wait sits between the DMA issue and the tile's first read (the fetch of tile t + 1 is waited for in front of the K loop
+// of tile t, not at the top of t + 1), and with the DMA inside the K loop it would also wait for each spread store.
+__device__ __forceinline__ void p64_dma16s(unsigned voff, const unsigned char* sbase, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds_dst)
+      : "memory");
+}
+
 // ABL: timing-ablation build (WRONG results): 1 = only the first patch is fetched, 2 = no output
 // stores, 4 = one tap instead of nine.
 // RED: fused BatchNorm-backward reduction over the stored rows (conv_tile.h); the partial sums
@@ -65,10 +103,14 @@ __device__ __forceinline__ void p64_walk_pixels(const P64Walk& w, const iic_conv
 // sits in 288 registers of the wave, the A fragments of tap t+1 are read while the MFMAs of tap t run.  Measured
 // (round 3, tools/p64_phases.py, 660 x 49 x 49, forward): NW = 8 155-165 us, wide 186-199 us -- a single wave per
 // SIMD does not cover its own LDS latency (K loop 9.7 k cycles per tile against 5.9 k + 1.6 k of barrier wait).
-// Where a tile's 10.3 k cycles go at NW = 8 (matrix pipe alone: 4.6 k): K loop 5.9 k, barrier B 1.6 k, row tables +
-// DMA issue 1.4 k, accumulators -> LDS 1.0 k, waiting for the patch 0.3 k (the DMA is hidden); the residual
-// epilogue of backward-data adds 5.5 k (its 64 KB of residual-gradient / mask loads per tile are exposed).
-template <int ABL, int RED>
+// Where a tile's cycles go at NW = 8 (matrix pipe alone: 4.6 k; LAB.md S9, same tool and shape):
+//   FORM 0, 10.6 k: K loop 6.0 k, barrier B 1.6 k, row tables + DMA issue 1.5 k, accumulators -> LDS 1.0 k, waiting for
+//     the patch 0.3 k -- the K-loop figure hides a compiler-made vmcnt(0) between the DMA issue and the first LDS read;
+//   FORM 1,  9.3 k: K loop 6.5 k (DMA issue and row tables inside it), barrier B 0.6 k, accumulators -> LDS + the next
+//     tile's patch rows 1.3 k, waiting for the patch 0.5 k, spread-store bookkeeping 0.2 k;
+// the residual epilogue of backward-data adds 5.7-6.0 k in both (its 64 KB of residual-gradient / mask loads per tile
+// are exposed).
+template <int ABL, int RED, bool FORM>
 __global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
     const iic_conv_geom g, const bf16_t* __restrict__ in, const unsigned char* __restrict__ wfrag,
     bf16_t* __restrict__ out, float* __restrict__ stats, const bf16_t* __restrict__ res_grad,
@@ -80,6 +122,10 @@ __global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
   // the tile loop into prof[blockIdx][8]: wait for patch + barrier A | store of tile t-1 | DMA issue + row
   // tables | K loop | barrier B | accumulators -> LDS; [6] = tiles, [7] = whole loop (tools/p64_phases.py)
   constexpr bool PROF = (ABL & 8) != 0;
+  // FORM 1 = closed-form patch addresses (every build) + the bookkeeping taken off the tile's serial path (BK).  With
+  // the fused reduction's sums resident there is no register room for BK -- its scalar walkers and the work moved
+  // into the K loop spill (RED 2: 72 B of scratch against 8) -- so those builds keep the first form's bookkeeping.
+  constexpr bool BK = FORM && RED == 0;
   constexpr int NW = 8, BM = P64_BM;
   constexpr int NWM = BM / 64;                  // 64-row groups of the tile
   constexpr int SC_BYTES = BM * P64_CLD * 2, TAB_ROWS = P64_NTAB * BM;
@@ -100,6 +146,10 @@ __global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, g5 = lane >> 5;
+  const uint32_t g5x = (uint32_t)g5 << 4;
+  typedef const bf16x8 __attribute__((address_space(3))) * lds_frag_ptr;
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane(
+      (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem_raw);
   const int M = g.N * g.MY * g.MX;
   const int in_pixels = g.N * g.in_Hp * g.in_Wp;
 
@@ -156,11 +206,86 @@ __global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
     }
   };
 
+  // ---- FORM 1 (BK): the same tables, queue and DMA with the bookkeeping off the tile's serial path -----------------
+  //   * waves 0-3 walk one table row per thread (P64Row: adds and selects); the tile's first / last row walk in
+  //     scalar registers (every input is workgroup-uniform), so waves 4-7 spend no VALU on tables at all.  (The
+  //     table holds pin - p0, so p0 has to be known before the row is written: it cannot be read back from it.)
+  //   * a 1-KB DMA block is 8 whole patch rows and a wave's blocks are 8 apart, so the lane's source offset
+  //     (row lane >> 3, logical slot) is the same for every block: scalar base + one hoisted lane offset, the
+  //     per-lane clamp only in the block that reaches the tensor's last pixel.
+  P64Step stp;
+  P64Row rr, r0, r255;
+  int pin_last = 0;
+  uint32_t lane_src = 0;
+  if (BK) {
+    const int plane = g.MY * g.MX;
+    stp.d_n = BM / plane;
+    const int rem = BM - stp.d_n * plane;
+    stp.d_y = rem / g.MX;
+    stp.d_x = rem - stp.d_y * g.MX;
+    stp.MY = g.MY; stp.MX = g.MX;
+    stp.pin_step = (stp.d_n * g.in_Hp + stp.d_y * g.sy) * g.in_Wp + stp.d_x * g.sx;
+    stp.pin_xw = g.sy * g.in_Wp - g.MX * g.sx;
+    stp.pin_yw = (g.in_Hp - g.MY * g.sy) * g.in_Wp;
+    stp.pout_step = (stp.d_n * g.out_Hp + stp.d_y * g.ty) * g.out_Wp + stp.d_x * g.tx;
+    stp.pout_xw = g.ty * g.out_Wp - g.MX * g.tx;
+    stp.pout_yw = (g.out_Hp - g.MY * g.ty) * g.out_Wp;
+    pin_last = ((g.N - 1) * g.in_Hp + (g.MY - 1) * g.sy + g.oy) * g.in_Wp + (g.MX - 1) * g.sx + g.ox;
+    p64_row_init(rr, g, t0 * BM + (tid & (BM - 1)));
+    p64_row_init(r0, g, t0 * BM);
+    p64_row_init(r255, g, t0 * BM + BM - 1);
+    lane_src = (uint32_t)(lane >> 3) * 128u + (uint32_t)(((lane & 7) ^ (lane >> 4) ^ ((wave & 1) << 2)) << 4);
+  }
+  auto tabulate1 = [&](int t) {
+    const int p0 = r0.n < g.N ? r0.pin : pin_last;
+    const int p255 = r255.n < g.N ? r255.pin : pin_last;
+    if (wave < BM / 64) {
+      const bool valid = rr.n < g.N;
+      s_pout[(t & (P64_NTAB - 1)) * BM + tid] = valid ? rr.pout : -1;
+      s_prow[(t & (P64_NTAB - 1)) * BM + tid] = (unsigned short)((valid ? rr.pin : pin_last) - p0);
+      p64_row_advance(rr, stp);
+    }
+    p64_row_advance(r0, stp);
+    p64_row_advance(r255, stp);
+    plo_q[0] = plo_q[1];
+    nblk_q[0] = nblk_q[1];
+    plo_q[1] = plo_q[2];
+    nblk_q[1] = nblk_q[2];
+    plo_q[2] = p0;
+    nblk_q[2] = ((p255 + max_tap_off - p0 + 1) * 128 + 1023) >> 10;
+  };
+  auto dma_issue1 = [&](uint32_t dst, int plo, int nblk) {      // dst: LDS byte address of the patch buffer
+    const unsigned char* const ing = reinterpret_cast<const unsigned char*>(in);
+    for (int blk = wave; blk < nblk; blk += NW) {         // 1-KB blocks = 8 patch rows, wave-uniform
+      const int rb = plo + blk * 8;
+      const unsigned char* src = ing + (long)rb * 128;
+      uint32_t vo = lane_src;
+      if (rb + 7 >= in_pixels) {                          // (uniform) rows past the tensor repeat its last pixel
+        const int rc = rb < in_pixels ? rb : in_pixels - 1;
+        int p = rb + (lane >> 3);
+        p = p < in_pixels ? p : in_pixels - 1;
+        src = ing + (long)rc * 128;
+        vo = (uint32_t)(p - rc) * 128u + (lane_src & 127u);
+      }
+      p64_dma16s(vo, src, dst + (uint32_t)blk * 1024u);
+    }
+  };
+  int R0[2];                     // BK: patch rows of this lane's two 32-row groups, read one tile ahead
+
   // ---- prologue: tables of the first two tiles, first patch in flight, resident weights -------
-  tabulate(t0);
-  tabulate(t0 + 1);
-  // queue now: [1] = tile t0, [2] = tile t0 + 1
-  dma_issue(sP0, plo_q[1], nblk_q[1]);
+  if (BK) {
+    tabulate1(t0);
+    tabulate1(t0 + 1);
+    __syncthreads();
+#pragma unroll
+    for (int ms = 0; ms < 2; ++ms) R0[ms] = s_prow[(t0 & (P64_NTAB - 1)) * BM + wm * 64 + ms * 32 + l31];
+    dma_issue1(lds_base, plo_q[1], nblk_q[1]);
+  } else {
+    tabulate(t0);
+    tabulate(t0 + 1);
+    // queue now: [1] = tile t0, [2] = tile t0 + 1
+    dma_issue(sP0, plo_q[1], nblk_q[1]);
+  }
   u32x4 Bw[P64_NT][NCO][4];
 #pragma unroll
   for (int tap = 0; tap < P64_NT; ++tap)
@@ -179,6 +304,14 @@ __global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
   TileRed tr;
   if (RED) tile_red_zero(tr);
 
+  // BK: what iteration t touches besides its own patch and sC, and why that is safe (A, B = the two barriers below;
+  // every wave waits lgkmcnt(0) in front of B, so all LDS reads and table writes of an iteration are done at its B):
+  //   * table slot (t + 2) & 3 is WRITTEN under tap 6, after A of t.  Its last readers: the patch rows of tile t - 2
+  //     (read after B of t - 3) and s_pout of tile t - 2, read by the stores of iteration t - 1 -- done before B of t - 1.
+  //   * the patch rows of tile t + 1 are READ after B of t; they were written under tap 6 of t - 1, before B of t - 1
+  //     (tile t0 + 1: in the prologue, in front of its barrier).
+  //   * patch buffer (t + 1) & 1 is WRITTEN by the DMA issued behind tap 0's reads, after A of t; its last readers are
+  //     the K loop of t - 1, done before B of t - 1.  The queue is rotated after the issue, as in the first form.
   if (PROF) t_loop = __builtin_readcyclecounter();
   for (int t = t0; t < t1; ++t) {
     const int par = (t - t0) & 1;
@@ -198,18 +331,42 @@ __global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
                                                             red_y, red_coef, red_y2, &tr);
     if (PROF) { t_b = __builtin_readcyclecounter(); ph[1] += t_b - t_a; t_a = t_b; }
     // queue: [2] = tile t + 1 (tabulated one iteration ago)
-    if (t + 1 < t1 && !(ABL & 1)) dma_issue(par ? sP0 : sP1, plo_q[2], nblk_q[2]);
-    tabulate(t + 2);
+    if (!BK) {
+      if (t + 1 < t1 && !(ABL & 1)) dma_issue(par ? sP0 : sP1, plo_q[2], nblk_q[2]);
+      tabulate(t + 2);
+    }
     if (PROF) { t_b = __builtin_readcyclecounter(); ph[2] += t_b - t_a; t_a = t_b; }
     // ---- tile t: 9 taps x 4 k-steps x (2 A reads, 2 MFMAs) --------------------------------
-    int R0[2];
+    if (!BK) {
 #pragma unroll
-    for (int ms = 0; ms < 2; ++ms)
-      R0[ms] = s_prow[(t & (P64_NTAB - 1)) * BM + wm * 64 + ms * 32 + l31];
+      for (int ms = 0; ms < 2; ++ms)
+        R0[ms] = s_prow[(t & (P64_NTAB - 1)) * BM + wm * 64 + ms * 32 + l31];
+    }
+    // FORM 1: the buffer's LDS address joins the tap offset on the scalar side.  A buffer starts k KB = 8 k rows into
+    // LDS (this kernel has no static LDS: smem_raw is 1-KB aligned, and pb_bytes is whole KB), which moves the row's
+    // swizzle key (R >> 1) & 7 by 4 k: the k-step terms undo that.
+    const uint32_t pbase = lds_base + (par ? (uint32_t)pb_bytes : 0u);
+    const int prow = (int)(pbase >> 7);
+    const uint32_t kfix = (pbase >> 4) & 0x40u;
     f32x16 acc[2][NCO];
     constexpr int NTAPS = (ABL & 4) ? 1 : P64_NT;
     auto load_a = [&](int tap, bf16x8 (&a)[2][4]) {
       const int toff = __builtin_amdgcn_readlane(v_tapoff, tap);
+      if (FORM) {
+        // byte ((R << 7) | ((R << 3) & 0x70)) ^ (g5 << 4) ^ (ks << 5): slot ((ks << 1) | g5) ^ key, key << 4 = (R << 3) & 0x70
+        const int toffp = toff + prow;
+#pragma unroll
+        for (int ms = 0; ms < 2; ++ms) {
+          uint32_t tt = (uint32_t)(R0[ms] + toffp) << 3;
+          asm volatile("" : "+v"(tt));                   // (keeps the compiler from splitting the sum again)
+          uint32_t u = (tt << 4) | (tt & 0x70u);
+          asm volatile("" : "+v"(u));
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks)
+            a[ms][ks] = *reinterpret_cast<const lds_frag_ptr>((uintptr_t)(u ^ g5x ^ ((uint32_t)(ks << 5) ^ kfix)));
+        }
+        return;
+      }
 #pragma unroll
       for (int ms = 0; ms < 2; ++ms) {
         const int R = R0[ms] + toff;
@@ -225,6 +382,11 @@ __global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
     for (int tap = 0; tap < NTAPS; ++tap) {
       bf16x8 a[2][4];
       load_a(tap, a);
+      if (BK) {
+        // behind the first tap's reads: the DMA of tile t + 1 (queue [2]); under a late tap's MFMAs: table t + 2
+        if (tap == 0 && t + 1 < t1 && !(ABL & 1)) dma_issue1(lds_base + (par ? 0u : (uint32_t)pb_bytes), plo_q[2], nblk_q[2]);
+        if (tap == (NTAPS > 6 ? 6 : NTAPS - 1)) tabulate1(t + 2);
+      }
       if (spread && t > t0 && !(ABL & 2)) {
         constexpr int SIT = BM * 8 / NTH;           // 16-byte pieces per thread and tile (4 | 8)
         constexpr int PER = (SIT + P64_NT - 2) / (P64_NT - 1);
@@ -289,6 +451,10 @@ __global__ __launch_bounds__(512) void conv_igemm_p64_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           sC[(wm * 64 + ms * 32 + mfma32_row(r, lane)) * P64_CLD + (wn + c) * 32 + l31] = f32_to_bf16(acc[ms][c][r]);
+    if (BK && t + 1 < t1) {
+#pragma unroll
+      for (int ms = 0; ms < 2; ++ms) R0[ms] = s_prow[((t + 1) & (P64_NTAB - 1)) * BM + wm * 64 + ms * 32 + l31];
+    }
     if (PROF) { t_b = __builtin_readcyclecounter(); ph[5] += t_b - t_a; }
   }
   if (PROF && prof && tid == 0) {
@@ -342,6 +508,9 @@ IIC_HOOK void iic_debug_p64_prof(void* buf) { g_p64_prof = (unsigned long long*)
 static constexpr unsigned long long* g_p64_prof = nullptr;
 #endif
 IIC_SWITCH(g_p64_grid, 0, iic_debug_p64_grid)       // tests: force a small persistent grid (many tiles per workgroup)
+// 1: closed-form patch addresses, bookkeeping off the tile's serial path (template FORM); 0: the first form of the
+// tile loop, instantiated in the instrumented library only (A/B, tests/test_gpu_p64_forms.py)
+IIC_SWITCH(g_p64_form, 1, iic_debug_p64_form)
 
 static long p64_pb_bytes(const iic_conv_geom* g, int bm = P64_BM) {
   return (((long)(bm == 128 ? g->NP : g->NP256) * 128) + 1023) & ~1023L;
@@ -377,12 +546,21 @@ int iic_p64_launch(const iic_conv_geom* g, const conv_plan& p, const void* in, c
   int mto = 0;
   for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
   int rc = IIC_OK;
-#define P64_LAUNCH2(AB_, RD_)                                                                          \
-  rc = iic_launch_lds<conv_igemm_p64_kernel<AB_, RD_>>(                                                \
+#define P64_LAUNCH3(AB_, RD_, FM_)                                                                     \
+  rc = iic_launch_lds<conv_igemm_p64_kernel<AB_, RD_, FM_>>(                                           \
       dim3(p.grid), dim3(512), p.lds, (hipStream_t)stream, *g, (const bf16_t*)in,                      \
       (const unsigned char*)wfrag, (bf16_t*)out, stats, (const bf16_t*)res_grad,                       \
       (const bf16_t*)res_act, accumulate, p.mtiles, p.lds_a, mto, (const bf16_t*)red_y, red_coef,      \
       (const bf16_t*)red_y2, red_stats, red_stats2, g_p64_prof)
+#ifdef IIC_DEBUG_HOOKS
+#define P64_LAUNCH2(AB_, RD_)                                                                          \
+  do {                                                                                                 \
+    if (g_p64_form) P64_LAUNCH3(AB_, RD_, true);                                                       \
+    else P64_LAUNCH3(AB_, RD_, false);                                                                 \
+  } while (0)
+#else
+#define P64_LAUNCH2(AB_, RD_) P64_LAUNCH3(AB_, RD_, true)
+#endif
 #define P64_LAUNCH(AB_) P64_LAUNCH2(AB_, 0)
   if (red == 1) P64_LAUNCH2(0, 1);
   else if (red == 2) P64_LAUNCH2(0, 2);

@@ -57,6 +57,41 @@ def timeit_cold(fn, iters):
   return tot * 1e3 / iters
 
 
+def p64_form_ab(N, iters, rounds=5):
+  """Layer 1 on the persistent 64 -> 64 kernel, its two tile-loop forms (iic_debug_p64_form) alternating in one process:
+  per launch kind the median and the min..max of `rounds` timings per form, caches hot and cold."""
+  import ctypes
+  import statistics
+  from iic_amd import _lib
+  L = ctypes.CDLL(_lib.LIB_PATH)
+  dev = torch.device("cuda:0")
+  H, C = 49, 64
+  spec = geom.ConvSpec(C, C, 3, 1, 1)
+  gf = geom.fwd_geom(spec, N, H, H, 1, 1)
+  gb = geom.bwd_data_geoms(spec, N, H, H, 1, 1)
+  x = torch.randn(N, H + 2, H + 2, C, device=dev).to(torch.bfloat16)
+  dy = torch.randn_like(x)
+  rg = torch.randn_like(x)
+  y = torch.zeros_like(x)
+  pw = ops.PreppedWeights(torch.randn(C, C, 3, 3, device=dev) * 0.05)
+  st = ops.new_stats(C, dev)
+  kinds = [("fwd + stats", lambda: ops.conv_igemm(gf, x, pw[0], y, stats=st)),
+           ("bwd-data plain", lambda: [ops.conv_igemm(g, dy, pw[1], y) for g in gb]),
+           ("bwd-data + residual, premask", lambda: [ops.conv_igemm(g, dy, pw[1], y, res_grad=rg, res_act=x, premask=True) for g in gb])]
+  print("p64 forms, %d x %d x %d, %d rounds x %d launches: us per launch, median (min..max)" % (N, H, H, rounds, iters))
+  for name, fn in kinds:
+    for label, timer in (("hot", timeit), ("cold", timeit_cold)):
+      t = {0: [], 1: []}
+      for r in range(rounds):
+        for form in ((0, 1) if r % 2 == 0 else (1, 0)):
+          L.iic_debug_p64_form(form)
+          t[form].append(timer(fn, iters))
+      L.iic_debug_p64_form(1)
+      print("  %-30s %-4s | form 0 %7.1f (%7.1f..%7.1f) | form 1 %7.1f (%7.1f..%7.1f) | %+6.1f us" % (
+        name, label, statistics.median(t[0]), min(t[0]), max(t[0]), statistics.median(t[1]), min(t[1]), max(t[1]),
+        statistics.median(t[1]) - statistics.median(t[0])))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--n", type=int, default=660)
@@ -70,6 +105,9 @@ def main():
   ap.add_argument("--cold", action="store_true", help="also time every kernel with cold caches (a 1-GB fill in front of each launch)")
   ap.add_argument("--pitch144", type=int, default=-1, help="patch form of the weights-direct kernels: 1 = rows at a 144-byte pitch "
                   "where the geometry allows, 0 = swizzled 128-byte rows (default: the library's)")
+  ap.add_argument("--p64-form", type=str, default="", choices=["", "0", "1", "ab"], help="tile-loop form of the persistent 64->64 kernel: "
+                  "1 = closed-form addresses, bookkeeping off the serial path, 0 = the first form (default: the library's); "
+                  "ab = time layer 1 alone with the two forms alternating, then exit")
   ap.add_argument("--no-pw", action="store_true", help="persistent kernel off: every launch on conv_igemm_bd_kernel (the ablation codes' baseline)")
   a = ap.parse_args()
   dev = torch.device("cuda:0")
@@ -79,6 +117,14 @@ def main():
     from iic_amd import _lib
     ctypes.CDLL(_lib.LIB_PATH).iic_debug_enable_pw(0)
     print("persistent kernel off")
+  if a.p64_form == "ab":
+    p64_form_ab(N, a.iters)
+    return
+  if a.p64_form:
+    import ctypes
+    from iic_amd import _lib
+    ctypes.CDLL(_lib.LIB_PATH).iic_debug_p64_form(int(a.p64_form))
+    print("p64 form", a.p64_form)
   if a.pitch144 >= 0:
     import ctypes
     from iic_amd import _lib

@@ -3,7 +3,7 @@ Where a tile's cycles go in the persistent 64 -> 64 convolution (conv_igemm_p64_
 ClusterNet5g): the kernel's PROF build (iic_debug_set_ablate(8), results unchanged) sums, per workgroup, the
 s_memtime cycles of each phase of its tile loop.
 
-python tools/p64_phases.py [--n 660] [--bwd]
+python tools/p64_phases.py [--n 660] [--bwd] [--form 0|1]
 """
 import argparse
 import ctypes
@@ -17,6 +17,8 @@ import torch
 
 from iic_amd import _lib, geom, ops
 
+# (form 1 issues the DMA and writes the row tables inside the K loop: its third phase is empty, and the last one
+# includes the read of the next tile's patch rows)
 PH = ["wait patch + barrier A", "store of tile t-1", "DMA issue + row tables", "K loop (9 taps x 4 k-steps)",
       "barrier B", "accumulators -> LDS (+stats)"]
 
@@ -25,8 +27,12 @@ def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--n", type=int, default=660)
   ap.add_argument("--bwd", action="store_true", help="backward-data with the residual gradient + ReLU mask epilogue")
+  ap.add_argument("--form", type=int, default=-1, help="tile-loop form (iic_debug_p64_form); default: the library's")
   args = ap.parse_args()
   L = _lib.lib()
+  if args.form >= 0:
+    ctypes.CDLL(_lib.LIB_PATH).iic_debug_p64_form(args.form)
+    print("p64 form", args.form)
   for name in ("iic_debug_p64_prof", "iic_debug_set_ablate"):
     getattr(L, name).restype = None
   L.iic_debug_p64_prof.argtypes = [ctypes.c_void_p]
