@@ -185,6 +185,15 @@ def _bn_training(bn):
   return bn.training or not bn.track_running_stats
 
 
+def _frozen_runs_eagerly(ctx):
+  """A forward that will be differentiated through a BatchNorm on running statistics (eval(), a frozen layer) is not
+  captured into a HIP graph: iic_amd.graphed leaves such a module to eager launches (graphed.eligible), and a capture
+  by iic_amd.graph (CapturedStep / CapturedPairStep), which only sees closures, stops here."""
+  if any(ctx.needs_input_grad) and torch.cuda.is_current_stream_capturing():
+    raise RuntimeError("HIP BatchNorm backward on running statistics (eval() / frozen BatchNorm) is not captured into "
+                       "a graph: run this step eagerly")
+
+
 # ------------------------------------------------------------------------------------
 # Stem
 # ------------------------------------------------------------------------------------
@@ -201,6 +210,8 @@ class _StemFn(torch.autograd.Function):
     bn = mod.bn1
     rm, rv, nbt = _bn_buffers(bn)
     training = _bn_training(bn)
+    if not training:
+      _frozen_runs_eagerly(ctx)
     wd = w.detach()
     if training:
       st = mod._h_conv1.stats(x.device)
@@ -222,19 +233,23 @@ class _StemFn(torch.autograd.Function):
   @ops.branch_backward
   def backward(ctx, dpool):
     x, w, gamma, coef, out = ctx.saved_tensors
-    if not ctx.training:
-      raise RuntimeError("HIP BatchNorm backward is implemented for batch statistics only")
     N, C, H, W = x.shape
     dpool = dpool.contiguous()
     sums = ctx.mod._h_conv1.stats(x.device, "bwd")
+
+    def finalize():
+      if ctx.training:
+        return ops.bn_bwd_finalize(sums, gamma.detach(), coef, 64, N * H * W)
+      # running statistics: bcoef = (scale, 0, 0), the weight-gradient kernels below then see dy = scale * g
+      return ops.bn_bwd_finalize_frozen(sums, coef, 64, want_bcoef=True)
     if STEM_FUSED_BWD[0] and ops.stem_bwd_fused_ok(C):
       # one recompute pass: BN-backward sums + coefficient-free dW GEMMs, coefficients applied after
       h = ops.stem_bwd_fused(x, w.detach(), coef, dpool, sums)
-      bcoef, dgamma, dbeta = ops.bn_bwd_finalize(sums, gamma.detach(), coef, 64, N * H * W)
+      bcoef, dgamma, dbeta = finalize()
       dW = ops.stem_wgrad_combine(h, bcoef, w.detach())
     else:
       ops.stem_bwd_reduce(x, w.detach(), coef, dpool, sums)
-      bcoef, dgamma, dbeta = ops.bn_bwd_finalize(sums, gamma.detach(), coef, 64, N * H * W)
+      bcoef, dgamma, dbeta = finalize()
       dW = ops.stem_bwd_wgrad(x, w.detach(), coef, bcoef, dpool)
     ops.POOL.release(dpool)
     ops.POOL.release(out)
@@ -253,6 +268,8 @@ class _StemF32Fn(torch.autograd.Function):
     bn, h = mod.bn1, mod._h_conv1
     rm, rv, nbt = _bn_buffers(bn)
     training = _bn_training(bn)
+    if not training:
+      _frozen_runs_eagerly(ctx)
     dev = x.device
     xp = ops.f32_nchw_to_pt(x, ops.pt_alloc(N, H, W, C, 1, dev), 1)
     gf, _ = h.geoms(N, H, W)
@@ -275,17 +292,14 @@ class _StemF32Fn(torch.autograd.Function):
   @ops.branch_backward
   def backward(ctx, dpool):
     xp, y, a, coef, gamma = ctx.saved_tensors
-    if not ctx.training:
-      raise RuntimeError("HIP BatchNorm backward is implemented for batch statistics only")
     N, C, H, W = ctx.dims
     dev, h = xp.device, ctx.mod._h_conv1
     with ops.fp32_mode():
       da = ops.f32_maxpool_s2p1_bwd(a, dpool.contiguous(), ops.pt_alloc(N, H, W, 64, 1, dev), N, H, W, 64)
       sums = h.stats(dev, "bwd")
-      ops.bn_bwd_reduce(da, None, y, sums, N, H, W, 1, 64, mask_coef=coef)
-      bcoef, dgamma, dbeta = ops.bn_bwd_finalize(sums, gamma.detach(), coef, 64, N * H * W)
       dy = ops.pt_alloc(N, H, W, 64, 1, dev)
-      ops.bn_bwd_apply(da, None, y, bcoef, dy, N, H, W, 1, 64, mask_coef=coef)
+      dgamma, dbeta = ops.bn_bwd(ctx.training, da, None, y, coef, gamma.detach(), dy, sums, N, H, W, 1, 64,
+                                 mask_coef=coef)
       gf, _ = h.geoms(N, H, W)
       dW = ops.conv_wgrad(gf, xp, dy, 9).view(64, C, 3, 3)
     for t in (dpool, da, dy, xp, y, a):
@@ -348,7 +362,14 @@ class _BlockFn(torch.autograd.Function):
       ctx.blk = blk
       ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
       ctx.dims = (N, H, W, Ho, Wo, Cin, planes)
-      ctx.bn_batch = (_bn_training(blk.bn1) and _bn_training(blk.bn2))
+      # per BatchNorm: batch statistics (True) or running statistics (False: eval(), a frozen layer)
+      ctx.bn_modes = (_bn_training(blk.bn1), _bn_training(blk.bn2),
+                      _bn_training(blk.downsample[1]) if hd is not None else True)
+      # the fused reductions below are for batch statistics only: the one-pass backward of a BatchNorm on running
+      # statistics takes its own sums, a second producer would count them twice
+      ctx.bn_batch = all(ctx.bn_modes)
+      if not ctx.bn_batch:
+        _frozen_runs_eagerly(ctx)
       # (set by the trunk for the duration of its sequential forward, see PREMASK)
       ctx.dout_premasked, ctx.mask_dx = blk._dout_premasked, blk._mask_dx
       # fused reduction of the PREVIOUS block's bn2 in this block's conv1 backward-data
@@ -377,8 +398,7 @@ class _BlockFn(torch.autograd.Function):
   def backward(ctx, dout):
     x, y1, a1, y2, out, yd, coef1, coef2, coefd, g1, g2, gd = ctx.saved_tensors
     blk = ctx.blk
-    if not ctx.bn_batch:
-      raise RuntimeError("HIP BatchNorm backward is implemented for batch statistics only")
+    batch1, batch2, batchd = ctx.bn_modes
     N, H, W, Ho, Wo, Cin, planes = ctx.dims
     dev = x.device
     h1, h2, hd = blk._h1, blk._h2, blk._hd
@@ -394,15 +414,27 @@ class _BlockFn(torch.autograd.Function):
     m_out = None if pre else out
     s2 = h2.stats(dev, "bwd")
     sd = hd.stats(dev, "bwd") if hd is not None else None
-    if not ctx.dout_prereduced:      # else: the next block's conv1 backward-data took these sums
-      ops.bn_bwd_reduce(dout, m_out, y2, s2, N, Ho, Wo, 1, planes, y2=yd, sums2=sd)
-    bc2, dg2, db2 = ops.bn_bwd_finalize(s2, g2.detach(), coef2, planes, cnt)
-    dy2 = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
     bcd = dgd = dbd = dyd = None
-    if hd is not None:
-      bcd, dgd, dbd = ops.bn_bwd_finalize(sd, gd.detach(), coefd, planes, cnt)
-      dyd = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
-    ops.bn_bwd_apply(dout, m_out, y2, bc2, dy2, N, Ho, Wo, 1, planes, y2=yd, bcoef2=bcd, dy2=dyd)
+    if batch2 and batchd:
+      if not ctx.dout_prereduced:      # else: the next block's conv1 backward-data took these sums
+        ops.bn_bwd_reduce(dout, m_out, y2, s2, N, Ho, Wo, 1, planes, y2=yd, sums2=sd)
+      bc2, dg2, db2 = ops.bn_bwd_finalize(s2, g2.detach(), coef2, planes, cnt)
+      dy2 = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
+      if hd is not None:
+        bcd, dgd, dbd = ops.bn_bwd_finalize(sd, gd.detach(), coefd, planes, cnt)
+        dyd = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
+      ops.bn_bwd_apply(dout, m_out, y2, bc2, dy2, N, Ho, Wo, 1, planes, y2=yd, bcoef2=bcd, dy2=dyd)
+    else:
+      assert not ctx.dout_prereduced
+      dy2 = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
+      dyd = ops.pt_alloc(N, Ho, Wo, planes, 1, dev) if hd is not None else None
+      if hd is None or not (batch2 or batchd):
+        # running statistics (both, when there is a downsample BatchNorm: they share g, one launch serves both)
+        dg2, db2, dgd, dbd = ops.bn_bwd_frozen(dout, m_out, y2, coef2, dy2, s2, N, Ho, Wo, 1, planes, y2=yd,
+                                               coef2=coefd, dy2=dyd, sums2=sd)
+      else:                            # one of the two on batch statistics: each is served on its own
+        dg2, db2 = ops.bn_bwd(batch2, dout, m_out, y2, coef2, g2.detach(), dy2, s2, N, Ho, Wo, 1, planes)
+        dgd, dbd = ops.bn_bwd(batchd, dout, m_out, yd, coefd, gd.detach(), dyd, sd, N, Ho, Wo, 1, planes)
 
     # ---- conv2 backward: weight grad, data grad + bn1 backward
     dW2 = ops.conv_wgrad(gf2, a1, dy2, 9, use_tr).view(planes, planes, 3, 3)
@@ -416,16 +448,17 @@ class _BlockFn(torch.autograd.Function):
     # a1 = relu(bn1(y1)) exactly: the ReLU mask comes from (y1, coef1), a1 is not read
     m_act, m_coef = (None, coef1) if BN_MASK_FROM_Y[0] else (a1, None)
     w2b = h2.weights()[1]
-    if FUSE_RED[0] and m_coef is not None and len(gb2) == 1 and ops.red_supported(gb2[0], w2b):
+    if batch1 and FUSE_RED[0] and m_coef is not None and len(gb2) == 1 and ops.red_supported(gb2[0], w2b):
       # the conv2 backward-data launch takes bn1's sums in its epilogue (reads y1 beside da1)
       ops.conv_igemm(gb2[0], dy2, w2b, da1, red=(y1, coef1, s1, None, None))
+      reduced = True
     else:
       for g in gb2:
         ops.conv_igemm(g, dy2, w2b, da1)
-      ops.bn_bwd_reduce(da1, m_act, y1, s1, N, Ho, Wo, 1, planes, mask_coef=m_coef)
-    bc1, dg1, db1 = ops.bn_bwd_finalize(s1, g1.detach(), coef1, planes, cnt)
+      reduced = False
     dy1 = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
-    ops.bn_bwd_apply(da1, m_act, y1, bc1, dy1, N, Ho, Wo, 1, planes, mask_coef=m_coef)
+    dg1, db1 = ops.bn_bwd(batch1, da1, m_act, y1, coef1, g1.detach(), dy1, s1, N, Ho, Wo, 1, planes, mask_coef=m_coef,
+                          reduced=reduced)
 
     # ---- conv1 backward: weight grad, data grad (+ residual / downsample gradient)
     dW1 = ops.conv_wgrad(gf1, x, dy1, 9, use_tr).view(planes, Cin, 3, 3)

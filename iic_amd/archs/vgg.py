@@ -16,7 +16,8 @@ import torch.nn as nn
 from .. import geom as G
 from .. import ops
 from ..dist import shard_batch
-from .cluster import FUSE_RED, _ApplyCounter, _ConvHolder, _HeadsFn, _bn_buffers, _bn_training
+from .cluster import (FUSE_RED, _ApplyCounter, _ConvHolder, _HeadsFn, _bn_buffers, _bn_training,
+                      _frozen_runs_eagerly)
 
 import os
 
@@ -37,6 +38,8 @@ class _StageFn(torch.autograd.Function):
     dev = x.device
     bn = st.bn
     training = _bn_training(bn)
+    if not training:
+      _frozen_runs_eagerly(ctx)
     rm, rv, nbt = _bn_buffers(bn)
     C = st.cout
     if st.first:
@@ -109,12 +112,9 @@ class _StageFn(torch.autograd.Function):
   def backward(ctx, dout):
     x, w, gamma, y, a, coef, pooled = ctx.saved_tensors
     st = ctx.st
-    if not ctx.training:
-      raise RuntimeError("HIP BatchNorm backward is implemented for batch statistics only")
     N, H, W, Ho, Wo = ctx.dims
     P, C, dev = st.P, st.cout, y.device
     dout = dout.contiguous()
-    cnt = N * Ho * Wo
     if st.pool:
       da = ops.pt_alloc(N, Ho, Wo, C, P, dev)
       if a is None:          # fused pool: the arg-max is taken on the activation recomputed from (y, coef)
@@ -127,11 +127,11 @@ class _StageFn(torch.autograd.Function):
       da = dout
     sums = st.holder.stats(dev, "bwd")
     # a = relu(bn(y)) exactly: the ReLU mask is recomputed from (y, coef), a is not read here
-    if not ctx.dout_prereduced:      # else: the next stage's backward-data conv took these sums
-      ops.bn_bwd_reduce(da, None, y, sums, N, Ho, Wo, P, C, mask_coef=coef)
-    bcoef, dgamma, dbeta = ops.bn_bwd_finalize(sums, gamma.detach(), coef, C, cnt)
+    # (ctx.dout_prereduced: the next stage's backward-data conv took these sums -- batch statistics only, a stage on
+    # running statistics never offers itself through its _Link; there the one-pass backward writes dy and takes the sums)
     dy = ops.pt_alloc(N, Ho, Wo, C, P, dev)
-    ops.bn_bwd_apply(da, None, y, bcoef, dy, N, Ho, Wo, P, C, mask_coef=coef)
+    dgamma, dbeta = ops.bn_bwd(ctx.training, da, None, y, coef, gamma.detach(), dy, sums, N, Ho, Wo, P, C,
+                               mask_coef=coef, reduced=ctx.dout_prereduced)
     dx = None
     if st.first and x.dim() == 4 and x.dtype == torch.float32 and dy.dtype == torch.float32:
       gf, _ = st.holder.geoms(N, H, W)         # fp32 parity path: x is the PT copy of the image

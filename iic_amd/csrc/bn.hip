@@ -508,6 +508,138 @@ __global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(
          HAS2 ? ld16<NTL>(y2 + wa.off) : z);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Backward of a BatchNorm that normalised with its RUNNING statistics (eval(), or a frozen layer of a
+// fine-tuning run).  mean and invstd are constants there, so dy = scale * g needs no batch sum and the
+// reduce / apply pair above collapses into one pass: g and y are read once (3 tensor streams, 5 before),
+// dy is written, and sum g, sum g*y go to the same exact accumulators for dgamma / dbeta.  Layout of
+// bn_bwd_reduce2_kernel (its grid as well: the pass ends with the same 2C / 3C atomics per block).
+template <int MASK, bool HAS2, bool NTL>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(
+    const bf16_t* __restrict__ dout, const bf16_t* __restrict__ act, const bf16_t* __restrict__ y,
+    const float* __restrict__ coef, bf16_t* __restrict__ dy, const bf16_t* __restrict__ y2,
+    const float* __restrict__ coef2, bf16_t* __restrict__ dy2, float* __restrict__ sums,
+    float* __restrict__ sums2, const float* __restrict__ mcoef, long npx, long per, int H, int W, int P,
+    int C) {
+  __shared__ float s_acc[256 * 8];
+  const int c8n = C >> 3;
+  const int PL = 256 / c8n;
+  const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
+  float sg[8], sgy[8], sgy2[HAS2 ? 8 : 1], k1[8], j1[HAS2 ? 8 : 1], msc[MASK == 2 ? 8 : 1], msh[MASK == 2 ? 8 : 1];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    sg[i] = sgy[i] = 0.f;
+    k1[i] = coef[c8 * 8 + i];
+    if (HAS2) {
+      sgy2[HAS2 ? i : 0] = 0.f;
+      j1[HAS2 ? i : 0] = coef2[c8 * 8 + i];
+    }
+    if (MASK == 2) {
+      msc[MASK == 2 ? i : 0] = mcoef[c8 * 8 + i];
+      msh[MASK == 2 ? i : 0] = mcoef[C + c8 * 8 + i];
+    }
+  }
+  const long q0 = (long)blockIdx.x * per;
+  const long q1 = q0 + per < npx ? q0 + per : npx;
+  auto emit = [&](long off, const uint4 rg, const uint4 ra, const uint4 ry, const uint4 ry2) {
+    float g[8], v[8], o[8];
+    unpack8(rg, g);
+    unpack8(ry, v);
+    if (MASK == 1) {
+      float a[8];
+      unpack8(ra, a);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) g[i] = a[i] > 0.f ? g[i] : 0.f;
+    } else if (MASK == 2) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        g[i] = (v[i] * msc[MASK == 2 ? i : 0] + msh[MASK == 2 ? i : 0]) > 0.f ? g[i] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      o[i] = k1[i] * g[i];
+      sg[i] += g[i];
+      sgy[i] += g[i] * v[i];
+    }
+    *reinterpret_cast<uint4*>(dy + off) = pack8(o);
+    if (HAS2) {
+      unpack8(ry2, v);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        o[i] = j1[HAS2 ? i : 0] * g[i];
+        sgy2[HAS2 ? i : 0] += g[i] * v[i];
+      }
+      *reinterpret_cast<uint4*>(dy2 + off) = pack8(o);
+    }
+  };
+  if (q0 + pl < q1) {
+    PxWalk wa = px_start(q0 + pl, H, W, P, C, c8);
+    long q = q0 + pl;
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (; q + PL < q1; q += 2 * PL) {          // two pixels per iteration
+      PxWalk wb = wa;
+      px_advance(wb, PL, H, W, P, C);
+      const uint4 g0 = ld16<NTL>(dout + wa.off);
+      const uint4 g1 = ld16<NTL>(dout + wb.off);
+      const uint4 y0 = ld16<NTL>(y + wa.off);
+      const uint4 y1 = ld16<NTL>(y + wb.off);
+      const uint4 a0 = MASK == 1 ? ld16<NTL>(act + wa.off) : z;
+      const uint4 a1 = MASK == 1 ? ld16<NTL>(act + wb.off) : z;
+      const uint4 t0 = HAS2 ? ld16<NTL>(y2 + wa.off) : z;
+      const uint4 t1 = HAS2 ? ld16<NTL>(y2 + wb.off) : z;
+      emit(wa.off, g0, a0, y0, t0);
+      emit(wb.off, g1, a1, y1, t1);
+      wa = wb;
+      px_advance(wa, PL, H, W, P, C);
+    }
+    if (q < q1)
+      emit(wa.off, ld16<NTL>(dout + wa.off),
+           MASK == 1 ? ld16<NTL>(act + wa.off) : z,
+           ld16<NTL>(y + wa.off),
+           HAS2 ? ld16<NTL>(y2 + wa.off) : z);
+  }
+  const int stripe = blockIdx.x % IIC_STAT_STRIPES;
+  for (int which = 0; which < (HAS2 ? 3 : 2); ++which) {
+    const float* src = which == 0 ? sg : (which == 1 || !HAS2 ? sgy : sgy2);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s_acc[(pl * c8n + c8) * 8 + i] = src[i];
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+      float t = 0.f;
+      for (int p = 0; p < PL; ++p) t += s_acc[(p * c8n + (c >> 3)) * 8 + (c & 7)];
+      if (which == 0) {
+        iic_stat_add(sums, stripe, C, c, 0, t);
+        if (HAS2) iic_stat_add(sums2, stripe, C, c, 0, t);
+      } else if (which == 1) {
+        iic_stat_add(sums, stripe, C, c, 1, t);
+      } else {
+        iic_stat_add(sums2, stripe, C, c, 1, t);
+      }
+    }
+  }
+}
+
+// dgamma = (sum g*y - running_mean * sum g) * invstd, dbeta = sum g; bcoef (nullable) = (scale, 0, 0): the
+// three-coefficient form dy = c1*g + c2*y + c3 of the consumers that keep it (stem, fp32 parity kernels)
+__global__ __launch_bounds__(256) void bn_bwd_finalize_frozen_kernel(
+    float* __restrict__ sums, const float* __restrict__ coef, float* __restrict__ bcoef,
+    float* __restrict__ dgamma, float* __restrict__ dbeta, int C) {
+  const int lane16 = threadIdx.x & 15;
+  const int c = blockIdx.x * 16 + (threadIdx.x >> 4);
+  double s, sy;
+  iic_stat_collect(sums, IIC_STAT_STRIPES, C, c < C ? c : C - 1, lane16, s, sy);
+  if (c >= C || lane16 != 0) return;
+  const double mean = coef[2 * C + c], invstd = coef[3 * C + c];
+  if (bcoef) {
+    bcoef[c] = coef[c];
+    bcoef[C + c] = 0.f;
+    bcoef[2 * C + c] = 0.f;
+  }
+  if (dgamma) dgamma[c] = (float)((sy - mean * s) * invstd);
+  if (dbeta) dbeta[c] = (float)s;
+}
+
 // 0: first-generation backward kernels; 1 (default): second generation where it measured faster
 // (tools/bn_perf.py: every reduce, and the apply unless it reads the activation tensor for its mask
 // -- with 3 reads + 1 write per element the deeper prefetch costs occupancy: 161 vs 158 us at
@@ -686,6 +818,45 @@ int iic_bn_bwd_apply(const void* dout, const void* act, const void* y, const flo
   hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)dout, (const bf16_t*)act, (const bf16_t*)y, bcoef, (bf16_t*)dy,
                      (const bf16_t*)y2, bcoef2, (bf16_t*)dy2, mask_coef, H, W, P, C);
+  return iic_launch_status();
+}
+
+int iic_bn_bwd_frozen(const void* dout, const void* act, const void* y, const float* coef, void* dy,
+                      const void* y2, const float* coef2, void* dy2, float* sums, float* sums2,
+                      const float* mask_coef, int N, int H, int W, int P, int C, void* stream) {
+  if (!dout || !y || !coef || !dy || !sums || N <= 0 || H <= 0 || W <= 0 || P < 0 || (act && mask_coef))
+    return IIC_ERR_ARG;
+  if ((y2 == nullptr) != (coef2 == nullptr) || (y2 == nullptr) != (dy2 == nullptr) ||
+      (y2 == nullptr) != (sums2 == nullptr))
+    return IIC_ERR_ARG;
+  if (check_c(C)) return IIC_ERR_UNSUPPORTED;
+  const int mode = act ? 1 : (mask_coef ? 2 : 0);
+  long per;
+  int grid2;
+  bn_v2_grid((long)N * H * W, C, per, grid2, 1);
+#define BN_FRZ_LAUNCH_(M_, H2_, L_)                                                              \
+  hipLaunchKernelGGL((bn_bwd_frozen_kernel<M_, H2_, L_>), dim3(grid2), dim3(256), 0,            \
+                     (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act,              \
+                     (const bf16_t*)y, coef, (bf16_t*)dy, (const bf16_t*)y2, coef2,             \
+                     (bf16_t*)dy2, sums, sums2, mask_coef, (long)N * H * W, per, H, W, P, C)
+#define BN_FRZ_LAUNCH(M_, H2_)                                   \
+  do {                                                           \
+    if (g_bn_nt) BN_FRZ_LAUNCH_(M_, H2_, true);                  \
+    else BN_FRZ_LAUNCH_(M_, H2_, false);                         \
+  } while (0)
+  if (y2) {
+    if (mode == 1) BN_FRZ_LAUNCH(1, true); else if (mode == 2) BN_FRZ_LAUNCH(2, true); else BN_FRZ_LAUNCH(0, true);
+  } else {
+    if (mode == 1) BN_FRZ_LAUNCH(1, false); else if (mode == 2) BN_FRZ_LAUNCH(2, false); else BN_FRZ_LAUNCH(0, false);
+  }
+  return iic_launch_status();
+}
+
+int iic_bn_bwd_finalize_frozen(float* sums, const float* coef, float* bcoef, float* dgamma, float* dbeta,
+                               int C, void* stream) {
+  if (!sums || !coef || C <= 0 || (C & 15)) return IIC_ERR_ARG;
+  hipLaunchKernelGGL(bn_bwd_finalize_frozen_kernel, dim3((C + 15) / 16), dim3(256), 0,
+                     (hipStream_t)stream, sums, coef, bcoef, dgamma, dbeta, C);
   return iic_launch_status();
 }
 

@@ -254,12 +254,29 @@ def _state(mod):
   return st
 
 
+def _any_frozen_bn(mod):
+  """Is a BatchNorm of a module in train() mode itself in eval() (the fine-tuning recipe: net.train(), then .eval() on
+  every BatchNorm2d)?  Its backward takes the running-statistics path, which is not captured.  The BatchNorm modules
+  are listed once per module (and again every _SIG_FULL_EVERY-th call, as the storage signature is); a forward only
+  reads their `training` flags -- no walk of the module tree."""
+  st = _state(mod)
+  n = st["bn_calls"] = st.get("bn_calls", 0) + 1
+  bns = st.get("bns")
+  if bns is None or n % _SIG_FULL_EVERY == 0:
+    bns = st["bns"] = [m for m in mod.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+  for m in bns:
+    if not m.training and m.track_running_stats:
+      return True
+  return False
+
+
 def eligible(mod, x, args, kwargs):
   bc = context()
   return (ops.GRAPH_FORWARD[0] and mod.training and torch.is_grad_enabled() and torch.is_tensor(x) and x.is_cuda
           and not x.requires_grad and not args and set(kwargs) <= {"head"}
           and (bc.branch == 0 or bc.branch in bc.no_proxy_branches)    # (parameters, not leaf aliases)
-          and ops.PT_DTYPE[0] is ops.BF16 and not torch.cuda.is_current_stream_capturing())
+          and ops.PT_DTYPE[0] is ops.BF16 and not torch.cuda.is_current_stream_capturing()
+          and not _any_frozen_bn(mod))
 
 
 def _epoch(mod):

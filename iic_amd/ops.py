@@ -323,6 +323,55 @@ def bn_bwd_apply(dout, act, y, bcoef, dy, N, H, W, P, C, y2=None, bcoef2=None, d
         "iic_bn_bwd_apply")
 
 
+def bn_bwd_finalize_frozen(sums, coef, C, want_bcoef=False):
+  """Finaliser of a BatchNorm that normalised with its running statistics: dgamma = (sum g*y - running_mean * sum g)
+  * invstd, dbeta = sum g, from `sums` (re-zeroed) and the forward coef.  want_bcoef: also (scale, 0, 0), the
+  three-coefficient form of the consumers that keep it (stem_wgrad_combine, stem_bwd_wgrad, the fp32 bn_bwd_apply)."""
+  bcoef = torch.empty((3, C), dtype=F32, device=coef.device) if want_bcoef else None
+  dgamma = torch.empty(C, dtype=F32, device=coef.device)
+  dbeta = torch.empty(C, dtype=F32, device=coef.device)
+  check(lib().iic_bn_bwd_finalize_frozen(ptr(sums), ptr(coef), ptr(bcoef), ptr(dgamma), ptr(dbeta), C, stream_ptr()),
+        "iic_bn_bwd_finalize_frozen")
+  return bcoef, dgamma, dbeta
+
+
+def bn_bwd_frozen(dout, act, y, coef, dy, sums, N, H, W, P, C, y2=None, coef2=None, dy2=None, sums2=None,
+                  mask_coef=None):
+  """Whole backward of a BatchNorm on running statistics (eval(), a frozen layer): writes dy = scale * g (dy2 for a
+  second BatchNorm sharing g) and returns (dgamma, dbeta, dgamma2, dbeta2).  bf16: one streaming pass
+  (iic_bn_bwd_frozen) + the finaliser.  F32 (fp32_mode, the parity instrument): the existing fp32 kernels, reduce ->
+  finaliser with bcoef = (scale, 0, 0) -> apply."""
+  dg2 = db2 = None
+  if y.dtype == F32:
+    bn_bwd_reduce(dout, act, y, sums, N, H, W, P, C, y2=y2, sums2=sums2, mask_coef=mask_coef)
+    bc, dg, db = bn_bwd_finalize_frozen(sums, coef, C, want_bcoef=True)
+    bc2 = None
+    if y2 is not None:
+      bc2, dg2, db2 = bn_bwd_finalize_frozen(sums2, coef2, C, want_bcoef=True)
+    bn_bwd_apply(dout, act, y, bc, dy, N, H, W, P, C, y2=y2, bcoef2=bc2, dy2=dy2, mask_coef=mask_coef)
+    return dg, db, dg2, db2
+  check(lib().iic_bn_bwd_frozen(ptr(dout), ptr(act), ptr(y), ptr(coef), ptr(dy), ptr(y2), ptr(coef2), ptr(dy2),
+                                ptr(sums), ptr(sums2), ptr(mask_coef), N, H, W, P, C, stream_ptr()),
+        "iic_bn_bwd_frozen")
+  _, dg, db = bn_bwd_finalize_frozen(sums, coef, C)
+  if y2 is not None:
+    _, dg2, db2 = bn_bwd_finalize_frozen(sums2, coef2, C)
+  return dg, db, dg2, db2
+
+
+def bn_bwd(batch, dout, act, y, coef, gamma, dy, sums, N, H, W, P, C, mask_coef=None, reduced=False):
+  """Backward of ONE BatchNorm in the mode its forward ran in: batch statistics (reduce -> finalise -> apply; reduced:
+  a convolution's epilogue took the sums already) or running statistics (bn_bwd_frozen).  Returns (dgamma, dbeta)."""
+  if not batch:
+    assert not reduced, "a BatchNorm on running statistics never takes part in a fused reduction"
+    return bn_bwd_frozen(dout, act, y, coef, dy, sums, N, H, W, P, C, mask_coef=mask_coef)[:2]
+  if not reduced:
+    bn_bwd_reduce(dout, act, y, sums, N, H, W, P, C, mask_coef=mask_coef)
+  bcoef, dgamma, dbeta = bn_bwd_finalize(sums, gamma, coef, C, N * H * W)
+  bn_bwd_apply(dout, act, y, bcoef, dy, N, H, W, P, C, mask_coef=mask_coef)
+  return dgamma, dbeta
+
+
 # ------------------------------------------------------------------------------------
 # stem + sobel
 # ------------------------------------------------------------------------------------

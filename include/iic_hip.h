@@ -246,6 +246,22 @@ int iic_bn_bwd_finalize(float* sums, const float* gamma, const float* coef, floa
 int iic_bn_bwd_apply(const void* dout, const void* act, const void* y, const float* bcoef,
                      void* dy, const void* y2, const float* bcoef2, void* dy2,
                      const float* mask_coef, int N, int H, int W, int P, int C, void* stream);
+/* Backward of a BatchNorm that normalised with its running statistics (eval(), or a frozen layer of a
+ * fine-tuning run: what torch.nn.functional.batch_norm(training=False) differentiates to; residual.py:20,23,56-57,
+ * vgg.py:28-30 under net.eval()).  One pass over the PT interiors: dy = bf16(scale * g) with scale = coef row 0
+ * (iic_bn_finalize(training=0)) and g as in iic_bn_bwd_reduce (act / mask_coef: the same three mask modes), and
+ * sums += sum g, sum g*y into the accumulators of iic_bn_bwd_reduce.  Second BatchNorm sharing g (downsample
+ * branch): y2, coef2, dy2, sums2 -- all four or none.  C: 64, 128, 256, 512, 1024, 2048 (IIC_ERR_UNSUPPORTED
+ * otherwise, nothing launched).  The border of dy / dy2 is not written.                                        */
+int iic_bn_bwd_frozen(const void* dout, const void* act, const void* y, const float* coef, void* dy,
+                      const void* y2, const float* coef2, void* dy2, float* sums, float* sums2,
+                      const float* mask_coef, int N, int H, int W, int P, int C, void* stream);
+/* from sums and the forward coef -> dgamma = (sum g*y - running_mean * sum g) * invstd, dbeta = sum g (in
+ * double; both nullable).  bcoef (nullable) receives (scale, 0, 0): dy = c1*g + c2*y + c3 of iic_bn_bwd_apply,
+ * iic_stem_wgrad_combine and iic_stem_bwd_wgrad is then the frozen gradient.  Re-zeroes sums.  The running
+ * statistics and num_batches_tracked are not touched.                                                        */
+int iic_bn_bwd_finalize_frozen(float* sums, const float* coef, float* bcoef, float* dgamma, float* dbeta,
+                               int C, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Stem: conv3x3(Cin<=5 -> 64, pad 1, no bias) + BN + ReLU + MaxPool(k2,s2,p1), computed
