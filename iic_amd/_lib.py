@@ -89,6 +89,9 @@ _SIGNATURES = {
   "iic_augment": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, c_int, _P, _P]),
   "iic_seg_augment": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P,
                               _P, _P]),
+  "iic_seg_augment_ragged": (c_int, [_P, _P, _P, c_int, c_long, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P,
+                                     _P, _P, _P, _P, _P]),
+  "iic_seg_augment_warp": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
   "iic_seg_prepare_test": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P,
                                    _P, _P, _P]),
   "iic_stem_bwd_fused": (c_int, [_P, _P, _P, _P, _P, _P, POINTER(c_int), c_int, c_int, c_int, c_int, _P]),

@@ -33,6 +33,10 @@
 // seg_prepare_test_kernel (below the training kernel) is the test-time twin, `_prepare_test`
 // (potsdam.py:295-350, cocostuff.py:309-358): the centre crop, one view, no jitter, plus the
 // filtered label map; it shares seg_load, seg_grey and seg_pad_offset with the training kernel.
+//
+// seg_augment_ragged_kernel (between the two) is the training kernel for a dataset whose images differ in size
+// (COCO-Stuff): images packed without padding, every sample padded and cropped by its own extent, optionally resampled
+// through host-built tables (use_random_scale); it shares seg_load, seg_grey, seg_jitter and seg_pad_offset.
 #include "common.h"
 #include "aug_jitter.h"
 #include "../../include/iic_hip.h"
@@ -199,6 +203,239 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_augment_kernel(
   }
 }
 
+// ---- datasets whose images differ in size (COCO-Stuff), optionally with use_random_scale: the packed twin of
+// seg_augment_kernel.  Image i is h_i x w_i x CS at pixel offset offsets[i] of one packed array, row pitch w_i; pad
+// offsets and the inside test come from the sample's own extent (cocostuff.py:133-135 over transforms.py:23-88).
+// SCALED (cocostuff.py:123-130, potsdam.py:109-114): every crop row and column carries a host-built resampling tap
+// (iic_seg_resample_tap: OpenCV 3.x's INTER_LINEAR coefficients for the float image, INTER_NEAREST's index for the
+// label); the kernel only multiplies and adds, in cv2's order (horizontal pass, then vertical), each operation rounded
+// to float32 on its own, and truncates RGB to uint8 as `img.astype(np.uint8)` does after the crop.  Without SCALED no
+// tap is read.
+struct seg_ragged_src {
+  const uint8_t* im;             // nullptr: a black image
+  const uint8_t* lb;             // nullptr: no labels, or a black image
+  int h, w;                      // the stored extent; w is the row pitch
+  int x0, y0;                    // crop origin in source coordinates (not SCALED)
+  const iic_seg_resample_tap* ty;   // S row taps, then S column taps (SCALED)
+  const iic_seg_resample_tap* tx;
+};
+
+__device__ __forceinline__ int seg_clamp_index(int i, int len) { return i < 0 ? 0 : (i >= len ? len - 1 : i); }
+
+// (a * wa + b * wb), every operation rounded to float32 (contraction is off in this file)
+__device__ __forceinline__ float seg_lerp(float a, float wa, float b, float wb) { return a * wa + b * wb; }
+
+__device__ __forceinline__ int seg_trunc_u8(float v) {
+  const int i = (int)v;          // toward zero, as astype(np.uint8) of a value in [0, 256)
+  return i < 0 ? 0 : (i > 255 ? 255 : i);
+}
+
+// one pixel of the crop at (y, x): r, g, b, ir and the fine label l (0 in the padding).  SCALED: irf is the resampled
+// IR value BEFORE truncation -- the reference truncates only the RGB part it hands to PIL (potsdam.py:148-151), IR goes
+// on as the float image / 255. (potsdam.py:170)
+template <int CS, bool SCALED>
+__device__ __forceinline__ void seg_ragged_fetch(const seg_ragged_src& s, int y, int x, bool want_label, int& r, int& g,
+                                                 int& b, int& ir, float& irf, int& l) {
+  l = 0;
+  irf = 0.f;
+  if (!SCALED) {
+    const int sy = s.y0 + y, sx = s.x0 + x;
+    seg_load<CS>(s.im, sy, sx, s.h, s.w, r, g, b, ir);
+    if (want_label && s.lb != nullptr && sy >= 0 && sy < s.h && sx >= 0 && sx < s.w) l = s.lb[(long)sy * s.w + sx];
+  } else {
+    r = g = b = ir = 0;
+    const iic_seg_resample_tap ty = s.ty[y], tx = s.tx[x];
+    if (s.im == nullptr || !ty.inside || !tx.inside) return;
+    const int ya = seg_clamp_index(ty.i0, s.h), yb = seg_clamp_index(ty.i1, s.h);
+    const int xa = seg_clamp_index(tx.i0, s.w), xb = seg_clamp_index(tx.i1, s.w);
+    int p00[4], p01[4], p10[4], p11[4];
+    seg_load<CS>(s.im, ya, xa, s.h, s.w, p00[0], p00[1], p00[2], p00[3]);
+    seg_load<CS>(s.im, ya, xb, s.h, s.w, p01[0], p01[1], p01[2], p01[3]);
+    seg_load<CS>(s.im, yb, xa, s.h, s.w, p10[0], p10[1], p10[2], p10[3]);
+    seg_load<CS>(s.im, yb, xb, s.h, s.w, p11[0], p11[1], p11[2], p11[3]);
+    int out[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < CS; ++c) {
+      const float top = seg_lerp((float)p00[c], tx.a0, (float)p01[c], tx.a1);
+      const float bot = seg_lerp((float)p10[c], tx.a0, (float)p11[c], tx.a1);
+      const float v = seg_lerp(top, ty.a0, bot, ty.a1);
+      out[c] = seg_trunc_u8(v);
+      if (c == 3) irf = v;
+    }
+    r = out[0]; g = out[1]; b = out[2]; ir = out[3];
+    if (want_label && s.lb != nullptr)
+      l = s.lb[(long)seg_clamp_index(ty.nearest, s.h) * s.w + seg_clamp_index(tx.nearest, s.w)];
+  }
+}
+
+// MODE as above.  One workgroup per sample, a thread per four consecutive output x of one row, as seg_augment_kernel.
+template <int CS, int MODE, bool SCALED>
+__global__ __launch_bounds__(SEG_THREADS) void seg_augment_ragged_kernel(
+    const uint8_t* __restrict__ imgs, const uint8_t* __restrict__ labels, const uint8_t* __restrict__ table,
+    const long* __restrict__ offsets, const int* __restrict__ sizes, int B, long total_px,
+    const int* __restrict__ iparams, const float* __restrict__ fparams, const iic_seg_resample_tap* __restrict__ taps,
+    int S, const float* __restrict__ lut, float* __restrict__ img1, float* __restrict__ img2, uint8_t* __restrict__ mask,
+    float* __restrict__ aff) {
+  __shared__ int s_red[SEG_THREADS / 64];
+  constexpr int C = (MODE == 0 ? 3 : (MODE == 1 ? 4 : 1)) + (CS == 4 ? 1 : 0);
+  constexpr int CG = MODE == 1 ? 3 : 0;
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const int* ip = iparams + (long)n * SEG_IP;
+  const float* fp = fparams + (long)n * SEG_FP;
+  const int src = ip[0], flip = ip[3] & 1, defer = (ip[3] >> 1) & 1;
+  int nops = ip[4];
+  nops = nops < 0 ? 0 : (nops > 4 ? 4 : nops);
+  const int opsw = (ip[5] & 3) | ((ip[6] & 3) << 4) | ((ip[7] & 3) << 8) | ((ip[8] & 3) << 12);
+  const int hdelta = ip[9] & 255;
+  const float f_b = fp[0], f_c = fp[1], f_s = fp[2];
+  // an index outside the dataset, or an image whose extent or offset would leave the pack, reads as a black image
+  seg_ragged_src s = {nullptr, nullptr, 1, 1, 0, 0, nullptr, nullptr};
+  if (src >= 0 && src < B) {
+    const int h = sizes[2 * src], w = sizes[2 * src + 1];
+    const long off = offsets[src];
+    if (h >= 1 && h <= 16384 && w >= 1 && w <= 16384 && off >= 0 && off <= total_px && (long)h * w <= total_px - off) {
+      s.im = imgs + off * CS;
+      s.lb = labels != nullptr ? labels + off : nullptr;
+      s.h = h; s.w = w;
+      s.x0 = ip[1] - seg_pad_offset(w, S);
+      s.y0 = ip[2] - seg_pad_offset(h, S);
+    }
+  }
+  if (SCALED) {
+    s.ty = taps + (long)n * 2 * S;
+    s.tx = s.ty + S;
+  }
+  const int Q = S >> 2, nquads = S * Q;
+
+  // ---- affine2_to_1: the given rows, top row negated when flipped (cocostuff.py:220)
+  if (tid < 6) {
+    const float v = fp[4 + tid];
+    aff[(long)n * 6 + tid] = (flip && tid < 3) ? v * -1.f : v;
+  }
+
+  // ---- contrast: rounded mean of the L image after the ops that precede it, over all S * S pixels, padding included
+  int cpos = -1;
+  for (int o = 0; o < nops; ++o)
+    if (((opsw >> (4 * o)) & 15) == 1 && cpos < 0) cpos = o;
+  int mean = 0;
+  if (cpos >= 0) {                                   // uniform over the workgroup
+    int part = 0;
+    for (int q = tid; q < nquads; q += SEG_THREADS) {
+      const int y = q / Q, xq = (q - y * Q) << 2;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int r, g, b, ir, l;
+        float irf;
+        seg_ragged_fetch<CS, SCALED>(s, y, xq + j, false, r, g, b, ir, irf, l);
+        seg_jitter(r, g, b, opsw, 0, cpos, f_b, f_c, f_s, 0, hdelta);
+        part += aug_luma(r, g, b);
+      }
+    }
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) part += __shfl_xor(part, sft, 64);
+    if ((tid & 63) == 0) s_red[tid >> 6] = part;
+    __syncthreads();
+    int tot = 0;
+#pragma unroll
+    for (int w = 0; w < SEG_THREADS / 64; ++w) tot += s_red[w];
+    mean = (int)((double)tot / (double)(S * S) + 0.5);
+  }
+
+  // ---- both views
+  const long plane = (long)S * S;
+  float* o1 = img1 + (long)n * C * plane;
+  float* o2 = img2 + (long)n * C * plane;
+  uint8_t* om = mask + (long)n * plane;
+  const bool mirror = flip && !defer;
+  for (int q = tid; q < nquads; q += SEG_THREADS) {
+    const int y = q / Q, xq = (q - y * Q) << 2;
+    f32x4 v1[C], v2[C];
+    uint32_t mk = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int r, g, b, ir, l;
+      float irf;
+      seg_ragged_fetch<CS, SCALED>(s, y, xq + j, labels != nullptr, r, g, b, ir, irf, l);
+      const int m = labels != nullptr ? (int)table[l] : 1;
+      mk |= (uint32_t)(m & 255) << (8 * j);
+      int r2 = r, g2 = g, b2 = b;
+      seg_jitter(r2, g2, b2, opsw, 0, nops, f_b, f_c, f_s, mean, hdelta);
+      if (MODE != 2) {
+        v1[0][j] = lut[r]; v1[1][j] = lut[g]; v1[2][j] = lut[b];
+        v2[0][j] = lut[r2]; v2[1][j] = lut[g2]; v2[2][j] = lut[b2];
+      }
+      if (MODE != 0) {
+        v1[CG][j] = lut[seg_grey(r, g, b)];
+        v2[CG][j] = lut[seg_grey(r2, g2, b2)];
+      }
+      if (CS == 4) {
+        const float vir = SCALED ? irf / 255.f : lut[ir];
+        v1[C - 1][j] = vir;
+        v2[C - 1][j] = vir;
+      }
+    }
+    const long off1 = (long)y * S + xq;
+    const long off2 = (long)y * S + (mirror ? S - 4 - xq : xq);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      *reinterpret_cast<f32x4*>(o1 + c * plane + off1) = v1[c];
+      const f32x4 m2 = {v2[c][3], v2[c][2], v2[c][1], v2[c][0]};     // torch.flip(img2, dims=[2]) within the run
+      *reinterpret_cast<f32x4*>(o2 + c * plane + off2) = mirror ? m2 : v2[c];
+    }
+    *reinterpret_cast<uint32_t*>(om + off1) = mk;
+  }
+}
+
+// ---- random_affine's warp of img2 for the ragged augmenter: perform_affine_tf (transforms.py:131-143), F.affine_grid +
+// F.grid_sample (bilinear, zeros, align_corners false -- the convention of seg_losses.ALIGN_CORNERS), followed by
+// torch.flip(dims=[2]) where flips[n], restated operation by operation so that the result is bit-identical to what the
+// reference computes on a CPU (tests/golden/seg_augment_ragged.npz): the sampling position is
+// fma(y_b, t01, x_b * t00) + t02 on the host-made base grid (linspace(-1, 1, S) * (S - 1) / S), un-normalised as
+// fma(g + 1, S / 2, -0.5); the four taps are accumulated as nw_val * nw, then one fma per further tap in the order ne,
+// sw, se, with the weights (1 - fy)(1 - fx), (1 - fy) fx, fy (1 - fx), fy fx.  iic_affine_warp_fwd computes the same warp
+// from a pixel-space matrix in another order of operations (within 2e-6 of this one).
+#define SEG_WARP_THREADS 256
+__global__ __launch_bounds__(SEG_WARP_THREADS) void seg_grid_warp_kernel(
+    const float* __restrict__ x, const float* __restrict__ theta, const int* __restrict__ flips,
+    const float* __restrict__ base, float* __restrict__ out, int N, int C, int S) {
+  const long idx = (long)blockIdx.x * SEG_WARP_THREADS + threadIdx.x;
+  const long plane = (long)S * S;
+  if (idx >= (long)N * plane) return;
+  const int n = (int)(idx / plane);
+  const int rem = (int)(idx - (long)n * plane);
+  const int oy = rem / S, ox = rem - oy * S;
+  const float* t = theta + (long)n * 6;
+  const float xb = base[flips[n] ? S - 1 - ox : ox], yb = base[oy];
+  const float gx = __fmaf_rn(yb, t[1], xb * t[0]) + t[2];
+  const float gy = __fmaf_rn(yb, t[4], xb * t[3]) + t[5];
+  const float half = (float)S / 2.f;
+  const float fx = __fmaf_rn(gx + 1.f, half, -0.5f), fy = __fmaf_rn(gy + 1.f, half, -0.5f);
+  const float* xi = x + (long)n * C * plane;
+  float* o = out + (long)n * C * plane + rem;
+  // a position further than one pixel outside the image (or not a number) has four zero taps
+  if (!(fx > -1.f && fx < (float)S && fy > -1.f && fy < (float)S)) {
+    for (int c = 0; c < C; ++c) o[c * plane] = 0.f;
+    return;
+  }
+  const float xw = floorf(fx), yn = floorf(fy);
+  const float w = fx - xw, e = 1.f - w, nn = fy - yn, s = 1.f - nn;
+  const float nw = s * e, ne = s * w, sw = nn * e, se = nn * w;
+  const int ix = (int)xw, iy = (int)yn;
+  const bool x0 = ix >= 0, x1 = ix + 1 < S, y0 = iy >= 0, y1 = iy + 1 < S;     // ix, iy in [-1, S - 1]
+  for (int c = 0; c < C; ++c) {
+    const float* p = xi + c * plane;
+    const float a = (y0 && x0) ? p[(long)iy * S + ix] : 0.f;
+    const float b = (y0 && x1) ? p[(long)iy * S + ix + 1] : 0.f;
+    const float cc = (y1 && x0) ? p[(long)(iy + 1) * S + ix] : 0.f;
+    const float d = (y1 && x1) ? p[(long)(iy + 1) * S + ix + 1] : 0.f;
+    float r = a * nw;
+    r = __fmaf_rn(b, ne, r);
+    r = __fmaf_rn(cc, sw, r);
+    r = __fmaf_rn(d, se, r);
+    o[c * plane] = r;
+  }
+}
+
 // ---- test-time batches: `_prepare_test`, one thread per four consecutive output x of one row, no LDS
 #define SEG_TEST_THREADS 256
 
@@ -317,6 +554,55 @@ int iic_seg_augment(const void* imgs_u8, int B, int H, int W, int Cs, const void
     else SEG_LAUNCH(4, 2);
   }
 #undef SEG_LAUNCH
+  return iic_launch_status();
+}
+
+int iic_seg_augment_ragged(const void* imgs_u8, const long* offsets, const int* sizes, int B, long total_px, int Cs,
+                           const void* labels_u8, const void* relevance, const int* iparams, const float* fparams,
+                           const iic_seg_resample_tap* taps, int N, int S, int no_sobel, int include_rgb,
+                           const float* lut, float* img1, float* img2, void* mask_img1, float* affine2_to_1,
+                           void* stream) {
+  if (!imgs_u8 || !offsets || !sizes || !iparams || !fparams || !lut || !img1 || !img2 || !mask_img1 || !affine2_to_1)
+    return IIC_ERR_ARG;
+  if (B <= 0 || N <= 0 || S <= 0 || total_px <= 0) return IIC_ERR_ARG;
+  if ((labels_u8 == nullptr) != (relevance == nullptr)) return IIC_ERR_ARG;
+  if (Cs != 3 && Cs != 4) return IIC_ERR_UNSUPPORTED;
+  if (S % 4 != 0 || S > 4096) return IIC_ERR_UNSUPPORTED;
+  const int mode = no_sobel ? 0 : (include_rgb ? 1 : 2);
+  hipStream_t s = (hipStream_t)stream;
+#define SEG_LAUNCH(CS_, MODE_, SCALED_)                                                                        \
+  hipLaunchKernelGGL((seg_augment_ragged_kernel<CS_, MODE_, SCALED_>), dim3(N), dim3(SEG_THREADS), 0, s,       \
+                     (const uint8_t*)imgs_u8, (const uint8_t*)labels_u8, (const uint8_t*)relevance, offsets,   \
+                     sizes, B, total_px, iparams, fparams, taps, S, lut, img1, img2, (uint8_t*)mask_img1,      \
+                     affine2_to_1)
+#define SEG_LAUNCH_MODE(CS_, SCALED_)          \
+  do {                                         \
+    if (mode == 0) SEG_LAUNCH(CS_, 0, SCALED_); \
+    else if (mode == 1) SEG_LAUNCH(CS_, 1, SCALED_); \
+    else SEG_LAUNCH(CS_, 2, SCALED_);          \
+  } while (0)
+  if (taps == nullptr) {
+    if (Cs == 3) SEG_LAUNCH_MODE(3, false);
+    else SEG_LAUNCH_MODE(4, false);
+  } else {
+    if (Cs == 3) SEG_LAUNCH_MODE(3, true);
+    else SEG_LAUNCH_MODE(4, true);
+  }
+#undef SEG_LAUNCH_MODE
+#undef SEG_LAUNCH
+  return iic_launch_status();
+}
+
+int iic_seg_augment_warp(const float* img2, const float* affine1_to_2, const int* flips, const float* base_grid,
+                         float* out, int N, int C, int S, void* stream) {
+  if (!img2 || !affine1_to_2 || !flips || !base_grid || !out || img2 == out) return IIC_ERR_ARG;
+  if (N <= 0 || C <= 0 || S <= 0) return IIC_ERR_ARG;
+  if (S > 4096 || C > 8) return IIC_ERR_UNSUPPORTED;
+  const long total = (long)N * S * S;
+  const long blocks = (total + SEG_WARP_THREADS - 1) / SEG_WARP_THREADS;
+  if (blocks > 0x7fffffffL) return IIC_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(seg_grid_warp_kernel, dim3((unsigned)blocks), dim3(SEG_WARP_THREADS), 0, (hipStream_t)stream, img2,
+                     affine1_to_2, flips, base_grid, out, N, C, S);
   return iic_launch_status();
 }
 

@@ -84,7 +84,71 @@ def _flag(config, name, default=False):
   return getattr(config, name, default)
 
 
-class SegPairedAugmenter(object):
+class _SegDraws(object):
+  """What SegPairedAugmenter and seg_ragged.SegRaggedAugmenter share: the reference's flags, its jitter and
+  random_affine draws from self.rng, the channel layout, and the warp of img2 that follows either kernel."""
+
+  def _read_flags(self, config, seed, device):
+    self.no_sobel, self.include_rgb = bool(config.no_sobel), bool(config.include_rgb)
+    self.jitter = tuple(float(getattr(config, "jitter_" + n)) for n in ("brightness", "contrast", "saturation", "hue"))
+    self.flip_p = float(config.flip_p)
+    self.use_random_affine = bool(_flag(config, "use_random_affine"))
+    if self.use_random_affine:
+      self.aff = tuple(float(getattr(config, "aff_" + n)) for n in
+                       ("min_rot", "max_rot", "min_shear", "max_shear", "min_scale", "max_scale"))
+    self.rng = np.random.RandomState(seed)
+    self.lut = (torch.arange(256, dtype=torch.float32) / 255).to(device)               # astype(float32) / 255.
+
+  @property
+  def out_channels(self):
+    return (3 if self.no_sobel else (4 if self.include_rgb else 1)) + (1 if self.Cs == 4 else 0)
+
+  def _jitter_draws(self, ip, fp):
+    """torchvision 0.2.1 ColorJitter.get_params: one uniform per non-zero strength, in the order brightness,
+    contrast, saturation, hue, then np.random.shuffle of the op list."""
+    r = self.rng
+    b, c, s, h = self.jitter
+    ops = []
+    if b > 0:
+      fp[OP_BRIGHTNESS] = r.uniform(max(0, 1 - b), 1 + b)
+      ops.append(OP_BRIGHTNESS)
+    if c > 0:
+      fp[OP_CONTRAST] = r.uniform(max(0, 1 - c), 1 + c)
+      ops.append(OP_CONTRAST)
+    if s > 0:
+      fp[OP_SATURATION] = r.uniform(max(0, 1 - s), 1 + s)
+      ops.append(OP_SATURATION)
+    hue = 0.0
+    if h > 0:
+      hue = r.uniform(-h, h)
+      fp[OP_HUE] = hue
+      ops.append(OP_HUE)
+    r.shuffle(ops)
+    ip[4] = len(ops)
+    ip[5:5 + len(ops)] = ops
+    ip[9] = hue_shift(float(hue))
+    return hue
+
+  def _affine_draw(self):
+    """random_affine (transforms.py:111-121): the three uniforms, affine1_to_2 and its float32 inverse."""
+    min_rot, max_rot, min_shear, max_shear, min_scale, max_scale = self.aff
+    r = self.rng
+    a = np.radians(r.rand() * (max_rot - min_rot) + min_rot)
+    shear = np.radians(r.rand() * (max_shear - min_shear) + min_shear)
+    scale = r.rand() * (max_scale - min_scale) + min_scale
+    return affine_pair(a, shear, scale)
+
+  def _warp_img2(self, img2, a12, iparams):
+    """img2 = flip(perform_affine_tf(img2, affine1_to_2)) as one iic_affine_warp_fwd launch."""
+    n, C, S = int(img2.shape[0]), int(img2.shape[1]), self.S
+    mats = warp_matrices(a12, iparams[:, 3] & 1, S).to(img2.device, non_blocking=True)
+    warped = torch.empty_like(img2)
+    _lib.check(_lib.lib().iic_affine_warp_fwd(img2.data_ptr(), mats.data_ptr(), warped.data_ptr(), n, C, S, S,
+                                              0, 0, _lib.stream_ptr()), "iic_affine_warp_fwd")
+    return warped
+
+
+class SegPairedAugmenter(_SegDraws):
   """images_u8: uint8 [B, H, W, Cs] on the GPU, Cs = 3 (COCO-Stuff, RGB) or 4 (Potsdam, RGB + IR);
   labels_u8: uint8 [B, H, W] fine labels with 255 for the reference's -1, and relevance: the 256-entry
   table of `relevance_table` -- both or neither (neither: mask_img1 is all ones, as for Potsdam).
@@ -136,45 +200,7 @@ class SegPairedAugmenter(object):
                                             dtype=np.uint8).reshape(-1))
       assert rel.shape == (256,)
       self.relevance = torch.from_numpy(rel).to(images_u8.device)
-    self.no_sobel, self.include_rgb = bool(config.no_sobel), bool(config.include_rgb)
-    self.jitter = tuple(float(getattr(config, "jitter_" + n)) for n in ("brightness", "contrast", "saturation", "hue"))
-    self.flip_p = float(config.flip_p)
-    self.use_random_affine = bool(_flag(config, "use_random_affine"))
-    if self.use_random_affine:
-      self.aff = tuple(float(getattr(config, "aff_" + n)) for n in
-                       ("min_rot", "max_rot", "min_shear", "max_shear", "min_scale", "max_scale"))
-    self.rng = np.random.RandomState(seed)
-    self.lut = (torch.arange(256, dtype=torch.float32) / 255).to(images_u8.device)     # astype(float32) / 255.
-
-  @property
-  def out_channels(self):
-    return (3 if self.no_sobel else (4 if self.include_rgb else 1)) + (1 if self.Cs == 4 else 0)
-
-  def _jitter_draws(self, ip, fp):
-    """torchvision 0.2.1 ColorJitter.get_params: one uniform per non-zero strength, in the order brightness,
-    contrast, saturation, hue, then np.random.shuffle of the op list."""
-    r = self.rng
-    b, c, s, h = self.jitter
-    ops = []
-    if b > 0:
-      fp[OP_BRIGHTNESS] = r.uniform(max(0, 1 - b), 1 + b)
-      ops.append(OP_BRIGHTNESS)
-    if c > 0:
-      fp[OP_CONTRAST] = r.uniform(max(0, 1 - c), 1 + c)
-      ops.append(OP_CONTRAST)
-    if s > 0:
-      fp[OP_SATURATION] = r.uniform(max(0, 1 - s), 1 + s)
-      ops.append(OP_SATURATION)
-    hue = 0.0
-    if h > 0:
-      hue = r.uniform(-h, h)
-      fp[OP_HUE] = hue
-      ops.append(OP_HUE)
-    r.shuffle(ops)
-    ip[4] = len(ops)
-    ip[5:5 + len(ops)] = ops
-    ip[9] = hue_shift(float(hue))
-    return hue
+    self._read_flags(config, seed, images_u8.device)
 
   def draw(self, idx):
     """The reference's draws for the samples `idx`, per sample in its order: crop centre (h, w), jitter,
@@ -210,15 +236,6 @@ class SegPairedAugmenter(object):
     fp[:, :4] = fp64
     return dict(iparams=ip, fparams=fp, coords=coords, hue=hue, affine1_to_2=a12)
 
-  def _affine_draw(self):
-    """random_affine (transforms.py:111-121): the three uniforms, affine1_to_2 and its float32 inverse."""
-    min_rot, max_rot, min_shear, max_shear, min_scale, max_scale = self.aff
-    r = self.rng
-    a = np.radians(r.rand() * (max_rot - min_rot) + min_rot)
-    shear = np.radians(r.rand() * (max_shear - min_shear) + min_shear)
-    scale = r.rand() * (max_scale - min_scale) + min_scale
-    return affine_pair(a, shear, scale)
-
   def apply(self, params):
     iparams = np.ascontiguousarray(params["iparams"], dtype=np.int32)
     fparams = np.ascontiguousarray(params["fparams"], dtype=np.float32)
@@ -250,11 +267,7 @@ class SegPairedAugmenter(object):
       ip.data_ptr(), fp.data_ptr(), n, S, int(self.no_sobel), int(self.include_rgb), self.lut.data_ptr(),
       img1.data_ptr(), img2.data_ptr(), mask.data_ptr(), aff.data_ptr(), _lib.stream_ptr()), "iic_seg_augment")
     if a12 is not None:
-      mats = warp_matrices(a12, iparams[:, 3] & 1, S).to(dev, non_blocking=True)
-      warped = torch.empty_like(img2)
-      _lib.check(_lib.lib().iic_affine_warp_fwd(img2.data_ptr(), mats.data_ptr(), warped.data_ptr(), n, C, S, S,
-                                                0, 0, _lib.stream_ptr()), "iic_affine_warp_fwd")
-      img2 = warped
+      img2 = self._warp_img2(img2, a12, iparams)
     return img1, img2, aff, mask
 
   def paired_batch(self, idx):
@@ -290,27 +303,50 @@ def warp_matrices(affine1_to_2, flips, S):
 
 class _SegPairedLoader(object):
   """One element of the list `_create_dataloaders` returns (code/utils/segmentation/data.py:86-126):
-  iterating yields (img1, img2, affine2_to_1, mask_img1) batches in sequential sample order, the last one
-  ragged (drop_last=False); every loader of the list draws its own augmentation of the same samples."""
+  iterating yields (img1, img2, affine2_to_1, mask_img1) batches, the last one ragged (drop_last=False); every loader
+  of the list draws its own augmentation of the same samples.  order: None for sequential sample order, else the
+  `_EpochOrder` the loaders of one list share."""
 
-  def __init__(self, augmenter, batch_sz):
-    self.aug, self.batch_sz, self.n = augmenter, int(batch_sz), int(augmenter.B)
+  def __init__(self, augmenter, batch_sz, order=None):
+    self.aug, self.batch_sz, self.n, self.order = augmenter, int(batch_sz), int(augmenter.B), order
+    self.epoch = 0
     assert self.batch_sz > 0
 
   def __len__(self):
     return (self.n + self.batch_sz - 1) // self.batch_sz
 
   def __iter__(self):
+    perm = np.arange(self.n) if self.order is None else self.order.permutation(self.epoch)
+    self.epoch += 1
     for lo in range(0, self.n, self.batch_sz):
-      yield self.aug.paired_batch(np.arange(lo, min(self.n, lo + self.batch_sz)))
+      yield self.aug.paired_batch(perm[lo:min(self.n, lo + self.batch_sz)])
 
 
-def seg_paired_dataloaders(augmenter, batch_sz, num_dataloaders):
+class _EpochOrder(object):
+  """The sample order of epoch e, the same for every loader that asks: a permutation seeded by (seed, e) alone,
+  from a generator that serves nothing else, so the augmenter's draws are what they would be without shuffling."""
+
+  def __init__(self, n, seed):
+    self.n, self.seed = int(n), int(seed)
+
+  def permutation(self, epoch):
+    return np.random.RandomState([self.seed, int(epoch)]).permutation(self.n)
+
+
+def seg_paired_dataloaders(augmenter, batch_sz, num_dataloaders, shuffle=False, shuffle_seed=0):
   """Drop-in for the list of DataLoaders the segmentation scripts zip
   (code/scripts/segmentation/segmentation_twohead.py:262-300): num_dataloaders loaders over the same
-  samples, each yielding the four tensors of `_prepare_train` per batch, already on the GPU."""
+  samples, each yielding the four tensors of `_prepare_train` per batch, already on the GPU.  augmenter: a
+  SegPairedAugmenter or a seg_ragged.SegRaggedAugmenter.
+
+  shuffle=False (default): sequential sample order.  shuffle=True: every epoch (every iteration of the loaders)
+  visits the samples in a fresh permutation, the same one for every loader of the list, drawn from a generator of
+  its own (shuffle_seed) so that the augmentation draws do not shift.  The reference shuffles when
+  num_dataloaders == 1 (code/utils/segmentation/data.py:90) with torch's randperm; that permutation is NOT
+  reproduced here, only the property that each epoch is a permutation."""
   assert int(num_dataloaders) >= 1
-  return [_SegPairedLoader(augmenter, batch_sz) for _ in range(int(num_dataloaders))]
+  order = _EpochOrder(augmenter.B, shuffle_seed) if shuffle else None
+  return [_SegPairedLoader(augmenter, batch_sz, order) for _ in range(int(num_dataloaders))]
 
 
 # ------------------------------------------------------------------------------------------

@@ -575,6 +575,59 @@ int iic_seg_augment(const void* imgs_u8, int B, int H, int W, int Cs, const void
                     void* mask_img1, float* affine2_to_1, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * iic_seg_augment for a dataset whose images differ in size (COCO-Stuff: every published command,
+ * examples/commands.txt:74-97), optionally with use_random_scale.  The reference pads and crops each image by
+ * its own extent: pad_if_too_small + pad_and_or_crop(mode="random") of
+ * code/utils/segmentation/transforms.py:23-88, called from code/datasets/segmentation/cocostuff.py:133-135
+ * (potsdam.py:117); the random scale is cocostuff.py:123-130 / potsdam.py:109-114.
+ * imgs_u8    uint8, the images concatenated without padding: image i is [h_i][w_i][Cs] (row pitch w_i) and starts
+ *            at PIXEL offsets[i]; Cs = 3 or 4 (with 4 every pixel stays 4-byte aligned).
+ * offsets    int64 [B]; sizes int32 [B][2] = (h_i, w_i), 1 <= h_i, w_i <= 16384; total_px: pixels in the pack.
+ *            An image with offsets[i] + h_i w_i > total_px (or an extent out of range) reads as a black image:
+ *            no read leaves [0, total_px) whatever the tables hold.
+ * labels_u8  uint8 at the same pixel offsets, one byte per pixel, 255 = -1, or NULL; relevance as for
+ *            iic_seg_augment.  Label pixels outside the image are fine label 0 (pad_if_too_small zero-fills).
+ * iparams, fparams, lut, img1, img2, mask_img1, affine2_to_1, no_sobel, include_rgb: as for iic_seg_augment;
+ *            the crop origin is in THIS sample's padded image: sides of max(len, S), the source at
+ *            int(max(len, S) / 2.) - int(len / 2.) inside, where len is the sample's h or w -- after the random
+ *            scale, the scaled one.  ColorJitter's contrast mean divides by S * S, padding included.  A source
+ *            index outside [0, B) reads as a black image.
+ * taps       NULL: no random scale, no table is read.  Else iic_seg_resample_tap [N][2][S]: for sample n the S
+ *            crop rows, then the S crop columns, of the crop in the image scaled by cv2.resize(fx = fy = scale)
+ *            (OpenCV 3.x resize on float32, restated from its source, not compared against a cv2 binary):
+ *            inside = 0 in the padding; i0, i1, a0, a1 the two INTER_LINEAR taps of the source side and their
+ *            float32 weights; nearest the INTER_NEAREST source index (labels).  The kernel computes
+ *            (p00 ax0 + p01 ax1) by0 + (p10 ax0 + p11 ax1) by1 on the uint8 pixels as float32, every product and
+ *            sum rounded separately, and truncates R, G, B toward zero to uint8 before the jitter; IR (Cs = 4) is
+ *            NOT truncated, as in the reference (potsdam.py:148-151 truncates the RGB part only, :170 divides the
+ *            float IR plane): its output is value / 255.f.  With taps the crop origin in iparams is not read
+ *            (the tables carry it).  Tap indices are clamped to the image.
+ * The random affine of the second view is a following iic_seg_augment_warp of img2 (flip bit 1 defers the mirror).
+ * One workgroup per sample, 16-byte planar stores (S % 4 == 0), no atomics: two calls give identical bytes.
+ * ------------------------------------------------------------------------------- */
+typedef struct iic_seg_resample_tap {
+  int32_t i0, i1;
+  float a0, a1;
+  int32_t nearest;
+  int32_t inside;
+} iic_seg_resample_tap;
+int iic_seg_augment_ragged(const void* imgs_u8, const long* offsets, const int* sizes, int B, long total_px,
+                           int Cs, const void* labels_u8, const void* relevance, const int* iparams,
+                           const float* fparams, const iic_seg_resample_tap* taps, int N, int S, int no_sobel,
+                           int include_rgb, const float* lut, float* img1, float* img2, void* mask_img1,
+                           float* affine2_to_1, void* stream);
+
+/* random_affine's warp of the second view for iic_seg_augment_ragged (code/utils/segmentation/transforms.py:
+ * 122-143: perform_affine_tf = F.affine_grid + F.grid_sample, bilinear, zero padding; then torch.flip(dims=[2]),
+ * cocostuff.py:213-214), in the operation order of torch's CPU kernels, so that img2 equals the reference's bit for
+ * bit on the reference-generated fixture (iic_affine_warp_fwd computes the same warp from a pixel-space matrix within
+ * 2e-6 of it).  img2, out float [N][C][S][S] (out != img2); affine1_to_2 float [N][6], the matrix random_affine
+ * draws, in normalised coordinates; flips int32 [N]: mirror the output row; base_grid float [S] =
+ * linspace(-1, 1, S) * (S - 1) / S as F.affine_grid(align_corners=False) builds it (made by the host).            */
+int iic_seg_augment_warp(const float* img2, const float* affine1_to_2, const int* flips,
+                         const float* base_grid, float* out, int N, int C, int S, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Test-time batches of the segmentation datasets on the GPU -- replaces the per-sample host pipeline of
  * the evaluation __getitem__:
  *   code/datasets/segmentation/potsdam.py:295-350   (_Potsdam._prepare_test)

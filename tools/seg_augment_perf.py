@@ -10,6 +10,15 @@
 
     python tools/seg_augment_perf.py [--iters 50] [--repeats 7] [--host-batches 2]
 
+--ragged: instead, the kernel for images of different sizes (iic_seg_augment_ragged, iic_amd/seg_ragged.py) against
+iic_seg_augment at the COCO-Stuff-3 shape (batch 120, input_sz 128, sobel + include_rgb, label masks, 24 resident
+images around 213 x 160): (a) both kernels on the SAME uniform 160 x 213 data and parameters, outputs compared byte for
+byte first; (b) the ragged kernel on a pack of genuinely different sizes; (c) the same pack with use_random_scale.
+Kernel alone (parameters resident, outputs preallocated) and `apply` (parameter upload, tap tables, allocations, launch),
+one process, the variants interleaved window by window: REPEATS windows of ITERS calls each per variant.
+
+    python tools/seg_augment_perf.py --ragged [--iters 1000] [--repeats 9]
+
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -40,14 +49,131 @@ def timed(fn, iters, repeats):
   return float(np.median(out)), float(min(out)), float(max(out))
 
 
+def interleaved(fns, iters, repeats):
+  """{name: (median, min, max) ms per call}: after a warm-up of every variant, `repeats` rounds, each timing one window
+  of `iters` calls of every variant in turn with device events."""
+  for fn in fns.values():
+    for _ in range(5):
+      fn()
+  torch.cuda.synchronize()
+  out = {k: [] for k in fns}
+  for _ in range(repeats):
+    for k, fn in fns.items():
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(iters):
+        fn()
+      e1.record()
+      torch.cuda.synchronize()
+      out[k].append(e0.elapsed_time(e1) / iters)
+  return {k: (float(np.median(v)), float(min(v)), float(max(v))) for k, v in out.items()}
+
+
+def ragged_mode(a):
+  import types
+  from iic_amd import _lib, seg_augment as sa, seg_ragged as sr
+  dev = torch.device("cuda:0")
+  L = _lib.lib()
+  B, batch, S, H, W = 24, 120, 128, 160, 213
+  rng = np.random.default_rng(2024)
+  rel = (np.arange(256) >= 91).astype(np.uint8)
+  rel[182:] = 0
+
+  def cfg(scale=False):
+    return types.SimpleNamespace(input_sz=S, no_sobel=False, include_rgb=True, jitter_brightness=0.4, jitter_contrast=0.4,
+                                 jitter_saturation=0.4, jitter_hue=0.125, flip_p=0.5, use_random_affine=False,
+                                 use_random_scale=scale, scale_min=0.6, scale_max=1.4, pre_scale_all=not scale)
+
+  def content(shapes):
+    imgs = [rng.integers(0, 256, s + (3,), dtype=np.uint8) for s in shapes]
+    labels = [rng.integers(0, 182, s).astype(np.uint8) for s in shapes]
+    return imgs, labels
+  imgs, labels = content([(H, W)] * B)
+  uni = sa.SegPairedAugmenter(torch.from_numpy(np.stack(imgs)).to(dev), cfg(),
+                              labels_u8=torch.from_numpy(np.stack(labels)).to(dev), relevance=rel, seed=1)
+  rag = sr.SegRaggedAugmenter(imgs, cfg(), labels=labels, relevance=rel, seed=1, device=dev)
+  # around 213 x 160, landscape and portrait, some sides below input_sz (padded)
+  shapes = [(int(h), int(w)) for h, w in zip(rng.integers(110, 215, B), rng.integers(110, 260, B))]
+  mimgs, mlabels = content(shapes)
+  mixed = sr.SegRaggedAugmenter(mimgs, cfg(), labels=mlabels, relevance=rel, seed=1, device=dev)
+  scaled = sr.SegRaggedAugmenter(mimgs, cfg(True), labels=mlabels, relevance=rel, seed=1, device=dev)
+  idx = np.random.default_rng(5).integers(0, B, batch)
+  p = uni.draw(idx)
+  pr = dict(p, scale=None)
+  pm, ps = mixed.draw(idx), scaled.draw(idx)
+  for x, y in zip(uni.apply(p), rag.apply(pr)):      # faster and different is not faster
+    assert x.cpu().numpy().tobytes() == y.cpu().numpy().tobytes(), "ragged kernel differs from iic_seg_augment"
+  C = uni.out_channels
+  outs = (torch.empty(batch, C, S, S, device=dev), torch.empty(batch, C, S, S, device=dev),
+          torch.empty(batch, S, S, device=dev, dtype=torch.uint8), torch.empty(batch, 2, 3, device=dev))
+
+  def resident(params):
+    return (torch.from_numpy(np.ascontiguousarray(params["iparams"])).to(dev),
+            torch.from_numpy(np.ascontiguousarray(params["fparams"])).to(dev))
+
+  def uniform_kernel(ipfp):
+    ip, fp = ipfp
+    return lambda: _lib.check(L.iic_seg_augment(
+      uni.images.data_ptr(), uni.B, uni.H, uni.W, uni.Cs, uni.labels.data_ptr(), uni.relevance.data_ptr(), ip.data_ptr(),
+      fp.data_ptr(), batch, S, 0, 1, uni.lut.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+      outs[3].data_ptr(), _lib.stream_ptr()), "iic_seg_augment")
+
+  def ragged_kernel(aug, ipfp, taps=None):
+    ip, fp = ipfp
+    return lambda: _lib.check(L.iic_seg_augment_ragged(
+      aug.images.data_ptr(), aug.offsets.data_ptr(), aug.sizes.data_ptr(), aug.B, aug.total, aug.Cs,
+      aug.labels.data_ptr(), aug.relevance.data_ptr(), ip.data_ptr(), fp.data_ptr(), _lib.ptr(taps), batch, S, 0, 1,
+      aug.lut.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(),
+      _lib.stream_ptr()), "iic_seg_augment_ragged")
+  src = scaled.sizes_host[ps["iparams"][:, 0]]
+  t = np.stack([sr.crop_taps(src[:, 0], ps["scale"], ps["iparams"][:, 2], S),
+                sr.crop_taps(src[:, 1], ps["scale"], ps["iparams"][:, 1], S)], 1)
+  taps = torch.from_numpy(np.ascontiguousarray(t).view(np.int32).reshape(batch, 2, S, 6)).to(dev)
+  kern_bytes = batch * (S * S * (3 + 1) + 2 * C * S * S * 4 + S * S + 24)
+  variants = [
+    ("kernel", {"uniform iic_seg_augment": uniform_kernel(resident(p)),
+                "ragged, uniform data": ragged_kernel(rag, resident(pr)),
+                "ragged, mixed sizes": ragged_kernel(mixed, resident(pm)),
+                "ragged, mixed + random scale": ragged_kernel(scaled, resident(ps), taps)}),
+    ("apply", {"uniform iic_seg_augment": lambda: uni.apply(p),
+               "ragged, uniform data": lambda: rag.apply(pr),
+               "ragged, mixed sizes": lambda: mixed.apply(pm),
+               "ragged, mixed + random scale": lambda: scaled.apply(ps)}),
+  ]
+  print("COCO-Stuff-3 shape: batch %d, input_sz %d, C %d, %d resident images; uniform %d x %d; mixed %d..%d x %d..%d; "
+        "%d windows of %d calls per variant, interleaved: median (min, max) per call"
+        % (batch, S, C, B, H, W, min(s[0] for s in shapes), max(s[0] for s in shapes), min(s[1] for s in shapes),
+           max(s[1] for s in shapes), a.repeats, a.iters))
+  rows = []
+  for what, fns in variants:
+    iters = a.iters if what == "kernel" else max(1, a.iters // 10)
+    res = interleaved(fns, iters, a.repeats)
+    base = res["uniform iic_seg_augment"][0]
+    for k, (med, lo, hi) in res.items():
+      rows.append(dict(what=what, variant=k, ms=med, min_ms=lo, max_ms=hi, ratio_to_uniform=med / base,
+                       GBps_algorithmic=kern_bytes / med / 1e6))
+      print("%-6s %-30s %.4f ms (min %.4f max %.4f)  x%.3f of uniform  %.0f GB/s algorithmic"
+            % (what, k, med, lo, hi, med / base, kern_bytes / med / 1e6), flush=True)
+  t0 = time.perf_counter()
+  for _ in range(20):
+    scaled.draw(idx)
+  print("host: draw with random scale %.3f ms per batch of %d" % ((time.perf_counter() - t0) / 20 * 1e3, batch))
+  print(json.dumps(rows))
+
+
 def main():
   ap = argparse.ArgumentParser()
-  ap.add_argument("--iters", type=int, default=50)
-  ap.add_argument("--repeats", type=int, default=7)
+  ap.add_argument("--iters", type=int, default=None)
+  ap.add_argument("--repeats", type=int, default=None)
   ap.add_argument("--host-batches", type=int, default=2)
+  ap.add_argument("--ragged", action="store_true")
   a = ap.parse_args()
   assert torch.cuda.is_available(), "seg_augment_perf needs a GPU"
   torch.set_num_threads(1)
+  if a.ragged:
+    a.iters, a.repeats = a.iters or 1000, a.repeats or 9
+    return ragged_mode(a)
+  a.iters, a.repeats = a.iters or 50, a.repeats or 7
   rows = []
   for case in REAL:
     name, batch = case[0], case[1]
