@@ -6,7 +6,7 @@ implemented on hand-written HIP kernels behind the C ABI of ``libiic_hip.so``
 (include/iic_hip.h).  ``iic_amd.install.install()`` registers them under the reference's
 module names so its training scripts import them unchanged.
 
-Submodules: losses, seg_losses, transforms, archs, optim, dist, install, geom, ops, branches, pool, augment, seg_augment, seg_ragged, _lib.
+Submodules: losses, seg_losses, transforms, archs, optim, dist, install, geom, ops, branches, pool, augment, seg_augment, seg_ragged, seg_prescale, _lib.
 """
 import importlib
 
@@ -17,6 +17,7 @@ _LAZY = {
   "Adam": ("optim", "Adam"),
   "SegPairedAugmenter": ("seg_augment", "SegPairedAugmenter"),
   "SegRaggedAugmenter": ("seg_ragged", "SegRaggedAugmenter"),
+  "prescale_dataset": ("seg_prescale", "prescale_dataset"),
   "seg_paired_dataloaders": ("seg_augment", "seg_paired_dataloaders"),
   "SegTestPreparer": ("seg_augment", "SegTestPreparer"),
   "seg_mapping_dataloader": ("seg_augment", "seg_mapping_dataloader"),

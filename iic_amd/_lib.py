@@ -91,6 +91,9 @@ _SIGNATURES = {
                               _P, _P]),
   "iic_seg_augment_ragged": (c_int, [_P, _P, _P, c_int, c_long, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P,
                                      _P, _P, _P, _P, _P]),
+  "iic_seg_augment_ragged_prescaled": (c_int, [_P, _P, _P, c_int, c_long, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int,
+                                               c_int, _P, _P, _P, _P, _P, _P]),
+  "iic_seg_prescale": (c_int, [_P, _P, _P, _P, c_int, c_long, c_double, _P, _P, _P, _P, _P, c_long, _P, c_int, _P]),
   "iic_seg_augment_warp": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
   "iic_seg_prepare_test": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P,
                                    _P, _P, _P]),

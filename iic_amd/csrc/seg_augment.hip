@@ -36,9 +36,11 @@
 //
 // seg_augment_ragged_kernel (between the two) is the training kernel for a dataset whose images differ in size
 // (COCO-Stuff): images packed without padding, every sample padded and cropped by its own extent, optionally resampled
-// through host-built tables (use_random_scale); it shares seg_load, seg_grey, seg_jitter and seg_pad_offset.
+// through host-built tables (use_random_scale; or, from the original-resolution images, pre_scale_all followed by
+// use_random_scale as two resampling stages); it shares seg_load, seg_grey, seg_jitter and seg_pad_offset.
 #include "common.h"
 #include "aug_jitter.h"
+#include "seg_resample.h"
 #include "../../include/iic_hip.h"
 
 #pragma clang fp contract(off)
@@ -206,75 +208,110 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_augment_kernel(
 // ---- datasets whose images differ in size (COCO-Stuff), optionally with use_random_scale: the packed twin of
 // seg_augment_kernel.  Image i is h_i x w_i x CS at pixel offset offsets[i] of one packed array, row pitch w_i; pad
 // offsets and the inside test come from the sample's own extent (cocostuff.py:133-135 over transforms.py:23-88).
-// SCALED (cocostuff.py:123-130, potsdam.py:109-114): every crop row and column carries a host-built resampling tap
+// RS = 1 (cocostuff.py:123-130, potsdam.py:109-114): every crop row and column carries a host-built resampling tap
 // (iic_seg_resample_tap: OpenCV 3.x's INTER_LINEAR coefficients for the float image, INTER_NEAREST's index for the
 // label); the kernel only multiplies and adds, in cv2's order (horizontal pass, then vertical), each operation rounded
-// to float32 on its own, and truncates RGB to uint8 as `img.astype(np.uint8)` does after the crop.  Without SCALED no
+// to float32 on its own, and truncates RGB to uint8 as `img.astype(np.uint8)` does after the crop.  With RS = 0 no
 // tap is read.
+// RS = 2 (pre_scale_all, then use_random_scale, on the ORIGINAL images: cocostuff.py:113-130, potsdam.py:103-114): the
+// reference resizes twice and never truncates in between.  Every crop row and column carries the two taps of the second
+// resize on the pre-scaled side and, for each of them, the two taps of the first resize on the source side
+// (iic_seg_resample_tap2); the four intermediate pixels are computed as above, kept in float32, and combined by the
+// same formula with the second stage's weights.  RS = 0 is no resampling, RS = 1 the single stage.
 struct seg_ragged_src {
   const uint8_t* im;             // nullptr: a black image
   const uint8_t* lb;             // nullptr: no labels, or a black image
   int h, w;                      // the stored extent; w is the row pitch
-  int x0, y0;                    // crop origin in source coordinates (not SCALED)
-  const iic_seg_resample_tap* ty;   // S row taps, then S column taps (SCALED)
+  int x0, y0;                    // crop origin in source coordinates (RS = 0)
+  const iic_seg_resample_tap* ty;   // S row taps, then S column taps (RS = 1)
   const iic_seg_resample_tap* tx;
+  const iic_seg_resample_tap2* ty2;  // the same for the two-stage tables (RS = 2)
+  const iic_seg_resample_tap2* tx2;
 };
 
 __device__ __forceinline__ int seg_clamp_index(int i, int len) { return i < 0 ? 0 : (i >= len ? len - 1 : i); }
 
-// (a * wa + b * wb), every operation rounded to float32 (contraction is off in this file)
-__device__ __forceinline__ float seg_lerp(float a, float wa, float b, float wb) { return a * wa + b * wb; }
-
-__device__ __forceinline__ int seg_trunc_u8(float v) {
-  const int i = (int)v;          // toward zero, as astype(np.uint8) of a value in [0, 256)
-  return i < 0 ? 0 : (i > 255 ? 255 : i);
+// cv2's INTER_LINEAR pixel on the uint8 source: (p00 ax0 + p01 ax1) by0 + (p10 ax0 + p11 ax1) by1 per channel, every
+// operation rounded to float32 (seg_lerp; contraction is off in this file).  Indices are clamped to the image.
+template <int CS>
+__device__ __forceinline__ void seg_bilinear(const seg_ragged_src& s, int y0, int y1, int x0, int x1, float ax0,
+                                             float ax1, float by0, float by1, float v[4]) {
+  const int ya = seg_clamp_index(y0, s.h), yb = seg_clamp_index(y1, s.h);
+  const int xa = seg_clamp_index(x0, s.w), xb = seg_clamp_index(x1, s.w);
+  int p00[4], p01[4], p10[4], p11[4];
+  seg_load<CS>(s.im, ya, xa, s.h, s.w, p00[0], p00[1], p00[2], p00[3]);
+  seg_load<CS>(s.im, ya, xb, s.h, s.w, p01[0], p01[1], p01[2], p01[3]);
+  seg_load<CS>(s.im, yb, xa, s.h, s.w, p10[0], p10[1], p10[2], p10[3]);
+  seg_load<CS>(s.im, yb, xb, s.h, s.w, p11[0], p11[1], p11[2], p11[3]);
+#pragma unroll
+  for (int c = 0; c < CS; ++c) {
+    const float top = seg_lerp((float)p00[c], ax0, (float)p01[c], ax1);
+    const float bot = seg_lerp((float)p10[c], ax0, (float)p11[c], ax1);
+    v[c] = seg_lerp(top, by0, bot, by1);
+  }
 }
 
-// one pixel of the crop at (y, x): r, g, b, ir and the fine label l (0 in the padding).  SCALED: irf is the resampled
+// one pixel of the crop at (y, x): r, g, b, ir and the fine label l (0 in the padding).  RS != 0: irf is the resampled
 // IR value BEFORE truncation -- the reference truncates only the RGB part it hands to PIL (potsdam.py:148-151), IR goes
 // on as the float image / 255. (potsdam.py:170)
-template <int CS, bool SCALED>
+template <int CS, int RS>
 __device__ __forceinline__ void seg_ragged_fetch(const seg_ragged_src& s, int y, int x, bool want_label, int& r, int& g,
                                                  int& b, int& ir, float& irf, int& l) {
   l = 0;
   irf = 0.f;
-  if (!SCALED) {
+  if (RS == 0) {
     const int sy = s.y0 + y, sx = s.x0 + x;
     seg_load<CS>(s.im, sy, sx, s.h, s.w, r, g, b, ir);
     if (want_label && s.lb != nullptr && sy >= 0 && sy < s.h && sx >= 0 && sx < s.w) l = s.lb[(long)sy * s.w + sx];
-  } else {
+  } else if (RS == 1) {
     r = g = b = ir = 0;
     const iic_seg_resample_tap ty = s.ty[y], tx = s.tx[x];
     if (s.im == nullptr || !ty.inside || !tx.inside) return;
-    const int ya = seg_clamp_index(ty.i0, s.h), yb = seg_clamp_index(ty.i1, s.h);
-    const int xa = seg_clamp_index(tx.i0, s.w), xb = seg_clamp_index(tx.i1, s.w);
-    int p00[4], p01[4], p10[4], p11[4];
-    seg_load<CS>(s.im, ya, xa, s.h, s.w, p00[0], p00[1], p00[2], p00[3]);
-    seg_load<CS>(s.im, ya, xb, s.h, s.w, p01[0], p01[1], p01[2], p01[3]);
-    seg_load<CS>(s.im, yb, xa, s.h, s.w, p10[0], p10[1], p10[2], p10[3]);
-    seg_load<CS>(s.im, yb, xb, s.h, s.w, p11[0], p11[1], p11[2], p11[3]);
-    int out[4] = {0, 0, 0, 0};
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    seg_bilinear<CS>(s, ty.i0, ty.i1, tx.i0, tx.i1, tx.a0, tx.a1, ty.a0, ty.a1, v);
+    r = seg_trunc_u8(v[0]); g = seg_trunc_u8(v[1]); b = seg_trunc_u8(v[2]);
+    if (CS == 4) {
+      ir = seg_trunc_u8(v[3]);
+      irf = v[3];
+    }
+    if (want_label && s.lb != nullptr)
+      l = s.lb[(long)seg_clamp_index(ty.nearest, s.h) * s.w + seg_clamp_index(tx.nearest, s.w)];
+  } else {
+    r = g = b = ir = 0;
+    const iic_seg_resample_tap2 ty = s.ty2[y], tx = s.tx2[x];
+    if (s.im == nullptr || !ty.inside || !tx.inside) return;
+    float m[2][2][4];              // the pre-scaled image at the second stage's four taps, untruncated
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        m[i][j][3] = 0.f;
+        seg_bilinear<CS>(s, ty.i0[i], ty.i1[i], tx.i0[j], tx.i1[j], tx.a0[j], tx.a1[j], ty.a0[i], ty.a1[i], m[i][j]);
+      }
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < CS; ++c) {
-      const float top = seg_lerp((float)p00[c], tx.a0, (float)p01[c], tx.a1);
-      const float bot = seg_lerp((float)p10[c], tx.a0, (float)p11[c], tx.a1);
-      const float v = seg_lerp(top, ty.a0, bot, ty.a1);
-      out[c] = seg_trunc_u8(v);
-      if (c == 3) irf = v;
+      const float top = seg_lerp(m[0][0][c], tx.b0, m[0][1][c], tx.b1);
+      const float bot = seg_lerp(m[1][0][c], tx.b0, m[1][1][c], tx.b1);
+      v[c] = seg_lerp(top, ty.b0, bot, ty.b1);
     }
-    r = out[0]; g = out[1]; b = out[2]; ir = out[3];
+    r = seg_trunc_u8(v[0]); g = seg_trunc_u8(v[1]); b = seg_trunc_u8(v[2]);
+    if (CS == 4) {
+      ir = seg_trunc_u8(v[3]);
+      irf = v[3];
+    }
     if (want_label && s.lb != nullptr)
       l = s.lb[(long)seg_clamp_index(ty.nearest, s.h) * s.w + seg_clamp_index(tx.nearest, s.w)];
   }
 }
 
 // MODE as above.  One workgroup per sample, a thread per four consecutive output x of one row, as seg_augment_kernel.
-template <int CS, int MODE, bool SCALED>
+template <int CS, int MODE, int RS>
 __global__ __launch_bounds__(SEG_THREADS) void seg_augment_ragged_kernel(
     const uint8_t* __restrict__ imgs, const uint8_t* __restrict__ labels, const uint8_t* __restrict__ table,
     const long* __restrict__ offsets, const int* __restrict__ sizes, int B, long total_px,
     const int* __restrict__ iparams, const float* __restrict__ fparams, const iic_seg_resample_tap* __restrict__ taps,
-    int S, const float* __restrict__ lut, float* __restrict__ img1, float* __restrict__ img2, uint8_t* __restrict__ mask,
+    const iic_seg_resample_tap2* __restrict__ taps2, int S, const float* __restrict__ lut, float* __restrict__ img1, float* __restrict__ img2, uint8_t* __restrict__ mask,
     float* __restrict__ aff) {
   __shared__ int s_red[SEG_THREADS / 64];
   constexpr int C = (MODE == 0 ? 3 : (MODE == 1 ? 4 : 1)) + (CS == 4 ? 1 : 0);
@@ -289,7 +326,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_augment_ragged_kernel(
   const int hdelta = ip[9] & 255;
   const float f_b = fp[0], f_c = fp[1], f_s = fp[2];
   // an index outside the dataset, or an image whose extent or offset would leave the pack, reads as a black image
-  seg_ragged_src s = {nullptr, nullptr, 1, 1, 0, 0, nullptr, nullptr};
+  seg_ragged_src s = {nullptr, nullptr, 1, 1, 0, 0, nullptr, nullptr, nullptr, nullptr};
   if (src >= 0 && src < B) {
     const int h = sizes[2 * src], w = sizes[2 * src + 1];
     const long off = offsets[src];
@@ -301,9 +338,12 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_augment_ragged_kernel(
       s.y0 = ip[2] - seg_pad_offset(h, S);
     }
   }
-  if (SCALED) {
+  if (RS == 1) {
     s.ty = taps + (long)n * 2 * S;
     s.tx = s.ty + S;
+  } else if (RS == 2) {
+    s.ty2 = taps2 + (long)n * 2 * S;
+    s.tx2 = s.ty2 + S;
   }
   const int Q = S >> 2, nquads = S * Q;
 
@@ -326,7 +366,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_augment_ragged_kernel(
       for (int j = 0; j < 4; ++j) {
         int r, g, b, ir, l;
         float irf;
-        seg_ragged_fetch<CS, SCALED>(s, y, xq + j, false, r, g, b, ir, irf, l);
+        seg_ragged_fetch<CS, RS>(s, y, xq + j, false, r, g, b, ir, irf, l);
         seg_jitter(r, g, b, opsw, 0, cpos, f_b, f_c, f_s, 0, hdelta);
         part += aug_luma(r, g, b);
       }
@@ -355,7 +395,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_augment_ragged_kernel(
     for (int j = 0; j < 4; ++j) {
       int r, g, b, ir, l;
       float irf;
-      seg_ragged_fetch<CS, SCALED>(s, y, xq + j, labels != nullptr, r, g, b, ir, irf, l);
+      seg_ragged_fetch<CS, RS>(s, y, xq + j, labels != nullptr, r, g, b, ir, irf, l);
       const int m = labels != nullptr ? (int)table[l] : 1;
       mk |= (uint32_t)(m & 255) << (8 * j);
       int r2 = r, g2 = g, b2 = b;
@@ -369,7 +409,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_augment_ragged_kernel(
         v2[CG][j] = lut[seg_grey(r2, g2, b2)];
       }
       if (CS == 4) {
-        const float vir = SCALED ? irf / 255.f : lut[ir];
+        const float vir = RS != 0 ? irf / 255.f : lut[ir];
         v1[C - 1][j] = vir;
         v2[C - 1][j] = vir;
       }
@@ -557,11 +597,12 @@ int iic_seg_augment(const void* imgs_u8, int B, int H, int W, int Cs, const void
   return iic_launch_status();
 }
 
-int iic_seg_augment_ragged(const void* imgs_u8, const long* offsets, const int* sizes, int B, long total_px, int Cs,
-                           const void* labels_u8, const void* relevance, const int* iparams, const float* fparams,
-                           const iic_seg_resample_tap* taps, int N, int S, int no_sobel, int include_rgb,
-                           const float* lut, float* img1, float* img2, void* mask_img1, float* affine2_to_1,
-                           void* stream) {
+// the three resampling flavours of seg_augment_ragged_kernel: no table, iic_seg_resample_tap, iic_seg_resample_tap2
+static int seg_ragged_launch(const void* imgs_u8, const long* offsets, const int* sizes, int B, long total_px, int Cs,
+                             const void* labels_u8, const void* relevance, const int* iparams, const float* fparams,
+                             const iic_seg_resample_tap* taps, const iic_seg_resample_tap2* taps2, int N, int S,
+                             int no_sobel, int include_rgb, const float* lut, float* img1, float* img2,
+                             void* mask_img1, float* affine2_to_1, void* stream) {
   if (!imgs_u8 || !offsets || !sizes || !iparams || !fparams || !lut || !img1 || !img2 || !mask_img1 || !affine2_to_1)
     return IIC_ERR_ARG;
   if (B <= 0 || N <= 0 || S <= 0 || total_px <= 0) return IIC_ERR_ARG;
@@ -570,27 +611,49 @@ int iic_seg_augment_ragged(const void* imgs_u8, const long* offsets, const int* 
   if (S % 4 != 0 || S > 4096) return IIC_ERR_UNSUPPORTED;
   const int mode = no_sobel ? 0 : (include_rgb ? 1 : 2);
   hipStream_t s = (hipStream_t)stream;
-#define SEG_LAUNCH(CS_, MODE_, SCALED_)                                                                        \
-  hipLaunchKernelGGL((seg_augment_ragged_kernel<CS_, MODE_, SCALED_>), dim3(N), dim3(SEG_THREADS), 0, s,       \
+#define SEG_LAUNCH(CS_, MODE_, RS_)                                                                            \
+  hipLaunchKernelGGL((seg_augment_ragged_kernel<CS_, MODE_, RS_>), dim3(N), dim3(SEG_THREADS), 0, s,           \
                      (const uint8_t*)imgs_u8, (const uint8_t*)labels_u8, (const uint8_t*)relevance, offsets,   \
-                     sizes, B, total_px, iparams, fparams, taps, S, lut, img1, img2, (uint8_t*)mask_img1,      \
-                     affine2_to_1)
-#define SEG_LAUNCH_MODE(CS_, SCALED_)          \
+                     sizes, B, total_px, iparams, fparams, taps, taps2, S, lut, img1, img2,                    \
+                     (uint8_t*)mask_img1, affine2_to_1)
+#define SEG_LAUNCH_MODE(CS_, RS_)              \
   do {                                         \
-    if (mode == 0) SEG_LAUNCH(CS_, 0, SCALED_); \
-    else if (mode == 1) SEG_LAUNCH(CS_, 1, SCALED_); \
-    else SEG_LAUNCH(CS_, 2, SCALED_);          \
+    if (mode == 0) SEG_LAUNCH(CS_, 0, RS_);    \
+    else if (mode == 1) SEG_LAUNCH(CS_, 1, RS_); \
+    else SEG_LAUNCH(CS_, 2, RS_);              \
   } while (0)
-  if (taps == nullptr) {
-    if (Cs == 3) SEG_LAUNCH_MODE(3, false);
-    else SEG_LAUNCH_MODE(4, false);
+  if (taps2 != nullptr) {
+    if (Cs == 3) SEG_LAUNCH_MODE(3, 2);
+    else SEG_LAUNCH_MODE(4, 2);
+  } else if (taps == nullptr) {
+    if (Cs == 3) SEG_LAUNCH_MODE(3, 0);
+    else SEG_LAUNCH_MODE(4, 0);
   } else {
-    if (Cs == 3) SEG_LAUNCH_MODE(3, true);
-    else SEG_LAUNCH_MODE(4, true);
+    if (Cs == 3) SEG_LAUNCH_MODE(3, 1);
+    else SEG_LAUNCH_MODE(4, 1);
   }
 #undef SEG_LAUNCH_MODE
 #undef SEG_LAUNCH
   return iic_launch_status();
+}
+
+int iic_seg_augment_ragged(const void* imgs_u8, const long* offsets, const int* sizes, int B, long total_px, int Cs,
+                           const void* labels_u8, const void* relevance, const int* iparams, const float* fparams,
+                           const iic_seg_resample_tap* taps, int N, int S, int no_sobel, int include_rgb,
+                           const float* lut, float* img1, float* img2, void* mask_img1, float* affine2_to_1,
+                           void* stream) {
+  return seg_ragged_launch(imgs_u8, offsets, sizes, B, total_px, Cs, labels_u8, relevance, iparams, fparams, taps,
+                           nullptr, N, S, no_sobel, include_rgb, lut, img1, img2, mask_img1, affine2_to_1, stream);
+}
+
+int iic_seg_augment_ragged_prescaled(const void* imgs_u8, const long* offsets, const int* sizes, int B, long total_px,
+                                     int Cs, const void* labels_u8, const void* relevance, const int* iparams,
+                                     const float* fparams, const iic_seg_resample_tap2* taps2, int N, int S,
+                                     int no_sobel, int include_rgb, const float* lut, float* img1, float* img2,
+                                     void* mask_img1, float* affine2_to_1, void* stream) {
+  if (!taps2) return IIC_ERR_ARG;
+  return seg_ragged_launch(imgs_u8, offsets, sizes, B, total_px, Cs, labels_u8, relevance, iparams, fparams, nullptr,
+                           taps2, N, S, no_sobel, include_rgb, lut, img1, img2, mask_img1, affine2_to_1, stream);
 }
 
 int iic_seg_augment_warp(const float* img2, const float* affine1_to_2, const int* flips, const float* base_grid,

@@ -22,6 +22,14 @@ NOT compared against a cv2 binary -- cv2 is not available where this is built an
 conversion of seg_augment.  All coefficient arithmetic happens here on the host: `apply` hands the kernel, per sample,
 the taps of the S crop rows and S crop columns, and the kernel multiplies and adds.
 
+pre_scale_all (cocostuff.py:113-120, potsdam.py:103-106) comes in two forms.  source="resident" (the default): the
+resident pack holds the PRE-SCALED, truncated images -- seg_prescale.prescale_dataset makes it on the device -- and the
+flag changes nothing here; use_random_scale cannot be combined with it, because the reference resizes the untruncated
+float image a second time.  source="original": the resident pack holds the original-resolution images and every
+sample is pre-scaled inside the kernel: without use_random_scale that is the resampling above with scale =
+pre_scale_factor; with it, `crop_taps2` composes the taps of both resizes and iic_seg_augment_ragged_prescaled keeps the
+intermediate image in float32 (sixteen source pixels per output pixel).  Cs = 4 is served by source="original" only.
+
 use_random_affine: img2 is warped by iic_seg_augment_warp, F.affine_grid + F.grid_sample + flip in the operation order of
 torch's CPU kernels (`grid_warp_host` is its host restatement), so that img2 equals the reference's bit for bit; the
 uniform augmenter's iic_affine_warp_fwd computes the same warp within 2e-6.
@@ -33,8 +41,12 @@ from . import _lib
 from .seg_augment import FPARAMS, IPARAMS, _SegDraws, _flag, crop_centre_range, pad_offsets
 
 MAX_SIDE = 16384
+SOURCES = ("resident", "original")
 # iic_seg_resample_tap (include/iic_hip.h)
 TAP_DTYPE = np.dtype([("i0", "<i4"), ("i1", "<i4"), ("a0", "<f4"), ("a1", "<f4"), ("nearest", "<i4"), ("inside", "<i4")])
+# iic_seg_resample_tap2: [k] = the first resize's taps that produce the second resize's tap k
+TAP2_DTYPE = np.dtype([("i0", "<i4", (2,)), ("i1", "<i4", (2,)), ("a0", "<f4", (2,)), ("a1", "<f4", (2,)),
+                       ("b0", "<f4"), ("b1", "<f4"), ("nearest", "<i4"), ("inside", "<i4")])
 
 
 # ------------------------------------------------------------------------------------------
@@ -111,6 +123,30 @@ def crop_taps(src_len, scale, origin, S):
   t = np.zeros(d.shape, TAP_DTYPE)
   t["i0"], t["i1"], t["a0"], t["a1"] = linear_taps(src_len, scale, d)
   t["nearest"] = nearest_index(src_len, scale, d)
+  t["inside"] = inside
+  return t
+
+
+def crop_taps2(src_len, factor, scale, origin, S):
+  """crop_taps for two resizes in a row -- by `factor` (pre_scale_all), then by `scale` (use_random_scale) -- of a side
+  of src_len pixels, TAP2_DTYPE [n, S]: the second resize's two taps and weights (b0, b1) on the pre-scaled side and,
+  for each of the two, the first resize's taps on the source side; nearest of nearest for the label.  factor: one
+  float; src_len int [n], scale float64 [n], origin int [n]: the crop origin in the padded twice-scaled side."""
+  src_len = np.asarray(src_len, np.int64).reshape(-1, 1)
+  scale = np.asarray(scale, np.float64).reshape(-1, 1)
+  factor = np.float64(factor)
+  mid_len = scaled_len(src_len, factor)
+  dst_len = scaled_len(mid_len, scale)
+  pad = np.maximum(dst_len, S) // 2 - dst_len // 2
+  d = np.asarray(origin, np.int64).reshape(-1, 1) + np.arange(S)[None, :] - pad
+  inside = (d >= 0) & (d < dst_len)
+  d = np.clip(d, 0, dst_len - 1)
+  t = np.zeros(d.shape, TAP2_DTYPE)
+  m0, m1, t["b0"], t["b1"] = linear_taps(mid_len, scale, d)
+  for k, m in enumerate((m0, m1)):
+    i0, i1, a0, a1 = linear_taps(src_len, factor, m)
+    t["i0"][..., k], t["i1"][..., k], t["a0"][..., k], t["a1"][..., k] = i0, i1, a0, a1
+  t["nearest"] = nearest_index(src_len, factor, nearest_index(mid_len, scale, d))
   t["inside"] = inside
   return t
 
@@ -197,6 +233,33 @@ def _host(t):
   return np.asarray(t.cpu() if torch.is_tensor(t) else t)
 
 
+def check_pack(total, sizes, offsets=None):
+  """sizes and offsets of a pack of `total` pixels as int64 arrays ([B, 2], [B]), or the ValueError that names what is
+  wrong with them.  offsets None: the images back to back."""
+  sz = _host(sizes)
+  if sz.dtype.kind not in "iu" or sz.ndim != 2 or sz.shape[1] != 2 or sz.shape[0] < 1:
+    raise ValueError("sizes: must be an integer array [B, 2], one (h, w) per image")
+  sz = sz.astype(np.int64)
+  if (sz < 1).any() or (sz > MAX_SIDE).any():
+    raise ValueError("sizes: every h and w must lie within 1..%d" % MAX_SIDE)
+  B = int(sz.shape[0])
+  area = sz[:, 0] * sz[:, 1]
+  if offsets is None:
+    off = np.concatenate([[0], np.cumsum(area)[:-1]]).astype(np.int64)
+  else:
+    off = _host(offsets)
+    if off.dtype.kind not in "iu" or off.shape != (B,):
+      raise ValueError("offsets: must be an integer array [%d], the pixel offset of every image" % B)
+    off = off.astype(np.int64)
+  if (off < 0).any() or (off + area > total).any():
+    raise ValueError("offsets: image %d leaves the packed array of %d pixels"
+                     % (int(np.argmax((off < 0) | (off + area > total))), total))
+  order = np.argsort(off, kind="stable")
+  if (off[order][1:] < (off + area)[order][:-1]).any():
+    raise ValueError("offsets: images overlap -- offsets are not consistent with sizes")
+  return sz, off
+
+
 class SegRaggedAugmenter(_SegDraws):
   """images: a list of uint8 [h_i, w_i, Cs] arrays (packed and uploaded to `device`, with labels: the list of uint8
   [h_i, w_i] fine-label maps, 255 for -1), OR the packed uint8 [total, Cs] tensor already on the device, with sizes
@@ -210,20 +273,36 @@ class SegRaggedAugmenter(_SegDraws):
   image a second time, which a resident uint8 image cannot reproduce; pre_scale_all with prescaled=False; input_sz
   not a multiple of 4.  mask_input is asserted false (cocostuff.py:63).
 
+  source="original": the resident pack holds the ORIGINAL-resolution images, and pre_scale_all / pre_scale_factor are
+  honoured inside the kernel, with or without use_random_scale (the module docstring says how); ValueError without
+  pre_scale_all or with a factor outside (0, 1) (cocostuff.py:114).  The default, source="resident", is described above.
+
   draw(idx) -> params: SegPairedAugmenter's dictionary, the crop origin in each sample's own padded (scaled) image,
-  plus scale float64 [n] (None without use_random_scale) and extent int [n, 2], the (h, w) the crop was drawn on.
+  plus scale float64 [n] (None without use_random_scale) and extent int [n, 2], the (h, w) the crop was drawn on
+  (source="original": cvRound(len * pre_scale_factor) per side, then cvRound(that * scale)).
   Per sample the reference's order: [scale], crop centre h then w, jitter, [random_affine's three], flip.
   apply(params) -> (img1, img2, affine2_to_1, mask_img1); paired_batch(idx) = both."""
 
   def __init__(self, images, config, labels=None, relevance=None, sizes=None, offsets=None, seed=0, prescaled=True,
-               device=None):
+               device=None, source="resident"):
     assert not _flag(config, "mask_input"), "mask_input is not built (cocostuff.py:63 asserts it false)"
+    if source not in SOURCES:
+      raise ValueError("source: %r, expected one of %s" % (source, ", ".join(repr(v) for v in SOURCES)))
     self.use_random_scale = bool(_flag(config, "use_random_scale"))
-    if _flag(config, "pre_scale_all") and self.use_random_scale:
+    self.pre_factor = None
+    if source == "original":
+      if not _flag(config, "pre_scale_all"):
+        raise ValueError("source='original' is for pre_scale_all: without the flag the resident images are the ones "
+                         "the crop is cut from (source='resident')")
+      self.pre_factor = float(config.pre_scale_factor)
+      if not 0 < self.pre_factor < 1:
+        raise ValueError("pre_scale_factor: %r, must lie within (0, 1) (cocostuff.py:114 asserts < 1.)"
+                         % (config.pre_scale_factor,))
+    elif _flag(config, "pre_scale_all") and self.use_random_scale:
       raise NotImplementedError("pre_scale_all with use_random_scale is not built: the reference resizes the untruncated "
                                 "float image a second time, which the resident uint8 (pre-scaled, truncated) image "
                                 "cannot reproduce")
-    if _flag(config, "pre_scale_all") and not prescaled:
+    if source == "resident" and _flag(config, "pre_scale_all") and not prescaled:
       raise NotImplementedError("pre_scale_all inside the kernel is not built: keep the pre-scaled, truncated "
                                 "images (labels: NEAREST) resident and pass those")
     self.S = int(config.input_sz)
@@ -249,28 +328,11 @@ class SegRaggedAugmenter(_SegDraws):
                        % (tuple(images.shape),))
     self.images = images
     self.total, self.Cs = int(images.shape[0]), int(images.shape[1])
-    sz = _host(sizes)
-    if sz.dtype.kind not in "iu" or sz.ndim != 2 or sz.shape[1] != 2 or sz.shape[0] < 1:
-      raise ValueError("sizes: must be an integer array [B, 2], one (h, w) per image")
-    sz = sz.astype(np.int64)
-    if (sz < 1).any() or (sz > MAX_SIDE).any():
-      raise ValueError("sizes: every h and w must lie within 1..%d" % MAX_SIDE)
+    sz, off = check_pack(self.total, sizes, offsets)
     self.B = int(sz.shape[0])
-    area = sz[:, 0] * sz[:, 1]
-    if offsets is None:
-      off = np.concatenate([[0], np.cumsum(area)[:-1]]).astype(np.int64)
-    else:
-      off = _host(offsets)
-      if off.dtype.kind not in "iu" or off.shape != (self.B,):
-        raise ValueError("offsets: must be an integer array [%d], the pixel offset of every image" % self.B)
-      off = off.astype(np.int64)
-    if (off < 0).any() or (off + area > self.total).any():
-      raise ValueError("offsets: image %d leaves the packed array of %d pixels"
-                       % (int(np.argmax((off < 0) | (off + area > self.total))), self.total))
-    order = np.argsort(off, kind="stable")
-    if (off[order][1:] < (off + area)[order][:-1]).any():
-      raise ValueError("offsets: images overlap -- offsets are not consistent with sizes")
     self.sizes_host, self.offsets_host = sz, off
+    # (h, w) before the random scale: the stored extent, or the pre-scaled one
+    self.base_extent = sz if self.pre_factor is None else scaled_len(sz, self.pre_factor)
     dev = images.device
     self.sizes = torch.from_numpy(sz.astype(np.int32)).to(dev)
     self.offsets = torch.from_numpy(off).to(dev)
@@ -294,8 +356,9 @@ class SegRaggedAugmenter(_SegDraws):
     self.base_grid = (torch.linspace(-1, 1, self.S) * (self.S - 1) / self.S).to(dev)
 
   def extents(self, idx, scale=None):
-    """(h, w) the crop is drawn on, int64 [n, 2]: the image's own, or cvRound(len * scale) per side."""
-    ext = self.sizes_host[np.asarray(idx, np.int64).reshape(-1)]
+    """(h, w) the crop is drawn on, int64 [n, 2]: the image's own (source="original": its pre-scaled extent), or
+    cvRound(len * scale) per side of that."""
+    ext = self.base_extent[np.asarray(idx, np.int64).reshape(-1)]
     return ext if scale is None else scaled_len(ext, np.asarray(scale, np.float64).reshape(-1, 1))
 
   def draw(self, idx):
@@ -315,7 +378,7 @@ class SegRaggedAugmenter(_SegDraws):
     ip[:, 0] = idx
     fp[:, 4], fp[:, 8] = 1.0, 1.0                               # identity affine2_to_1
     for i in range(n):
-      h, w = (int(v) for v in self.sizes_host[idx[i]])
+      h, w = (int(v) for v in self.base_extent[idx[i]])
       if self.use_random_scale:
         scale[i] = r.rand() * (self.scale_max - self.scale_min) + self.scale_min
         h, w = int(scaled_len(h, scale[i])), int(scaled_len(w, scale[i]))
@@ -360,10 +423,15 @@ class SegRaggedAugmenter(_SegDraws):
     if a12 is not None:
       iparams = iparams.copy()
       iparams[:, 3] |= 2                   # the mirror of img2 is folded into the warp below
-    taps = None
-    if scale is not None:
-      src = self.sizes_host[iparams[:, 0]]
-      t = np.stack([crop_taps(src[:, 0], scale, iparams[:, 2], S), crop_taps(src[:, 1], scale, iparams[:, 1], S)], 1)
+    taps = taps2 = None
+    src = self.sizes_host[iparams[:, 0]]
+    if self.pre_factor is not None and scale is not None:         # two resizes: pre_scale_all, then the random scale
+      t = np.stack([crop_taps2(src[:, 0], self.pre_factor, scale, iparams[:, 2], S),
+                    crop_taps2(src[:, 1], self.pre_factor, scale, iparams[:, 1], S)], 1)
+      taps2 = torch.from_numpy(np.ascontiguousarray(t).view(np.int32).reshape(n, 2, S, 12)).to(dev, non_blocking=True)
+    elif self.pre_factor is not None or scale is not None:        # one resize: by pre_scale_factor, or by the random scale
+      one = np.full(n, self.pre_factor, np.float64) if scale is None else scale
+      t = np.stack([crop_taps(src[:, 0], one, iparams[:, 2], S), crop_taps(src[:, 1], one, iparams[:, 1], S)], 1)
       taps = torch.from_numpy(np.ascontiguousarray(t).view(np.int32).reshape(n, 2, S, 6)).to(dev, non_blocking=True)
     ip = torch.from_numpy(iparams).to(dev, non_blocking=True)
     fp = torch.from_numpy(fparams).to(dev, non_blocking=True)
@@ -371,11 +439,13 @@ class SegRaggedAugmenter(_SegDraws):
     img2 = torch.empty(n, C, S, S, device=dev, dtype=torch.float32)
     mask = torch.empty(n, S, S, device=dev, dtype=torch.uint8)
     aff = torch.empty(n, 2, 3, device=dev, dtype=torch.float32)
-    _lib.check(_lib.lib().iic_seg_augment_ragged(
+    entry, name = ((_lib.lib().iic_seg_augment_ragged, "iic_seg_augment_ragged") if taps2 is None else
+                   (_lib.lib().iic_seg_augment_ragged_prescaled, "iic_seg_augment_ragged_prescaled"))
+    _lib.check(entry(
       self.images.data_ptr(), self.offsets.data_ptr(), self.sizes.data_ptr(), self.B, self.total, self.Cs,
-      _lib.ptr(self.labels), _lib.ptr(self.relevance), ip.data_ptr(), fp.data_ptr(), _lib.ptr(taps), n, S,
-      int(self.no_sobel), int(self.include_rgb), self.lut.data_ptr(), img1.data_ptr(), img2.data_ptr(), mask.data_ptr(),
-      aff.data_ptr(), _lib.stream_ptr()), "iic_seg_augment_ragged")
+      _lib.ptr(self.labels), _lib.ptr(self.relevance), ip.data_ptr(), fp.data_ptr(), _lib.ptr(taps if taps2 is None else taps2),
+      n, S, int(self.no_sobel), int(self.include_rgb), self.lut.data_ptr(), img1.data_ptr(), img2.data_ptr(),
+      mask.data_ptr(), aff.data_ptr(), _lib.stream_ptr()), name)
     if a12 is not None:
       img2 = self._grid_warp(img2, a12, iparams[:, 3] & 1)
     return img1, img2, aff, mask

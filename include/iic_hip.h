@@ -617,6 +617,62 @@ int iic_seg_augment_ragged(const void* imgs_u8, const long* offsets, const int* 
                            int include_rgb, const float* lut, float* img1, float* img2, void* mask_img1,
                            float* affine2_to_1, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * iic_seg_augment_ragged on the ORIGINAL-resolution images with pre_scale_all AND use_random_scale: the reference
+ * resizes the float image twice, by pre_scale_factor and then by the drawn scale, and truncates only after the crop
+ * (code/datasets/segmentation/cocostuff.py:113-135, potsdam.py:103-117); the labels go through INTER_NEAREST twice.
+ * A resident pre-scaled uint8 image cannot reproduce that (the truncation in between changes about half of the
+ * final bytes), so this entry reads the originals and composes both stages per output pixel.
+ * Every argument as for iic_seg_augment_ragged, except
+ * taps2      iic_seg_resample_tap2 [N][2][S], required: for sample n the S crop rows, then the S crop columns, of the
+ *            crop in the twice-resized image.  b0, b1: the INTER_LINEAR weights of the SECOND resize, whose two taps
+ *            are indices k = 0, 1 on the pre-scaled side; i0[k], i1[k], a0[k], a1[k]: the two taps of the FIRST
+ *            resize on the source side that produce pre-scaled index k; nearest: the source index of INTER_NEAREST
+ *            applied twice; inside = 0 in the padding.  The kernel computes the four pre-scaled pixels as
+ *            (p00 ax0 + p01 ax1) by0 + (p10 ax0 + p11 ax1) by1 in float32 WITHOUT truncating them, then
+ *            (I00 bx0 + I01 bx1) by0' + (I10 bx0 + I11 bx1) by1' with the second stage's weights, every product and
+ *            sum rounded on its own; R, G, B are truncated to uint8 before the jitter, IR (Cs = 4) leaves as
+ *            value / 255.f untruncated.  Sixteen source pixels per output pixel; indices are clamped to the image.
+ * pre_scale_all WITHOUT use_random_scale needs no entry of its own: it is iic_seg_augment_ragged with the taps of
+ * scale = pre_scale_factor.
+ * ------------------------------------------------------------------------------- */
+typedef struct iic_seg_resample_tap2 {
+  int32_t i0[2], i1[2];
+  float a0[2], a1[2];
+  float b0, b1;
+  int32_t nearest;
+  int32_t inside;
+} iic_seg_resample_tap2;
+int iic_seg_augment_ragged_prescaled(const void* imgs_u8, const long* offsets, const int* sizes, int B,
+                                     long total_px, int Cs, const void* labels_u8, const void* relevance,
+                                     const int* iparams, const float* fparams, const iic_seg_resample_tap2* taps2,
+                                     int N, int S, int no_sobel, int include_rgb, const float* lut, float* img1,
+                                     float* img2, void* mask_img1, float* affine2_to_1, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * pre_scale_all as one pass over a packed dataset -- replaces the resize the reference repeats on every access,
+ *   code/datasets/segmentation/cocostuff.py:113-120, :242-249, :321-328; potsdam.py:103-106
+ * cv2.resize(fx = fy = factor) with INTER_LINEAR on the float image and INTER_NEAREST on the labels (OpenCV 3.x's
+ * resize restated from its source, not compared against a cv2 binary), the image truncated toward zero to uint8 as
+ * `img.astype(np.uint8)` does after the crop.  RGB only (3 bytes per pixel): Potsdam's IR plane is never truncated.
+ * imgs_u8, labels_u8 (or NULL), offsets, sizes, B, total_px: the source pack, as for iic_seg_augment_ragged, Cs = 3.
+ * factor     0 < factor < 1 (cocostuff.py:114).  The coefficients are computed in the kernel, in double with
+ *            contraction off: inv = 1. / factor, f = float32((d + 0.5) inv - 0.5), floor, clamps and 1.f - f in float32.
+ * out_u8     uint8, out_px pixels of 3 bytes; out_labels_u8 uint8 [out_px], NULL exactly when labels_u8 is.
+ * out_offsets int64 [B], out_pitch int32 [B], out_sizes int32 [B][2]: image i is written as [h'_i][w'_i] pixels with a
+ *            row pitch of out_pitch[i] >= w'_i pixels from PIXEL out_offsets[i] -- back to back (pitch = w'), or the
+ *            top-left corner of a slab; h'_i = cvRound(h_i factor), w'_i likewise, at least 1 (the caller computes
+ *            them).  An image whose source extent leaves [0, total_px) or whose destination extent leaves
+ *            [0, out_px) (or with an extent outside 1..16384) is skipped: nothing of it is written.
+ * work       int32 [n_work][3] = (image, first output row, row count): one workgroup each, a one-dimensional grid
+ *            (B exceeds a grid's y extent on the full COCO set).  Rows outside the image are ignored.
+ * Pixels between the images (slab padding) are not written.  No atomics: two calls give identical bytes.
+ * ------------------------------------------------------------------------------- */
+int iic_seg_prescale(const void* imgs_u8, const void* labels_u8, const long* offsets, const int* sizes, int B,
+                     long total_px, double factor, void* out_u8, void* out_labels_u8, const long* out_offsets,
+                     const int* out_pitch, const int* out_sizes, long out_px, const int* work, int n_work,
+                     void* stream);
+
 /* random_affine's warp of the second view for iic_seg_augment_ragged (code/utils/segmentation/transforms.py:
  * 122-143: perform_affine_tf = F.affine_grid + F.grid_sample, bilinear, zero padding; then torch.flip(dims=[2]),
  * cocostuff.py:213-214), in the operation order of torch's CPU kernels, so that img2 equals the reference's bit for

@@ -113,7 +113,9 @@ def resize_stand_in(img, dsize=None, fx=None, fy=None, interpolation=None):
   return seg_ragged.resize_nearest_host(img, fx)
 
 
-def main():
+def main(cases=None, path=None):
+  """cases / path: another case table and fixture file (tools/gen_golden_seg_prescale.py); the defaults are this tool's."""
+  cases = CASES if cases is None else cases
   import cv2
   cv2.COLOR_RGB2GRAY = "RGB2GRAY"
   cv2.cvtColor = base.grey_fixed_point
@@ -222,7 +224,7 @@ def main():
       scale = 1.0
       if cfg["use_random_scale"]:
         scale = rec["rands"][0] * (cfg["scale_max"] - cfg["scale_min"]) + cfg["scale_min"]     # cocostuff.py:125-126
-      else:
+      elif not cfg["pre_scale_all"]:
         assert rec["extent"] == (h, w)
       out[key + "/image"] = img
       out[key + "/img1"] = img1.numpy().astype(np.float32)
@@ -247,11 +249,11 @@ def main():
     return flips, out
 
   out = {}
-  names = sorted(CASES)
+  names = sorted(cases)
   total = 0
   try:
     for ci, name in enumerate(names):
-      kind, cfg, sizes = CASES[name]
+      kind, cfg, sizes = cases[name]
       ds = instance(kind, cfg)
       cs = 4 if kind == "potsdam" else 3
       flips, salt = [], -1
@@ -271,7 +273,7 @@ def main():
     torch.Tensor.cuda = orig_cuda
     np.random.rand = orig_rand
   out["names"] = np.array(names)
-  path = os.path.join(ROOT, "tests", "golden", "seg_augment_ragged.npz")
+  path = os.path.join(ROOT, "tests", "golden", "seg_augment_ragged.npz") if path is None else path
   np.savez_compressed(path, **out)
   print("wrote", path, os.path.getsize(path), "bytes;", len(names), "cases,", total, "samples")
 

@@ -19,6 +19,15 @@ one process, the variants interleaved window by window: REPEATS windows of ITERS
 
     python tools/seg_augment_perf.py --ragged [--iters 1000] [--repeats 9]
 
+--ragged --prescaled: instead, pre_scale_all from the ORIGINAL images (SegRaggedAugmenter(source="original")) at the same
+COCO-Stuff-3 shape, 24 resident originals with sides 427..640, pre_scale_factor 0.33: (a) the parent's use_random_scale
+row re-measured -- the single-stage kernel over the pre-scaled pack seg_prescale.prescale_dataset makes; (b) the
+single-stage kernel over the originals (pre_scale_all without random scale); (c) the two-stage kernel
+(iic_seg_augment_ragged_prescaled: pre_scale_all, then use_random_scale).  A few samples of (b) and (c) are compared byte
+for byte with the host pipeline of tests/seg_prescale_cases.py before anything is timed.
+
+    python tools/seg_augment_perf.py --ragged --prescaled [--iters 1000] [--repeats 9]
+
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -161,18 +170,94 @@ def ragged_mode(a):
   print(json.dumps(rows))
 
 
+def prescaled_mode(a):
+  import types
+  from iic_amd import _lib, seg_prescale as sp, seg_ragged as sr
+  from tests import seg_prescale_cases as cases
+  dev = torch.device("cuda:0")
+  L = _lib.lib()
+  B, batch, S, factor = 24, 120, 128, 0.33
+  rng = np.random.default_rng(2025)
+  rel = (np.arange(256) >= 91).astype(np.uint8)
+  rel[182:] = 0
+
+  def cfg(scale, pre):
+    return types.SimpleNamespace(input_sz=S, no_sobel=False, include_rgb=True, jitter_brightness=0.4, jitter_contrast=0.4,
+                                 jitter_saturation=0.4, jitter_hue=0.125, flip_p=0.5, use_random_affine=False,
+                                 use_random_scale=scale, scale_min=0.6, scale_max=1.4, pre_scale_all=pre,
+                                 pre_scale_factor=factor)
+  shapes = [(int(h), int(w)) for h, w in zip(rng.integers(427, 641, B), rng.integers(427, 641, B))]
+  imgs = [rng.integers(0, 256, s + (3,), dtype=np.uint8) for s in shapes]
+  labels = [rng.integers(0, 182, s).astype(np.uint8) for s in shapes]
+  px, lab, nsz, noff = sp.prescale_dataset(imgs, labels=labels, factor=factor, device=dev)
+  # (a) what the parent commit offers: the pre-scaled pack resident, the random scale on the truncated image
+  resident = sr.SegRaggedAugmenter(px, cfg(True, False), labels=lab, relevance=rel, sizes=nsz, offsets=noff, seed=1)
+  one = sr.SegRaggedAugmenter(imgs, cfg(False, True), labels=labels, relevance=rel, seed=1, device=dev, source="original")
+  two = sr.SegRaggedAugmenter(imgs, cfg(True, True), labels=labels, relevance=rel, seed=1, device=dev, source="original")
+  idx = np.random.default_rng(5).integers(0, B, batch)
+  pa, pb, pc = resident.draw(idx), one.draw(idx), two.draw(idx)
+  for aug, params, scale in ((one, pb, False), (two, pc, True)):     # faster and different is not faster
+    few = cases.take(params, [0, 1, 2, 3])
+    got = [t.cpu().numpy() for t in aug.apply(few)]
+    want = cases.host_pipeline(imgs, labels, rel, cfg(scale, True), few, factor)
+    for k, w in enumerate(want):
+      assert all(got[j][k].tobytes() == w[j].tobytes() for j in range(4)), "kernel differs from the host pipeline"
+  C = two.out_channels
+  outs = (torch.empty(batch, C, S, S, device=dev), torch.empty(batch, C, S, S, device=dev),
+          torch.empty(batch, S, S, device=dev, dtype=torch.uint8), torch.empty(batch, 2, 3, device=dev))
+
+  def kernel(aug, params, stages):
+    ip = torch.from_numpy(np.ascontiguousarray(params["iparams"])).to(dev)
+    fp = torch.from_numpy(np.ascontiguousarray(params["fparams"])).to(dev)
+    src = aug.sizes_host[params["iparams"][:, 0]]
+    y0, x0 = params["iparams"][:, 2], params["iparams"][:, 1]
+    if stages == 2:
+      t = np.stack([sr.crop_taps2(src[:, 0], factor, params["scale"], y0, S),
+                    sr.crop_taps2(src[:, 1], factor, params["scale"], x0, S)], 1)
+      entry, width = L.iic_seg_augment_ragged_prescaled, 12
+    else:
+      sc = params["scale"] if params["scale"] is not None else np.full(batch, factor)
+      t = np.stack([sr.crop_taps(src[:, 0], sc, y0, S), sr.crop_taps(src[:, 1], sc, x0, S)], 1)
+      entry, width = L.iic_seg_augment_ragged, 6
+    taps = torch.from_numpy(np.ascontiguousarray(t).view(np.int32).reshape(batch, 2, S, width)).to(dev)
+    return lambda: _lib.check(entry(
+      aug.images.data_ptr(), aug.offsets.data_ptr(), aug.sizes.data_ptr(), aug.B, aug.total, aug.Cs,
+      aug.labels.data_ptr(), aug.relevance.data_ptr(), ip.data_ptr(), fp.data_ptr(), taps.data_ptr(), batch, S, 0, 1,
+      aug.lut.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(),
+      _lib.stream_ptr()), "ragged kernel")
+  names = ("resident pre-scaled pack + random scale (parent)", "originals, pre_scale_all (one stage)",
+           "originals, pre_scale_all + random scale (two stages)")
+  variants = [("kernel", dict(zip(names, (kernel(resident, pa, 1), kernel(one, pb, 1), kernel(two, pc, 2))))),
+              ("apply", dict(zip(names, (lambda: resident.apply(pa), lambda: one.apply(pb), lambda: two.apply(pc)))))]
+  print("COCO-Stuff-3 shape: batch %d, input_sz %d, C %d, %d resident originals %d..%d x %d..%d, pre_scale_factor %.2f; "
+        "%d windows of %d calls per variant, interleaved: median (min, max) per call"
+        % (batch, S, C, B, min(s[0] for s in shapes), max(s[0] for s in shapes), min(s[1] for s in shapes),
+           max(s[1] for s in shapes), factor, a.repeats, a.iters))
+  rows = []
+  for what, fns in variants:
+    iters = a.iters if what == "kernel" else max(1, a.iters // 10)
+    res = interleaved(fns, iters, a.repeats)
+    base = res[names[0]][0]
+    for k, (med, lo, hi) in res.items():
+      rows.append(dict(what=what, variant=k, ms=med, min_ms=lo, max_ms=hi, ratio_to_parent=med / base))
+      print("%-6s %-52s %.4f ms (min %.4f max %.4f)  x%.3f of the parent's row" % (what, k, med, lo, hi, med / base),
+            flush=True)
+  print(json.dumps(rows))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--iters", type=int, default=None)
   ap.add_argument("--repeats", type=int, default=None)
   ap.add_argument("--host-batches", type=int, default=2)
   ap.add_argument("--ragged", action="store_true")
+  ap.add_argument("--prescaled", action="store_true", help="with --ragged: pre_scale_all from the original images")
   a = ap.parse_args()
   assert torch.cuda.is_available(), "seg_augment_perf needs a GPU"
   torch.set_num_threads(1)
   if a.ragged:
     a.iters, a.repeats = a.iters or 1000, a.repeats or 9
-    return ragged_mode(a)
+    return prescaled_mode(a) if a.prescaled else ragged_mode(a)
   a.iters, a.repeats = a.iters or 50, a.repeats or 7
   rows = []
   for case in REAL:
