@@ -20,7 +20,11 @@
 // accumulators (<= 9 taps per pass: 144 fp32 registers); K-tiles of 128 pixels are split
 // across workgroups, partial sums go to [split][tap][co][ci] fp32 and are reduced (and
 // transposed to the OIHW parameter layout) by conv_wgrad_reduce_kernel.
+//
+// Which weight-gradient kernel a geometry gets -- this one or one of conv_wgrad_dma.hip's -- is decided once per launch
+// by wgrad_make_plan (below the kernels), which fills a wgrad_plan (conv_plan.h); iic_conv_wgrad launches from it.
 #include "common.h"
+#include "conv_plan.h"
 #include "conv_tile.h"
 #include "../../include/iic_hip.h"
 
@@ -332,14 +336,7 @@ __global__ void probe_tr16_kernel(uint16_t* out) {
   for (int j = 0; j < 4; ++j) out[l * 4 + j] = (uint16_t)v[j];
 }
 
-// conv_wgrad_dma.hip: LDS-DMA double-buffered variant for the stride-1 3x3 layers
-int iic_wgrad_dma_supported(const iic_conv_geom* g);
-int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, float* partials,
-                         int nsplit, void* stream);
-
 extern "C" {
-
-static int wgrad_cot(const iic_conv_geom* g) { return (g->Cout % 128 == 0) ? 128 : 64; }
 
 // Workgroups a weight-gradient launch aims for (tiles x K-splits); a 12-wave workgroup fills a CU.  256 (one per CU, rounds
 // 1-3) means every CU has to take one, and in the two-stream step a CU whose LDS the other view's kernel holds delays the
@@ -353,46 +350,87 @@ IIC_HOOK void iic_debug_wgrad_target_wgs(int v) { g_wgrad_target_wgs = v > 0 ? v
 static constexpr int g_wgrad_target_wgs = 224;
 #endif
 
+// Register-staged kernel: K-tiles of BM pixels and the tap batches in grid z (one tap per workgroup for a 1-tap gather)
+static int wgrad_reg_kt(const iic_conv_geom* g) { return (int)((igemm_rows_host(g) + BM - 1) / BM); }
+static int wgrad_reg_batches(const iic_conv_geom* g) { return g->ntaps == 1 ? 1 : (g->ntaps + NTG * TPG - 1) / (NTG * TPG); }
+
+// The split count is computed on the register-staged kernel's work split (its 128-pixel K-tiles, its tap batches)
+// WHICHEVER kernel the plan names (a DMA kernel has no grid z and may walk 64-pixel tiles), deliberately: the split
+// count sets the summation order, and LAB.md R6.8 declined a workgroup target that depends on how the launch is made
+// for that reason.  A count that followed the kernel would change a layer's gradient bits with every switch setting;
+// this one depends on the geometry alone, so the kernels that keep the summation order give the same bits by default.
 int iic_conv_wgrad_nsplit(const iic_conv_geom* g) {
-  const long M = igemm_rows_host(g);
-  const int kt = (int)((M + BM - 1) / BM);
-  const int batches = g->ntaps == 1 ? 1 : (g->ntaps + NTG * TPG - 1) / (NTG * TPG);
-  const int tiles = (g->Cout / wgrad_cot(g)) * (g->Cin / 64) * batches;
+  const int kt = wgrad_reg_kt(g);
+  const int tiles = (g->Cout / wgrad_cot(g)) * (g->Cin / 64) * wgrad_reg_batches(g);
   int ns = g_wgrad_target_wgs / (tiles > 0 ? tiles : 1);   // default: one workgroup (12 waves) per CU
   if (ns < 1) ns = 1;
   if (ns > kt) ns = kt;
   return ns;
 }
 
+// The plan of a geometry (conv_plan.h) under the switches in force; false (kernel WGRAD_NONE): no weight-gradient kernel
+// takes it.  In the order of preference: the DMA-fed kernels of conv_wgrad_dma.hip (block-tiled, planar, first
+// generation; transposing reads only), then the register-staged kernel where its patch fits LDS.
+static bool wgrad_make_plan(const iic_conv_geom* g, int use_tr, wgrad_plan* p) {
+  *p = wgrad_plan{};
+  if (!g || g->Cin % 64 != 0 || g->Cout % 64 != 0 || g->ntaps < 1 || g->ntaps > IIC_MAX_TAPS) return false;
+  if (igemm_rows_host(g) >= (1L << 31) || (long)g->N * g->in_Hp * g->in_Wp >= (1L << 31)) return false;
+  p->use_tr = use_tr != 0;
+  p->cot = wgrad_cot(g);
+  p->gx = (g->Cout / p->cot) * (g->Cin / 64);
+  p->nsplit = iic_conv_wgrad_nsplit(g);
+  if (use_tr && iic_wgrad_dma_plan(g, p)) return true;
+  p->gather = g->ntaps == 1;
+  p->bmk = BM; p->nbuf = 1;
+  p->np = p->gather ? BM : g->NP;
+  p->lx = (p->np * ROWB + 15) & ~15;
+  p->lds = (long)p->lx + BM * (p->cot == 64 ? 144 : 288) + 4 * BM * 4;
+  if (p->lds > IIC_LDS_BYTES) {
+    *p = wgrad_plan{};
+    return false;
+  }
+  p->kt = wgrad_reg_kt(g);
+  p->gz = wgrad_reg_batches(g);
+  p->threads = p->gather ? 256 : 768;
+  p->kernel = WGRAD_REG;
+  return true;
+}
+
 int iic_conv_wgrad(const iic_conv_geom* g, const void* x, const void* dy, float* partials,
                    int nsplit, int use_tr, void* stream) {
   if (!g || !x || !dy || !partials || nsplit < 1) return IIC_ERR_ARG;
-  if (g->Cin % 64 != 0 || g->Cout % 64 != 0 || g->ntaps < 1 || g->ntaps > IIC_MAX_TAPS)
-    return IIC_ERR_UNSUPPORTED;
-  const long M = igemm_rows_host(g);
-  if (M >= (1L << 31) || (long)g->N * g->in_Hp * g->in_Wp >= (1L << 31)) return IIC_ERR_UNSUPPORTED;
-  if (use_tr && iic_wgrad_dma_supported(g)) return iic_wgrad_dma_launch(g, x, dy, partials, nsplit, stream);
-  const int kt = (int)((M + BM - 1) / BM);
-  const bool ga = g->ntaps == 1;
-  const int cot = wgrad_cot(g);
-  const int lx = ((ga ? BM : g->NP) * ROWB + 15) & ~15;
-  const long lds = (long)lx + BM * (cot == 64 ? 144 : 288) + 4 * BM * 4;
-  if (lds > IIC_LDS_BYTES) return IIC_ERR_UNSUPPORTED;
-  dim3 grid((g->Cout / cot) * (g->Cin / 64), nsplit, ga ? g->ntaps : (g->ntaps + NTG * TPG - 1) / (NTG * TPG));
-  hipStream_t s = (hipStream_t)stream;
+  wgrad_plan p;
+  if (!wgrad_make_plan(g, use_tr, &p)) return IIC_ERR_UNSUPPORTED;
+  if (p.kernel != WGRAD_REG) return iic_wgrad_dma_launch(g, p, x, dy, partials, nsplit, stream);
   int rc = IIC_OK;
-#define WGRAD_LAUNCH(TR_, GA_, COT_)                                                            \
-  rc = iic_launch_lds<conv_wgrad_kernel<TR_, GA_, COT_>>(grid, dim3(GA_ ? 256 : 768), lds, s,   \
-                                                         *g, (const bf16_t*)x, (const bf16_t*)dy, \
-                                                         partials, nsplit, kt, lx)
+#define WGRAD_LAUNCH(TR_, GA_, COT_)                                                                           \
+  rc = iic_launch_lds<conv_wgrad_kernel<TR_, GA_, COT_>>(dim3(p.gx, nsplit, p.gz), dim3(p.threads), p.lds,     \
+                                                         (hipStream_t)stream, *g, (const bf16_t*)x,            \
+                                                         (const bf16_t*)dy, partials, nsplit, p.kt, p.lx)
 #define WGRAD_LAUNCH2(TR_, GA_)                                                                 \
   do {                                                                                          \
-    if (cot == 128) WGRAD_LAUNCH(TR_, GA_, 128); else WGRAD_LAUNCH(TR_, GA_, 64);               \
+    if (p.cot == 128) WGRAD_LAUNCH(TR_, GA_, 128); else WGRAD_LAUNCH(TR_, GA_, 64);             \
   } while (0)
-  if (use_tr) { if (ga) WGRAD_LAUNCH2(true, true); else WGRAD_LAUNCH2(true, false); }
-  else        { if (ga) WGRAD_LAUNCH2(false, true); else WGRAD_LAUNCH2(false, false); }
+  if (p.use_tr) { if (p.gather) WGRAD_LAUNCH2(true, true); else WGRAD_LAUNCH2(true, false); }
+  else          { if (p.gather) WGRAD_LAUNCH2(false, true); else WGRAD_LAUNCH2(false, false); }
   return rc ? rc : iic_launch_status();
 }
+
+#ifdef IIC_DEBUG_HOOKS
+// The plan of a geometry under the switches in force, as 28 ints (tests/test_conv_dispatch_cpu.py; host code only: needs
+// no device): kernel (0 = none, 1 = register-staged conv_wgrad_kernel, 2 = first-generation conv_wgrad_dma_kernel,
+// 3 = conv_wgrad_pl_kernel, 4 = conv_wgrad_pl2_kernel, 5 = conv_wgrad_b2d_kernel), banded (0 | 1), asm_reads, gather,
+// cot, bmk, nbuf, ntab, txs, band, bstride, mto, np, plane, lx, kt, grid x, grid y (= nsplit, the default split count),
+// grid z, threads, lds, then the block tiling bw, bh, nbx, nby, PW, NPR, drow.  A null geometry zeroes `out`.
+IIC_HOOK void iic_debug_wgrad_plan(const iic_conv_geom* g, int use_tr, int* out) {
+  wgrad_plan p;
+  wgrad_make_plan(g, use_tr, &p);
+  const int f[28] = {p.kernel, p.band > 0, p.asm_reads, p.gather, p.cot, p.bmk, p.nbuf, p.ntab, p.txs, p.band,
+                     p.bstride, p.mto, p.np, p.plane, p.lx, p.kt, p.gx, p.nsplit, p.gz, p.threads, (int)p.lds,
+                     p.blk.bw, p.blk.bh, p.blk.nbx, p.blk.nby, p.blk.PW, p.blk.NPR, p.blk.drow};
+  for (int i = 0; i < 28; ++i) out[i] = f[i];
+}
+#endif
 
 int iic_conv_wgrad_reduce(const float* partials, int nsplit, int T, int Cout, int Cin, float* dW,
                           int accumulate, void* stream) {

@@ -29,8 +29,13 @@
 //     one K-tile of prefetch the ~2-4 us HBM latency exceeded the ~1-2 us of MFMA work per tile
 //     and every tile waited for its data; each wave issues a FIXED number of DMA instructions per
 //     tile so that a counted s_waitcnt vmcnt(N) retires exactly tile kt.
+//
+// Which kernel a geometry gets, in which layout, is decided once per launch: iic_wgrad_dma_plan (below the kernels)
+// fills a wgrad_plan (conv_plan.h) for wgrad_make_plan of conv_wgrad.hip, and iic_wgrad_dma_launch only turns its
+// fields into template arguments.
 #include <type_traits>
 #include "common.h"
+#include "conv_plan.h"
 #include "../../include/iic_hip.h"
 
 #define WD_THREADS 768
@@ -925,12 +930,7 @@ __global__ __launch_bounds__(WD_THREADS) void conv_wgrad_pl2_kernel(
 // past the image edge (or past bw x bh) take their dY from pixel 0 of the PT tensor (zero border) and read whatever input
 // pixel lies there (finite x 0).  Same work split per wave, same partial-sum layout as the planar kernels; the summation
 // ORDER over pixels differs from theirs (so do the last bits).  Stride-1 3 x 3 taps on a regular grid, COT = 128 only.
-#define WDB_MAXNI 6
-struct wdb_args {
-  int bw, bh, nbx, nby;           // block size, blocks per image row / column
-  int PW, NPR, drow;              // patch width, patch pixels, tap-row distance in image rows
-  int plane_bytes, num_tiles;
-};
+#define WDB_MAXNI 6                 // (wdb_args: conv_plan.h)
 
 template <int TXS>
 __global__ __launch_bounds__(WD_THREADS) void conv_wgrad_b2d_kernel(
@@ -1164,13 +1164,17 @@ IIC_SWITCH(g_wd_enabled, 1, iic_debug_enable_wgrad_dma)     // 0: register-stage
 // patch 44 % larger per row (NP64/64 vs NP/128) and the tile barrier comes twice as often, which
 // costs more than the deeper prefetch hides.  The 64-pixel ring serves geometries whose 128-row
 // patch does not fit twice in LDS (wide images).  g_wd_enabled = 3 forces it (tests).
-static int wd_config(const iic_conv_geom* g, int* bmk, int* nbuf) {
+// (the three steps below fill bmk / nbuf / ntab / band / blk of the plan of a geometry they take and leave the plan
+// alone otherwise; they read its cot / txs / mto)
+static void wd_take(wgrad_plan* p, int bmk, int nbuf, int ntab, int band = 0) {
+  p->bmk = bmk; p->nbuf = nbuf; p->ntab = ntab; p->band = band;
+}
+static int wd_config(const iic_conv_geom* g, wgrad_plan* p) {
   if (g->ntaps != 9 || g->Cin % 64 != 0 || g->Cout % 64 != 0 || g->NP <= 0 || g->NP > 65535) return 0;
   if (g->MP > 0 && g->MP % 128 != 0) return 0;         // padded numbering: K-tiles must not straddle images
-  const int cot = (g->Cout % 128 == 0) ? 128 : 64;
+  const int cot = p->cot;
   if (g_wd_enabled != 3 && wd_lds(g->NP, cot, 128, 2) <= IIC_LDS_BYTES) {
-    *bmk = 128;
-    *nbuf = 2;
+    wd_take(p, 128, 2, WD_NTAB);
     return 1;
   }
   // padded row numbering = large images (SegmentationNet10a at 200 x 200): measured with the 64-pixel ring
@@ -1181,8 +1185,7 @@ static int wd_config(const iic_conv_geom* g, int* bmk, int* nbuf) {
     // (2 buffers: the stride-2 layers, whose 64-row patch spans 330-440 input pixels)
     for (int nb = 4; nb >= 2; --nb)
       if (wd_lds(g->NP64, cot, 64, nb) <= IIC_LDS_BYTES) {
-        *bmk = 64;
-        *nbuf = nb;
+        wd_take(p, 64, nb, WD_NTAB);
         return 1;
       }
   }
@@ -1208,45 +1211,39 @@ static int wdp_txs(const iic_conv_geom* g) {
 // span of span + max tap offset + 1 rows -- for dilated convolutions and wide images the rows between the tap rows are
 // most of that span (SegmentationNet10a c5 at Potsdam: 500 rows per 64-pixel tile contiguous, 3 x 80 banded).  Only
 // where the bands do not overlap (tap-row distance >= band) and only for the 128-cout kernel.
-static int wdp_band_rows(const iic_conv_geom* g, int np, int txs) {
-  int mto = 0;
-  for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
+static int wdp_band_rows(int np, int mto, int txs) {
   const int span = np - mto - 1;                    // last - first input pixel (tap 0) of a tile, at most
   return (span + 2 * txs + 1 + 15) & ~15;
 }
-static int wdp_config(const iic_conv_geom* g, int* bmk, int* nbuf, int* ntab, int* band) {
-  *band = 0;
+static int wdp_config(const iic_conv_geom* g, wgrad_plan* p) {
   if (!g_wd_planar || g->ntaps != 9 || g->Cin % 64 != 0 || g->Cout % 64 != 0 || g->NP <= 0 || g->NP > 65535) return 0;
-  const int txs = wdp_txs(g);
+  const int txs = p->txs, cot = p->cot, mto = p->mto;
   if (!txs) return 0;
   if ((long)g->N * g->out_Hp * g->out_Wp * g->Cout * 2 >= (1L << 32)) return 0;
-  const int cot = (g->Cout % 128 == 0) ? 128 : 64;
   const long lim = IIC_LDS_BYTES;
   if (g_wd_enabled != 3 && (g->MP <= 0 || g->MP % 128 == 0)) {
     for (int nt = 8; nt >= 4; nt >>= 1)
-      if (wdp_lds(g->NP, cot, 128, 2, nt) <= lim) { *bmk = 128; *nbuf = 2; *ntab = nt; return 1; }
+      if (wdp_lds(g->NP, cot, 128, 2, nt) <= lim) { wd_take(p, 128, 2, nt); return 1; }
   }
   if (g->NP64 > 0 && (g->MP <= 0 || g->MP % 64 == 0)) {
     for (int nb = 4; nb >= 3; --nb)
-      if (wdp_lds(g->NP64, cot, 64, nb, 8) <= lim) { *bmk = 64; *nbuf = nb; *ntab = 8; return 1; }
+      if (wdp_lds(g->NP64, cot, 64, nb, 8) <= lim) { wd_take(p, 64, nb, 8); return 1; }
     // banded 64-pixel ring: 3 bands of (64 + wraps + 2 txs + 1) rows instead of the contiguous span
     const int bstride = g->tap_off[3] - g->tap_off[0];
     if (cot == 128 && bstride > 0 && g->tap_off[6] - g->tap_off[3] == bstride) {
-      const int bp = wdp_band_rows(g, g->NP64, txs);
+      const int bp = wdp_band_rows(g->NP64, mto, txs);
       if (bp <= bstride && 3 * bp < g->NP64) {
         for (int nb = 4; nb >= 2; --nb)
-          if (wdp_lds(3 * bp, cot, 64, nb, 8) <= lim) { *bmk = 64; *nbuf = nb; *ntab = 8; *band = bp; return 1; }
+          if (wdp_lds(3 * bp, cot, 64, nb, 8) <= lim) { wd_take(p, 64, nb, 8, bp); return 1; }
       }
     }
     // two buffers of 64-pixel tiles: the patch is mostly halo there (NP64 / 64 = 5-8 rows fetched per row used) and the
     // planar DMA moves it in 64-byte pieces -- measured (profiles/r06_wgrad_seg_ab.txt): 1.12-1.22 x the previous kernel
     // up to 284 halo rows (COCO-Stuff c2 / c5 / c6), 1.04 x at 414 (Potsdam c2), 0.98 x at 420 (Potsdam c6) -- where the
     // banded form above does not apply
-    int mto = 0;
-    for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
     if (mto <= 400 || g_wd_enabled == 3) {          // (halo rows, not patch rows: the stride-2 layers' 64-row span is long by itself)
-      if (wdp_lds(g->NP64, cot, 64, 2, 8) <= lim) { *bmk = 64; *nbuf = 2; *ntab = 8; return 1; }
-      if (wdp_lds(g->NP64, cot, 64, 2, 4) <= lim) { *bmk = 64; *nbuf = 2; *ntab = 4; return 1; }
+      if (wdp_lds(g->NP64, cot, 64, 2, 8) <= lim) { wd_take(p, 64, 2, 8); return 1; }
+      if (wdp_lds(g->NP64, cot, 64, 2, 4) <= lim) { wd_take(p, 64, 2, 4); return 1; }
     }
   }
   return 0;
@@ -1255,10 +1252,10 @@ static int wdp_config(const iic_conv_geom* g, int* bmk, int* nbuf, int* ntab, in
 // Block-tiled kernel (conv_wgrad_b2d_kernel): block shape by exhaustive search -- the fewest 128-row tiles per image, then
 // the smallest patch.  0 = not applicable.  Taken wherever it applies: every layer of profiles/r06_wgrad_b2d_ab.txt is
 // faster on it (1.08-1.42 x), including those the planar kernels keep on their 128-pixel contiguous layout.
-static int wdb_config(const iic_conv_geom* g, wdb_args* A) {
-  if (!g_wd_enabled || g->ntaps != 9 || g->Cin % 64 != 0 || g->Cout % 128 != 0) return 0;
+static int wdb_config(const iic_conv_geom* g, wgrad_plan* p) {
+  if (g->ntaps != 9 || g->Cin % 64 != 0 || g->Cout % 128 != 0) return 0;
   if (g->sy != 1 || g->sx != 1 || g->ty != 1 || g->tx != 1) return 0;
-  const int txs = wdp_txs(g);
+  const int txs = p->txs;
   if (!txs) return 0;
   const int rowoff = g->tap_off[3] - g->tap_off[0];
   if (rowoff <= 0 || rowoff % g->in_Wp != 0 || g->tap_off[6] - g->tap_off[3] != rowoff || g->tap_off[0] != 0) return 0;
@@ -1284,9 +1281,10 @@ static int wdb_config(const iic_conv_geom* g, wdb_args* A) {
     if (best < 0 || cost < best) { best = cost; best_tiles = tiles; best_bw = bw; }
   }
   if (best < 0) return 0;
+  if ((double)g->MY * g->MX < 0.88 * 128.0 * (double)best_tiles) return 0;        // > 12 % idle rows: not worth it
+  wdb_args* A = &p->blk;
   A->bw = best_bw; A->bh = 128 / best_bw;
   A->nbx = (g->MX + A->bw - 1) / A->bw; A->nby = (g->MY + A->bh - 1) / A->bh;
-  if ((double)g->MY * g->MX < 0.88 * 128.0 * (double)best_tiles) return 0;        // > 12 % idle rows: not worth it
   A->PW = A->bw + 2 * txs; A->drow = drow;
   A->NPR = A->PW * (A->bh + 2 * drow);
   A->plane_bytes = (int)wdp_plane_bytes(A->NPR);
@@ -1294,107 +1292,98 @@ static int wdb_config(const iic_conv_geom* g, wdb_args* A) {
   return 1;
 }
 
-#ifdef IIC_DEBUG_HOOKS
-// Which weight-gradient kernel / layout a 3 x 3 geometry gets (tests: a layer must not fall off the planar kernels by a
-// few bytes of LDS unnoticed -- SegmentationNet10a c3 / c4 did, by 64): 0 = register-staged (conv_wgrad.hip),
-// 1 = first-generation DMA kernel, 2 = planar, 3 = planar with the banded patch; + 100 * K-tile pixels + 10000 * ring
-// depth + 100000 * table ring.
-IIC_HOOK int iic_debug_wgrad_config(const iic_conv_geom* g) {
-  int bmk = 0, nbuf = 0, ntab = 0, band = 0;
-  if (!g || !g_wd_enabled) return 0;
-  wdb_args A;
-  if (wdb_config(g, &A)) return 4 + 100 * 128 + 10000 * 2 + 1000000 * A.bw;      // 4 = block-tiled (+ 1e6 * block width)
-  if (wdp_config(g, &bmk, &nbuf, &ntab, &band)) return (band > 0 ? 3 : 2) + 100 * bmk + 10000 * nbuf + 100000 * ntab;
-  if (wd_config(g, &bmk, &nbuf)) return 1 + 100 * bmk + 10000 * nbuf + 100000 * WD_NTAB;
-  return 0;
-}
-#endif
-
-// used by conv_wgrad.hip's dispatcher
-int iic_wgrad_dma_supported(const iic_conv_geom* g) {
-  int bmk, nbuf, ntab, band;
-  wdb_args A;
-  return g_wd_enabled && (wdb_config(g, &A) || wdp_config(g, &bmk, &nbuf, &ntab, &band) || wd_config(g, &bmk, &nbuf));
-}
-
-int iic_wgrad_dma_launch(const iic_conv_geom* g, const void* x, const void* dy, float* partials,
-                         int nsplit, void* stream) {
-  const int cot = (g->Cout % 128 == 0) ? 128 : 64;
+// The DMA-fed part of wgrad_make_plan (conv_wgrad.hip), under the switches in force; false: none of these kernels takes
+// the geometry.  In the order of preference: block-tiled, planar (the pipelined form or the plain one by g_wd_planar),
+// first generation.
+bool iic_wgrad_dma_plan(const iic_conv_geom* g, wgrad_plan* p) {
+  if (!g_wd_enabled) return false;
+  p->txs = wdp_txs(g);
+  p->mto = 0;
+  for (int i = 0; i < g->ntaps; ++i) p->mto = g->tap_off[i] > p->mto ? g->tap_off[i] : p->mto;
+  p->threads = WD_THREADS;
+  p->gz = 1;
   const long M = (long)g->N * (g->MP > 0 ? g->MP : g->MY * g->MX);
-  int mto = 0;
-  for (int i = 0; i < g->ntaps; ++i) mto = g->tap_off[i] > mto ? g->tap_off[i] : mto;
-  dim3 grid((g->Cout / cot) * (g->Cin / 64), nsplit);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = IIC_OK;
-  wdb_args BA;
-  if (wdb_config(g, &BA)) {                            // block-tiled kernel (large images)
-    const long ldsb = 2L * (2L * BA.plane_bytes + 128 * 256);
-#define WDB_LAUNCH(TXS_)                                                                         \
-  rc = iic_launch_lds<conv_wgrad_b2d_kernel<TXS_>>(grid, dim3(WD_THREADS), ldsb, s, *g, (const bf16_t*)x, \
-                                                   (const bf16_t*)dy, partials, nsplit, BA, g_wd_ablate)
-    if (wdp_txs(g) == 1) WDB_LAUNCH(1); else WDB_LAUNCH(2);
-    return rc ? rc : iic_launch_status();
-  }
-  int pbmk = 0, pnbuf = 0, pntab = 0, pband = 0;
-  if (wdp_config(g, &pbmk, &pnbuf, &pntab, &pband)) {  // planar-patch kernels
-    const int txs = wdp_txs(g);
-    const int bstride = g->tap_off[3] - g->tap_off[0];
-    const int np = pband > 0 ? 3 * pband : (pbmk == 64 ? g->NP64 : g->NP);      // LDS rows per plane
-    const int kt = (int)((M + pbmk - 1) / pbmk);
-    const int plane = (int)wdp_plane_bytes(np);
-    const long ldsp = wdp_lds(np, cot, pbmk, pnbuf, pntab);
-#define WDP_LAUNCH3(COT_, BMK_, NBUF_, TXS_, ASM_, NTAB_)                                        \
-  rc = iic_launch_lds<conv_wgrad_pl_kernel<COT_, BMK_, NBUF_, TXS_, ASM_, NTAB_>>(              \
-      grid, dim3(WD_THREADS), ldsp, s, *g, (const bf16_t*)x, (const bf16_t*)dy, partials, nsplit, kt, plane, mto, \
-      g_wd_ablate, pband, bstride)
-#define WDP2_LAUNCH3(COT_, BMK_, NBUF_, TXS_, NTAB_)                                             \
-  rc = iic_launch_lds<conv_wgrad_pl2_kernel<COT_, BMK_, NBUF_, TXS_, NTAB_>>(                   \
-      grid, dim3(WD_THREADS), ldsp, s, *g, (const bf16_t*)x, (const bf16_t*)dy, partials, nsplit, kt, plane, mto, \
-      g_wd_ablate, pband, bstride)
-#ifdef IIC_DEBUG_HOOKS
-#define WDP_LAUNCH2(COT_, BMK_, NBUF_, TXS_, NTAB_)                                              \
-  do {                                                                                          \
-    if (g_wd_planar == 4 || (g_wd_planar == 5 && COT_ == 64)) WDP2_LAUNCH3(COT_, BMK_, NBUF_, TXS_, NTAB_); \
-    else if (g_wd_planar == 1) WDP_LAUNCH3(COT_, BMK_, NBUF_, TXS_, false, NTAB_);              \
-    else WDP_LAUNCH3(COT_, BMK_, NBUF_, TXS_, true, NTAB_);                                     \
-  } while (0)
-#else      /* the product library instantiates the default forms only */
-#define WDP_LAUNCH2(COT_, BMK_, NBUF_, TXS_, NTAB_)                                              \
-  do {                                                                                          \
-    if (COT_ == 64) WDP2_LAUNCH3(64, BMK_, NBUF_, TXS_, NTAB_);                                 \
-    else WDP_LAUNCH3(128, BMK_, NBUF_, TXS_, true, NTAB_);                                      \
-  } while (0)
-#endif
-#define WDP_LAUNCH(BMK_, NBUF_, NTAB_)                                                           \
-  do {                                                                                          \
-    if (cot == 128) { if (txs == 1) WDP_LAUNCH2(128, BMK_, NBUF_, 1, NTAB_); else WDP_LAUNCH2(128, BMK_, NBUF_, 2, NTAB_); } \
-    else { if (txs == 1) WDP_LAUNCH2(64, BMK_, NBUF_, 1, NTAB_); else WDP_LAUNCH2(64, BMK_, NBUF_, 2, NTAB_); } \
-  } while (0)
-    if (pbmk == 128) { if (pntab == 8) WDP_LAUNCH(128, 2, 8); else WDP_LAUNCH(128, 2, 4); }
-    else if (pnbuf == 4) WDP_LAUNCH(64, 4, 8);
-    else if (pnbuf == 3) WDP_LAUNCH(64, 3, 8);
-    else if (pntab == 8) WDP_LAUNCH(64, 2, 8);
-    else WDP_LAUNCH(64, 2, 4);
-    return rc ? rc : iic_launch_status();
-  }
-  int bmk = 0, nbuf = 0;
-  if (!wd_config(g, &bmk, &nbuf)) return IIC_ERR_UNSUPPORTED;
-  const int kt = (int)((M + bmk - 1) / bmk);
-  const int np = bmk == 64 ? g->NP64 : g->NP;
-  const int xb = (int)wd_xb_bytes(np);
-  const long lds = wd_lds(np, cot, bmk, nbuf);
-#define WD_LAUNCH(COT_, BMK_, NBUF_)                                                             \
-  rc = iic_launch_lds<conv_wgrad_dma_kernel<COT_, BMK_, NBUF_>>(grid, dim3(WD_THREADS), lds, s, *g, (const bf16_t*)x, \
-                                                                (const bf16_t*)dy, partials, nsplit, kt, xb, mto,     \
-                                                                g_wd_ablate)
-  if (bmk == 64 && nbuf == 4) {
-    if (cot == 128) WD_LAUNCH(128, 64, 4); else WD_LAUNCH(64, 64, 4);
-  } else if (bmk == 64 && nbuf == 3) {
-    if (cot == 128) WD_LAUNCH(128, 64, 3); else WD_LAUNCH(64, 64, 3);
-  } else if (bmk == 64) {
-    if (cot == 128) WD_LAUNCH(128, 64, 2); else WD_LAUNCH(64, 64, 2);
+  if (wdb_config(g, p)) {                             // (large images)
+    p->kernel = WGRAD_B2D;
+    p->bmk = 128; p->nbuf = 2;
+    p->np = p->blk.NPR; p->plane = p->blk.plane_bytes;
+    p->kt = p->blk.num_tiles;
+    p->lds = 2L * (2L * p->plane + 128 * 256);
+  } else if (wdp_config(g, p)) {
+    p->kernel = (g_wd_planar == 4 || (g_wd_planar == 5 && p->cot == 64)) ? WGRAD_PL2 : WGRAD_PL;
+    p->asm_reads = p->kernel == WGRAD_PL && g_wd_planar != 1;
+    p->bstride = g->tap_off[3] - g->tap_off[0];
+    p->np = p->band > 0 ? 3 * p->band : (p->bmk == 64 ? g->NP64 : g->NP);
+    p->plane = (int)wdp_plane_bytes(p->np);
+    p->kt = (int)((M + p->bmk - 1) / p->bmk);
+    p->lds = wdp_lds(p->np, p->cot, p->bmk, p->nbuf, p->ntab);
+  } else if (wd_config(g, p)) {
+    p->kernel = WGRAD_DMA;
+    p->np = p->bmk == 64 ? g->NP64 : g->NP;
+    p->plane = (int)wd_xb_bytes(p->np);
+    p->kt = (int)((M + p->bmk - 1) / p->bmk);
+    p->lds = wd_lds(p->np, p->cot, p->bmk, p->nbuf);
   } else {
-    if (cot == 128) WD_LAUNCH(128, 128, 2); else WD_LAUNCH(64, 128, 2);
+    return false;
+  }
+  return true;
+}
+
+// The launch of a plan: its fields only become template arguments and kernel arguments here.
+#define WD_LAUNCH_ARGS                                                                                         \
+  dim3(p.gx, nsplit, p.gz), dim3(p.threads), p.lds, (hipStream_t)stream, *g, (const bf16_t*)x, (const bf16_t*)dy, \
+      partials, nsplit
+
+// planar kernels.  FORM: 0 = conv_wgrad_pl_kernel with builtin reads, 1 = with inline-asm reads, 2 = conv_wgrad_pl2_kernel
+template <int COT, int TXS, int FORM>
+static int wdp_launch(const iic_conv_geom* g, const wgrad_plan& p, const void* x, const void* dy, float* partials,
+                      int nsplit, void* stream) {
+#define WDP_LAUNCH(BMK_, NBUF_, NTAB_)                                                                         \
+  do {                                                                                                        \
+    if constexpr (FORM == 2)                                                                                  \
+      return iic_launch_lds<conv_wgrad_pl2_kernel<COT, BMK_, NBUF_, TXS, NTAB_>>(                             \
+          WD_LAUNCH_ARGS, p.kt, p.plane, p.mto, g_wd_ablate, p.band, p.bstride);                              \
+    else                                                                                                      \
+      return iic_launch_lds<conv_wgrad_pl_kernel<COT, BMK_, NBUF_, TXS, FORM == 1, NTAB_>>(                   \
+          WD_LAUNCH_ARGS, p.kt, p.plane, p.mto, g_wd_ablate, p.band, p.bstride);                              \
+  } while (0)
+  if (p.bmk == 128) { if (p.ntab == 8) WDP_LAUNCH(128, 2, 8); else WDP_LAUNCH(128, 2, 4); }
+  else if (p.nbuf == 4) WDP_LAUNCH(64, 4, 8);
+  else if (p.nbuf == 3) WDP_LAUNCH(64, 3, 8);
+  else if (p.ntab == 8) WDP_LAUNCH(64, 2, 8);
+  else WDP_LAUNCH(64, 2, 4);
+}
+#ifdef IIC_DEBUG_HOOKS
+#define WDP_FORM(COT_, TXS_) \
+  (p.kernel == WGRAD_PL2 ? wdp_launch<COT_, TXS_, 2> : p.asm_reads ? wdp_launch<COT_, TXS_, 1> : wdp_launch<COT_, TXS_, 0>)
+#else      /* the product library instantiates the default forms only: 64-cout -> pl2, 128-cout -> pl asm */
+#define WDP_FORM(COT_, TXS_) wdp_launch<COT_, TXS_, (COT_ == 64 ? 2 : 1)>
+#endif
+
+int iic_wgrad_dma_launch(const iic_conv_geom* g, const wgrad_plan& p, const void* x, const void* dy, float* partials,
+                         int nsplit, void* stream) {
+  int rc = IIC_OK;
+  if (p.kernel == WGRAD_B2D) {
+    if (p.txs == 1) rc = iic_launch_lds<conv_wgrad_b2d_kernel<1>>(WD_LAUNCH_ARGS, p.blk, g_wd_ablate);
+    else rc = iic_launch_lds<conv_wgrad_b2d_kernel<2>>(WD_LAUNCH_ARGS, p.blk, g_wd_ablate);
+  } else if (p.kernel == WGRAD_PL || p.kernel == WGRAD_PL2) {
+    const auto launch = p.cot == 128 ? (p.txs == 1 ? WDP_FORM(128, 1) : WDP_FORM(128, 2))
+                                     : (p.txs == 1 ? WDP_FORM(64, 1) : WDP_FORM(64, 2));
+    rc = launch(g, p, x, dy, partials, nsplit, stream);
+  } else if (p.kernel == WGRAD_DMA) {
+#define WD_LAUNCH(BMK_, NBUF_)                                                                                 \
+  do {                                                                                                        \
+    if (p.cot == 128)                                                                                         \
+      rc = iic_launch_lds<conv_wgrad_dma_kernel<128, BMK_, NBUF_>>(WD_LAUNCH_ARGS, p.kt, p.plane, p.mto, g_wd_ablate); \
+    else                                                                                                      \
+      rc = iic_launch_lds<conv_wgrad_dma_kernel<64, BMK_, NBUF_>>(WD_LAUNCH_ARGS, p.kt, p.plane, p.mto, g_wd_ablate);  \
+  } while (0)
+    if (p.bmk == 128) WD_LAUNCH(128, 2);
+    else if (p.nbuf == 4) WD_LAUNCH(64, 4);
+    else if (p.nbuf == 3) WD_LAUNCH(64, 3);
+    else WD_LAUNCH(64, 2);
+  } else {
+    return IIC_ERR_UNSUPPORTED;
   }
   return rc ? rc : iic_launch_status();
 }

@@ -90,33 +90,3 @@ def test_product_code_never_imports_oracle():
       if f.endswith(".py"):
         src = open(os.path.join(dp, f)).read()
         assert "import oracle" not in src and "from oracle" not in src, f
-
-
-def test_weight_gradient_dispatch_of_the_baseline_configs():
-  """Every stride-1 3 x 3 weight gradient of the five BASELINE configs runs on the planar kernels, in the layout LAB.md
-  R6.8 / R6.12 / R6.13 measured (code = kernel + 100 * K-tile pixels + 10000 * ring depth + 100000 * table ring; kernel
-  2 = planar, 3 = planar with the banded patch, 4 = block-tiled): a few bytes of LDS must not drop a layer back to an
-  older kernel unnoticed."""
-  from iic_amd import _lib, geom
-  dbg = os.path.join(os.path.dirname(_lib.LIB_PATH), "libiic_hip_dbg.so")
-  assert os.path.exists(dbg), "build it: make -C iic_amd/csrc dbg"
-  L = ctypes.CDLL(dbg)            # a host-side function of the instrumented library: no device needed
-  L.iic_debug_wgrad_config.argtypes = [ctypes.c_void_p]
-  cases = [  # name, N, cin, cout, H, conv padding, dilation, PT border, expected
-      ("5g layer1", 660, 64, 64, 49, 1, 1, 1, 2 + 100 * 128 + 10000 * 2 + 100000 * 8),
-      ("5g layer2", 660, 128, 128, 25, 1, 1, 1, 2 + 100 * 128 + 10000 * 2 + 100000 * 8),
-      ("5g layer3", 660, 256, 256, 13, 1, 1, 1, 2 + 100 * 128 + 10000 * 2 + 100000 * 8),
-      ("5g layer4", 660, 512, 512, 7, 1, 1, 1, 2 + 100 * 128 + 10000 * 2 + 100000 * 8),
-      # SegmentationNet10a: every 3 x 3 layer on the block-tiled kernel (4), two buffers of 128-row blocks
-      ("potsdam c2", 75, 64, 128, 200, 1, 1, 3, None), ("potsdam c3", 75, 128, 256, 100, 1, 1, 3, None),
-      ("potsdam c4", 75, 256, 256, 100, 1, 1, 3, None), ("potsdam c5", 75, 256, 512, 100, 1, 2, 3, None),
-      ("potsdam c6", 75, 512, 512, 98, 1, 2, 3, None), ("coco c2", 120, 64, 128, 128, 1, 1, 3, None),
-      ("coco c3", 120, 128, 256, 64, 1, 1, 3, None), ("coco c4", 120, 256, 256, 64, 1, 1, 3, None),
-      ("coco c5", 120, 256, 512, 64, 1, 2, 3, None), ("coco c6", 120, 512, 512, 62, 1, 2, 3, None)]
-  for name, N, cin, cout, H, pad, dil, P, want in cases:
-    g = geom.fwd_geom(geom.ConvSpec(cin, cout, 3, 1, pad, dil), N, H, H, P, P)
-    got = L.iic_debug_wgrad_config(ctypes.byref(g))
-    if want is None:
-      assert got % 100 == 4 and (got % 1000000) == 4 + 100 * 128 + 10000 * 2, (name, got)   # block-tiled: 128-row blocks, 2 buffers
-    else:
-      assert got == want, (name, got, want)
