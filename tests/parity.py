@@ -54,6 +54,122 @@ def assert_within(got, ref, tol, what, family=None):
   assert not bool(bad.any()), "%s: %d elements outside the bound; worst |err| / bound = %g" % (what, int(bad.sum()), worst)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Convolutions: an accumulation bound and, for a bf16 store, the bracket it implies (tests/conv_f64_cases.py,
+# tests/test_conv_f64_cpu.py, tests/test_gpu_conv_f64.py, tests/test_gpu_p64_forms.py)
+# ----------------------------------------------------------------------------------------------------------------------
+BF16_MAX = (2.0 - 2.0 ** -7) * 2.0 ** 127
+
+
+def conv_acc_bound(terms, A, extra=0):
+  """|fp32 accumulator - exact sum| for a sum of `terms` products of bf16 operands, accumulated in fp32 in any order and
+  grouping: the products are exact in fp32 (8 x 8 significant bits), each of the at most `terms` additions rounds a
+  partial sum whose magnitude is at most A = sum |operand| |operand| (the same convolution applied to the magnitudes,
+  in float64), so each costs at most U32 * A -- whichever way it rounds.  `extra` counts further fp32 additions of
+  partial results of the same sum (the split-K fold of the weight gradient, the addition onto a previous dW, whose
+  magnitude the caller adds to A).  terms: forward taps * Cin; backward-data taps * Cout (an upper bound: a stride-2
+  parity class uses fewer); weight gradient N * Ho * Wo."""
+  return (terms + extra) * U32 * A
+
+
+def bf16_rne(v):
+  """float64 -> the nearest bf16 value, ties to even, as float64, in ONE rounding (torch's double -> bfloat16 passes
+  through float32 and so rounds twice).  Subnormal bf16 values (spacing 2^-133) and overflow to inf included; inf and
+  NaN pass through."""
+  v = torch.as_tensor(v, dtype=torch.float64)
+  fin = torch.isfinite(v)
+  z = torch.where(fin, v, torch.zeros_like(v))
+  q = bf16_spacing(z)
+  r = torch.round(z / q) * q                              # (z / q is exact; torch.round is half-to-even)
+  r = torch.where(r.abs() > BF16_MAX, torch.sign(r) * float("inf"), r)
+  return torch.where(fin, r, v)
+
+
+def bf16_spacing(v):
+  """Distance between neighbouring bf16 values at |v| (float64)."""
+  v = torch.as_tensor(v, dtype=torch.float64)
+  z = torch.where(torch.isfinite(v), v, torch.zeros_like(v))
+  _, e = torch.frexp(z)                                   # |z| in [2^(e-1), 2^e): 8 significant bits end at 2^(e-8)
+  e = torch.where(z == 0, torch.full_like(e, -125), e)
+  return torch.ldexp(torch.ones_like(v), e.clamp(min=-125) - 8)
+
+
+def bf16_bracket(ref, b):
+  """(lo, hi) = (bf16_rne(ref - b), bf16_rne(ref + b)), float64 tensors holding bf16 values.
+
+  Round-to-nearest-even is monotone: a kernel whose fp32 accumulator lies within b of the float64 reference and whose
+  store rounds it to nearest-even (v_cvt_pk_bf16_f32: csrc/common.h:205-213, f32_to_bf16 / pack_bf16x2) must store a
+  value in [lo, hi]; lo <= got <= hi is the whole assertion, no tolerance is tuned.  Where b is far below one bf16
+  spacing the bracket holds a single value (`decisive`): the check is bit-exact there and rejects a truncating store
+  and any intermediate error of bf16 size.  ref is float64 and bf16_rne rounds once, so no double rounding enters.
+
+  The rounding points of the conv kernels, as their code has them:
+    * accumulators -> bf16 tile in LDS, RNE: csrc/conv_igemm.hip:257, csrc/conv_igemm_bd.hip:442,
+      csrc/conv_igemm_p64.hip:453 (f32_to_bf16), csrc/conv_igemm_pw.hip:545 (pack_bf16x2);
+    * the BatchNorm statistics are taken from the fp32 accumulators BEFORE that rounding: csrc/conv_igemm.hip:215-248,
+      csrc/conv_igemm_bd.hip:410-432, csrc/conv_igemm_p64.hip:440 / 498, csrc/conv_igemm_pw.hip:517-521 / 589 (per-lane
+      fp32 partial sums, then the exact fixed-point cells of csrc/common.h:141-155);
+    * the epilogue igemm_store_tile (csrc/conv_tile.h:164-199; csrc/conv_igemm_pw.hip:113-178 repeats it) widens the
+      rounded tile to fp32, adds the previous contents (:169-173), then the residual gradient (:175-179 with
+      IIC_ACC_PREMASK, :188-195 without, where the ReLU mask gates the residual only), zeroes masked elements (:180-187)
+      and rounds ONCE more (:197, pack_bf16x2).  With no epilogue input the tile's bits are stored as they are (:200).
+  bf16_bracket_epilogue carries the bracket through those steps."""
+  ref, b = torch.as_tensor(ref, dtype=torch.float64), torch.as_tensor(b, dtype=torch.float64)
+  return bf16_rne(ref - b), bf16_rne(ref + b)
+
+
+def bf16_bracket_epilogue(lo, hi, prev=None, res_grad=None, res_act=None, premask=False):
+  """The bracket of the tile, carried through igemm_store_tile (bf16_bracket's docstring lists its steps).  Every step is
+  non-decreasing in the tile value t: a rounded fp32 addition of a fixed number is, the mask is (it maps to 0 or keeps),
+  and so is the final RNE.  So with t in [lo, hi] the stored value lies in [lo2, hi2],
+    lo2 = bf16_rne(lo + prev + rg - 3 U32 mag),   hi2 = bf16_rne(hi + prev + rg + 3 U32 mag),
+  mag = |t| + |prev| + |rg| at the respective end: at most two fp32 additions, each within U32 of a partial sum that mag
+  bounds, in either rounding direction -- 3 leaves one in hand.  rg = res_grad, gated by (res_act > 0) when premask is
+  off; with premask on the whole element is exactly zero where res_act <= 0 (or is NaN).  All arguments NCHW, float64 or
+  convertible, the epilogue inputs holding bf16 values."""
+  z = torch.zeros_like(lo)
+  prev = z if prev is None else prev.double()
+  rg = z if res_grad is None else res_grad.double()
+  keep = None if res_act is None else (res_act.double() > 0)
+  if keep is not None and not premask:
+    rg = torch.where(keep, rg, z)
+  out = []
+  for t, sign in ((lo, -1.0), (hi, 1.0)):
+    mag = t.abs() + prev.abs() + rg.abs()
+    v = bf16_rne(t + prev + rg + sign * 3 * U32 * mag)
+    if keep is not None and premask:
+      v = torch.where(keep, v, z)
+    out.append(v)
+  return out[0], out[1]
+
+
+def assert_in_bracket(got, lo, hi, what, family=None, ref=None, b=None):
+  """lo <= got <= hi element-wise (NaN fails).  With `family`, WORST[family] keeps two figures: `ratio`, the worst
+  |got - ref| / (b + bf16 spacing at ref) (ref, b: the float64 reference and the accumulation bound the bracket was made
+  from; a value inside its bracket stays below 1.5), and `decisive`, the smallest share of elements with lo == hi over
+  the calls -- that one from the reference alone."""
+  got, lo, hi = got.detach().cpu().double(), lo.double(), hi.double()
+  assert got.shape == lo.shape == hi.shape, (what, got.shape, lo.shape, hi.shape)
+  bad = ~((lo <= got) & (got <= hi))
+  if family is not None:
+    w = WORST.setdefault(family, {"ratio": 0.0, "decisive": 1.0, "elements": 0})
+    w["decisive"] = min(w["decisive"], float((lo == hi).double().mean()))
+    w["elements"] += got.numel()
+    if ref is not None:
+      den = torch.as_tensor(b, dtype=torch.float64) + bf16_spacing(ref)
+      w["ratio"] = max(w["ratio"], float(((got - ref.double()).abs() / den).nan_to_num(nan=float("inf")).max()))
+  if bool(bad.any()):
+    idx = tuple(int(i) for i in bad.nonzero()[0])
+    raise AssertionError("%s: %d of %d elements outside their bf16 bracket; first at %s: got %r, bracket [%r, %r]" % (
+      what, int(bad.sum()), bad.numel(), idx, float(got[idx]), float(lo[idx]), float(hi[idx])))
+
+
+def outside_share(got, lo, hi):
+  """Share of elements outside [lo, hi] (the CPU proof's rejection rates)."""
+  got = got.detach().cpu().double()
+  return float((~((lo <= got) & (got <= hi))).double().mean())
+
+
 def rnd(rng, *shape):
   return torch.from_numpy(rng.standard_normal(shape).astype(np.float32))
 

@@ -12,7 +12,8 @@ Every case is 64 -> 64, 3 x 3, pad 1, stride 1; the smallest shapes at which eac
   5 x 25 x 25, grid 3:   uneven tile ranges per workgroup (4, 4, 5), a row length other than the layer's own.
 One float64 assertion on the 13 x 13 case anchors the identity (two equally wrong kernels would pass it otherwise).  Its
 bound is in the units of tests/parity.py: the 576 products are exact in fp32, each of the 576 fp32 accumulations costs at
-most U32 of the magnitude sum A = sum |x| |w|, and the bf16 store U16 of the result: 576 U32 A + U16 |ref|."""
+most U32 of the magnitude sum A = sum |x| |w| (parity.conv_acc_bound), and the round-to-nearest-even store must then land in
+parity.bf16_bracket(ref, 576 U32 A), which lies inside the earlier 576 U32 A + U16 |ref|."""
 import ctypes
 
 import numpy as np
@@ -21,7 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.conftest import hook
-from tests.parity import U16, U32, assert_within
+from tests.parity import U16, assert_in_bracket, assert_within, bf16_bracket, conv_acc_bound
 
 pytestmark = [pytest.mark.gpu, pytest.mark.hooks]
 
@@ -163,11 +164,17 @@ def test_tile_loop_forms_are_bit_identical_with_the_fused_reduction(key):
 
 
 def test_new_form_matches_float64_convolution():
-  """Form 1, forward, 3 x 13 x 13, against F.conv2d in float64 on the bf16-rounded operands: 576 U32 A + U16 |ref|."""
+  """Form 1, forward, 3 x 13 x 13, against F.conv2d in float64 on the bf16-rounded operands: the fp32 accumulator lies
+  within conv_acc_bound(576, A) = 576 U32 A of it, so the stored value lies in bf16_bracket(ref, 576 U32 A)
+  (tests/parity.py) -- inside the earlier 576 U32 A + U16 |ref|, which is asserted as well."""
   from iic_amd import ops
   c = _case("13")
   _, new = _both_forms(c, c["gf"], lambda: _run(c, "fwd_stats"))
   xd, wd = c["x"].double(), c["w"].to(torch.bfloat16).double()
   ref = F.conv2d(xd, wd, stride=1, padding=1)
   A = F.conv2d(xd.abs(), wd.abs(), stride=1, padding=1)
-  assert_within(ops.pt_to_nchw(new[0], P).float(), ref, 576 * U32 * A + U16 * ref.abs(), "p64 form 1 forward")
+  b = conv_acc_bound(576, A)
+  lo, hi = bf16_bracket(ref, b)
+  got = ops.pt_to_nchw(new[0], P).float()
+  assert_in_bracket(got, lo, hi, "p64 form 1 forward", "conv64 forward p64-forms mixed", ref=ref, b=b)
+  assert_within(got, ref, b + U16 * ref.abs(), "p64 form 1 forward")
