@@ -649,6 +649,13 @@ int iic_stem_bwd_reduce(const float* x, const float* w, const float* coef, const
   int rc = stem_check(x, w, N, Cin, H, W);
   if (rc) return rc;
   if (!coef || !dpool_pt || !sums) return IIC_ERR_ARG;
+  // Where iic_stem_bwd_fused runs the register-resident kernel, so does this entry point, sums only: one routing code,
+  // one grid, one order of the fp32 partial sums -- the two entry points' sums are equal bit for bit on any operands
+  // (as those of stem_bwd_kernel<CIN, 0> and <CIN, 2> are elsewhere).
+  if (g_stem_bwd2 && iic_stem_bwd2_supported(Cin, W)) {
+    int nb = 0;
+    return iic_stem_bwd2_launch(x, w, coef, dpool_pt, sums, (float*)nullptr, &nb, N, Cin, H, W, stream);
+  }
   const int nseg = (W + 31) / 32, Ho = H / 2 + 1;
   long items = (long)N * Ho;
   int grid = (int)(items < STEM_PERSIST_BLOCKS ? items : STEM_PERSIST_BLOCKS);

@@ -15,7 +15,9 @@
 // input rows of the item (double-buffered, next item prefetched).
 #include "stem_common.h"
 
-template <int CIN>
+// GEMM = false: the sums alone (iic_stem_bwd_reduce) -- the same routing code on the same grid, hence the same fp32
+// partial sums in the same order: sum g and sum g*y equal those of the full kernel bit for bit; `partials` is not touched.
+template <int CIN, bool GEMM>
 __global__ __launch_bounds__(512) void stem_bwd2_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ coef,
                                                         const bf16_t* __restrict__ dpool,
@@ -221,6 +223,7 @@ __global__ __launch_bounds__(512) void stem_bwd2_kernel(const float* __restrict_
           }
         }
       // dW GEMMs of this half: A = g / y (channels x pixels), B = patch (pixels x k)
+      if (GEMM)
 #pragma unroll
       for (int rs = 0; rs < 2; ++rs) {
         if (!(rs ? rv1 : rv0)) continue;          // uniform: the whole row is outside the image
@@ -255,6 +258,7 @@ __global__ __launch_bounds__(512) void stem_bwd2_kernel(const float* __restrict_
   }
 
   // ---- block reduction: partial [128][32] = G1 rows 0..63, G2 rows 64..127; sums via atomics ----
+  if (GEMM) {
   for (int i = threadIdx.x; i < 128 * 33; i += blockDim.x) sRed[i] = 0.f;
   __syncthreads();
   // waves take turns in index order: a fixed summation order (LDS float atomics would add the
@@ -275,6 +279,7 @@ __global__ __launch_bounds__(512) void stem_bwd2_kernel(const float* __restrict_
   float* pout = partials + (long)blockIdx.x * 128 * 32;
   for (int i = threadIdx.x; i < 128 * 32; i += blockDim.x) pout[i] = sRed[(i >> 5) * 33 + (i & 31)];
   __syncthreads();
+  }
   // sums: lanes (l31, g5 = 0/1) hold the same channels -> fold halves, then waves through LDS
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -313,9 +318,15 @@ int iic_stem_bwd2_launch(const float* x, const float* w, const float* coef, cons
                      (size_t)2 * (((W / 2 + 1) * STEM_CO + 7) & ~7) * sizeof(bf16_t);
   // (above the 48 KB default from W = 104 at Cin = 3; 80 KB at the widest image, Cin = 3, W = 254)
   int rc = IIC_OK;
-#define BWD2_LAUNCH(CI_)                                                                          \
-  rc = iic_launch_lds<stem_bwd2_kernel<CI_>>(dim3(grid), dim3(64 * nseg), lds, (hipStream_t)stream, x, w, coef, \
-                                             (const bf16_t*)dpool_pt, partials, sums, N, H, W, iic_debug_get_ablate())
+  // partials == nullptr: the sums alone (iic_stem_bwd_reduce), same grid and block as the full kernel
+#define BWD2_LAUNCH2(CI_, GEMM_)                                                                  \
+  rc = iic_launch_lds<stem_bwd2_kernel<CI_, GEMM_>>(dim3(grid), dim3(64 * nseg), lds, (hipStream_t)stream, x, w, coef, \
+                                                    (const bf16_t*)dpool_pt, partials, sums, N, H, W, iic_debug_get_ablate())
+#define BWD2_LAUNCH(CI_)                      \
+  do {                                        \
+    if (partials) BWD2_LAUNCH2(CI_, true);    \
+    else BWD2_LAUNCH2(CI_, false);            \
+  } while (0)
   switch (Cin) {
     case 1: BWD2_LAUNCH(1); break;
     case 2: BWD2_LAUNCH(2); break;

@@ -1,5 +1,5 @@
 """Helpers shared by the float64 parity tests (tests/test_gpu_kernels_f64.py, tests/test_gpu_bn_bf16.py and the CPU proof of
-the latter's bounds, tests/test_bn_bf16_cpu.py): direct calls of the C entry points, bit / bound comparisons, PT tensors
+the latter's bounds, tests/test_bn_bf16_cpu.py; the convolution and first-layer files named further down): direct calls of the C entry points, bit / bound comparisons, PT tensors
 with a sentinel border and the mask inputs.  A plain module, not a test file: nothing here needs a GPU at import.
 
 Tolerances are derived, not tuned: U32 = 2^-24 per fp32 operation and U16 = 2^-8 per bf16 store -- one unit in the last
@@ -215,3 +215,75 @@ def _masked_g(dout, act, y, mcoef, mode):
   if mode == "mask_coef":
     return torch.where(y * mcoef[0] + mcoef[1] > 0, dout, torch.zeros_like(dout))
   return dout
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Exact-fp32 matrix pipe (stem, first conv, seg head): an accumulation bound for fp32 x fp32 products and the bracket of
+# "affine, ReLU, 2x2/2 max-pool with padding 1, one RNE store" (tests/first_layer_f64_cases.py,
+# tests/test_first_layer_f64_cpu.py, tests/test_gpu_first_layer_f64.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def fma_acc_bound(terms, A, extra=0):
+  """|fp32 accumulator - exact sum| for a sum of `terms` products of fp32 operands (a bf16 operand widened exactly is
+  one), accumulated in fp32 in any order and grouping, A = sum |operand| |operand| (the same operation on the
+  magnitudes, in float64):  n u / (1 - n u) * A,  u = U32 = 2^-24 (round to nearest), n = terms + extra + 1.
+
+  Derivation.  Write the computed sum as a binary tree whose leaves are the products p_i and whose inner nodes are fp32
+  additions (a chain is the degenerate tree; an accumulator that starts at zero adds 0 + p exactly; a fold of per-wave,
+  per-workgroup or split-K partials only joins subtrees).  A tree over `terms` leaves has terms - 1 inner nodes, so a leaf
+  lies under at most terms - 1 additions, each of which multiplies what is below it by (1 + d), |d| <= u:
+    computed = sum p_i prod_{j over i} (1 + d_j),   |computed - sum p_i| <= ((1 + u)^(terms-1) - 1) sum |p_i|.
+  * Fused (v_mfma_f32_*_f32 as an fmaf chain, which the kernels' headers state but no test establishes): a step rounds
+    p + partial once -- that is the addition above, and the products carry no rounding of their own.
+  * Not fused: every product is rounded first, p_i (1 + e_i), one more factor per leaf.  ALL the product roundings
+    together cost at most u sum |p_i| = u A -- one more unit of n, not one per term -- which is the `+ 1`: the bound
+    therefore holds for both, and nothing here presumes the fused form.
+  * `extra`: further fp32 additions that a value passes through and that are not joins of partials of this sum (the
+    acc + acc2 join of two chains is a join and needs none; the addition onto a previous result, a bias, or a fold the
+    caller prefers to count apart do).
+  (1 + u)^n - 1 <= n u / (1 - n u) for n u < 1 (Higham, Accuracy and Stability, lemma 3.1): second-order terms
+  included, so the bound also holds at the 40 000 terms of a 200 x 200 weight gradient."""
+  n = terms + extra + 1
+  assert n * U32 < 1
+  return (n * U32 / (1.0 - n * U32)) * A
+
+
+def affine_bound(y, b, sc, sh):
+  """z = sc y + sh in float64 and bz with |fp32 z - z| <= bz for the kernel's z = fl(acc * sc + sh), |acc - y| <= b,
+  fused or not:
+    not fused  fl(fl(acc sc) + sh): the product within u |acc sc|, the sum within u (|acc sc| (1 + u) + |sh|);
+    fused      one rounding of acc sc + sh, within u (|acc sc| + |sh|);
+  and |acc sc| <= |sc| (|y| + b), so
+    bz = |sc| b + 2 u (|sc y| + |sh|)  +  2 u |sc| b (1 + u) + u^2 |sc y|,
+  the last two being the second-order remainder of the same expansion, charged as (1 + 3 u) on the first-order terms.
+  sc, sh broadcast against y (NCHW: pass them as [1, C, 1, 1])."""
+  y, b, sc, sh = (torch.as_tensor(t, dtype=torch.float64) for t in (y, b, sc, sh))
+  z = sc * y + sh
+  bz = (sc.abs() * b + 2 * U32 * ((sc * y).abs() + sh.abs())) * (1 + 3 * U32)
+  return z, bz
+
+
+def pool_s2p1(a):
+  """2x2 / stride 2 / padding 1 max-pool of NCHW values >= 0 (post-ReLU: the padding is as good as zero)."""
+  return torch.nn.functional.max_pool2d(a, 2, 2, padding=1)
+
+
+def pooled_bracket(y, b, sc, sh):
+  """z, bz, lo, hi of bf16_rne(pool(relu(fl(acc sc + sh)))) for |acc - y| <= b.
+
+  ReLU, max and round-to-nearest-even are non-decreasing, and so is their composition in either order (the stem stores
+  f32_to_bf16(fmaxf(z, 0)) per pixel and takes the 2x2 max of the bf16 values: csrc/stem.hip stem_apply_pool_kernel --
+  rne(max) = max(rne)).  With the fp32 z within bz of the float64 z (affine_bound) the stored value lies in
+    [bf16_rne(pool(relu(z - bz))), bf16_rne(pool(relu(z + bz)))];
+  lo <= got <= hi is the whole assertion."""
+  z, bz = affine_bound(y, b, sc, sh)
+  lo = bf16_rne(pool_s2p1(torch.relu(z - bz)))
+  hi = bf16_rne(pool_s2p1(torch.relu(z + bz)))
+  return z, bz, lo, hi
+
+
+def bf16_half_spacing(v, err=0.0):
+  """Largest |bf16_rne(t) - t| over |t| <= |v| + err: half the bf16 spacing at |v| + err (the spacing does not decrease
+  with the magnitude).  This, not U16 / 2 relative, is what a round-to-nearest store costs: just above a power of two
+  half a spacing is 2^-8 |t|, just below the next one 2^-9 |t|."""
+  v = torch.as_tensor(v, dtype=torch.float64)
+  return 0.5 * bf16_spacing(v.abs() + err)

@@ -83,19 +83,32 @@ def test_seg_head_forward_backward(k, Hf, fused, C, monkeypatch):
   f = torch.from_numpy(rng.standard_normal((N, C, Hf, Hf)).astype(np.float32)).relu().to(torch.bfloat16).float()
   w = torch.from_numpy((rng.standard_normal((k, C, 1, 1)) * 0.05).astype(np.float32))
   ft, wt = f.clone().requires_grad_(True), w.clone().requires_grad_(True)
-  y = F.interpolate(F.softmax(F.conv2d(ft, wt, padding=1), dim=1), size=S, mode="bilinear", align_corners=False)
+  lg = F.conv2d(ft, wt, padding=1)
+  lg.retain_grad()
+  y = F.interpolate(F.softmax(lg, dim=1), size=S, mode="bilinear", align_corners=False)
   dy = torch.from_numpy(rng.standard_normal(tuple(y.shape)).astype(np.float32))
   y.backward(dy)
   d = dev()
   xp = ops.pt_from_nchw(f.to(d), P).requires_grad_(True)
   wd = w.to(d).requires_grad_(True)
+  used = []                                   # the dlog rows the backward pass hands to the dx and dW GEMMs
+  softmax_bwd = seg_mod.ops.softmax_bwd
+  monkeypatch.setattr(seg_mod.ops, "softmax_bwd", lambda *a: used.append(softmax_bwd(*a)) or used[-1])
   o = _SegHeadFn.apply(xp, wd, P, S)
   o.backward(dy.to(d))
   torch.cuda.synchronize()
   assert float((o.detach().cpu() - y.detach()).abs().max()) <= 2e-5
   assert torch.allclose(wd.grad.cpu(), wt.grad, rtol=1e-3, atol=1e-4 * float(wt.grad.abs().max()))
   gx = ops.pt_to_nchw(xp.grad, P).cpu()
-  assert _cos(gx, ft.grad) >= 0.9999
+  # every element inside the bf16 bracket of the float64 product of those dlog rows with W (k terms, one RNE store):
+  # a truncating store or a bf16-sized intermediate passes a cosine, not this
+  from tests import first_layer_f64_cases as fc
+  from tests.parity import assert_in_bracket
+  assert len(used) == 1 and tuple(used[0].shape) == (N * (Hf + 2) ** 2, k)
+  ref, b, lo, hi = fc.seg_dx_bracket(used[0], w, N, Hf + 2, Hf + 2)
+  assert_in_bracket(gx, lo, hi, "feature gradient of the seg head", "fl64 seg head autograd dx", ref=ref, b=b)
+  # (the rows themselves against torch's gradient of the logits, by the criterion the feature gradient was held to)
+  assert _cos(used[0].cpu().view(N, Hf + 2, Hf + 2, k).permute(0, 3, 1, 2), lg.grad) >= 0.9999
   assert xp.grad[:, :P].abs().max() == 0   # gradient of the conv's zero padding is dropped
   assert xp.grad[:, :, -P:].abs().max() == 0 and xp.grad[:, -P:].abs().max() == 0
   if fused and C % 256 == 0:                # the chunked weight gradient is order-fixed: bit-reproducible
