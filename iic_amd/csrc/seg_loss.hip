@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void seg_grad_kernel(
 
 
 // ====================================================================================
-// Streaming versions of the two kernels above (the default path whenever w % 4 == 0, k <= 32 and
+// Streaming versions of the two kernels above (the default path whenever w % 4 == 0 and
 // the tensors are 16-byte aligned).  Same tiles, same MFMA order -- identical results -- but the
 // row staging no longer serialises on memory latency: the generic kernels fetch one 4-byte element
 // per loop trip (a runtime division, a mask load and a source load each), i.e. ~50 dependent
@@ -432,8 +432,9 @@ __global__ __launch_bounds__(256, 2) void seg_joint_stream_kernel(
 // The same contractions on the bf16 matrix pipe (round 6): every fp32 operand element is split
 // into three bf16 terms  x = h + m + l  (h = bf16(x), m = bf16(x - h), l = bf16(x - h - m): 24 mantissa bits, the
 // subtractions are exact in fp32) and a product is the six MFMAs  h h', h m', m h', h l', l h', m m'  accumulated in
-// fp32 -- what is dropped (m l', l m', l l') is below 2^-24 of the product, i.e. inside the rounding of the exact-fp32
-// MFMA path itself (measured on the golden fixtures: the loss moves in its 8th digit).  One v_mfma_f32_16x16x32_bf16
+// fp32 -- what is dropped (m l', l m', l l') is at most 2^-23 + 2^-32 of the product (|m| <= 2^-8 |x|, |l| <= 2^-16 |x|:
+// tests/parity.py SPLIT_D) and typically below 2^-24, i.e. of the size of the rounding of the exact-fp32 MFMA path
+// itself (measured on the golden fixtures: the loss moves in its 8th digit).  One v_mfma_f32_16x16x32_bf16
 // covers 32 k values in 16 cycles where v_mfma_f32_16x16x4_f32 covers 4 in 32: six of them replace eight fp32 MFMAs at
 // 3/8 of the matrix-pipe time; the split costs ~36 VALU + 8 scalar LDS reads per 8-element fragment, paid once per
 // fragment, not per product.  That cost decides where this pays (see g_seg_bf16 below): the joint at k <= 16.
@@ -1135,8 +1136,11 @@ static bool seg_stream_ok(int k, int w, const void* a, const void* b, const void
 // at k = 15, w = 128): it does not fit.  Default (1): the joint at k <= 16, T >= 5 -- the only place it pays; the
 // gradient stays on the exact-fp32 MFMA.  iic_debug_seg_bf16(0): fp32 everywhere; (2): bf16 split everywhere (A/B, tests).
 IIC_SWITCH(g_seg_bf16, 1, iic_debug_seg_bf16)
-static bool seg_bf16_joint_ok(int k, int T) { return g_seg_bf16 == 2 || (g_seg_bf16 == 1 && T >= 5 && k <= 16); }
-static bool seg_bf16_grad_ok() { return g_seg_bf16 == 2; }
+// (the bf16 kernels are instantiated for one and two class tiles: 33 <= k <= 48 stays on the fp32 kernels in every mode)
+static bool seg_bf16_joint_ok(int k, int T) {
+  return seg_tk(k) <= 2 && (g_seg_bf16 == 2 || (g_seg_bf16 == 1 && T >= 5 && k <= 16));
+}
+static bool seg_bf16_grad_ok(int k) { return seg_tk(k) <= 2 && g_seg_bf16 == 2; }
 static int seg_qg(int tk) { return tk == 1 ? 21 : (tk == 2 ? 7 : 3); }
 // streaming joint kernel: row tiles per workgroup (accumulators) and the column shifts per group that
 // fill them -- groups balanced over the 2T+1 shifts
@@ -1232,7 +1236,7 @@ int iic_seg_grad(const float* src, const float* mask, const int* flips, const fl
   hipStream_t s = (hipStream_t)stream;
   int rc = IIC_OK;
   if (g_seg_stream && workspace && seg_stream_ok(k, w, src, mask, out) && ((uintptr_t)workspace & 15) == 0 &&
-      seg_bf16_grad_ok()) {
+      seg_bf16_grad_ok(k)) {
     // bf16-split path: as the streaming path below, classes padded to 8 per shift
     const int PG = 16 * tk, k8 = (k + 7) & ~7, rowsP = nq * k8;
     int QC = (256 * SEG_NG * 4 / PG) / k8;

@@ -287,3 +287,83 @@ def bf16_half_spacing(v, err=0.0):
   half a spacing is 2^-8 |t|, just below the next one 2^-9 |t|."""
   v = torch.as_tensor(v, dtype=torch.float64)
   return 0.5 * bf16_spacing(v.abs() + err)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# IID losses (csrc/iid_loss.hip, csrc/seg_loss.hip): the float64 k x k stage and the bf16 three-term split of the
+# segmentation joint (tests/iid_stage_cases.py, tests/test_iid_stages_cpu.py, tests/test_gpu_iid_stages.py)
+# ----------------------------------------------------------------------------------------------------------------------
+U64 = 2.0 ** -53
+
+
+def stage_n(k, nparts):
+  """Float64 roundings on the longest path from the fp32 partials to an output of the k x k stage, counted in the
+  kernels' code.  iid_loss_kernel (k < 96), an entry of dR:
+    nparts       the partial sums a, b (nparts - 1 additions each, they are parallel) and a + b; the 0.5 is exact
+    k k - 1      S: per-thread chain, six wave_sum_d steps, the fold of the per-wave values in block_sum_d -- a tree over
+                 k k leaves however it is grouped (additions of a zero padding lane are exact)
+    2            invS = 1 / S and P = Ps invS
+    k - 1        the marginal p_i (row sum of P: per-lane chain and wave_sum_d); the clamped row sum runs in parallel
+    1            log of the clamped marginal (charged as one rounding, as for every other operation)
+    10           the entry's d: lamb lj, lP - ., lamb li, - ., - 1, s_rc / p_i, rowi + colj, lamb (.), + ., and log Pc
+                 in parallel with log p_i (one of the two is on the path; both are charged: 10)
+    k k          g = sum d P: one product per term and a tree over k k leaves
+    2            (d - g) invS
+  n = nparts + 2 k k + k + 13.  The scalars stop after the sum of the k k loss terms (no `(d - g) invS`): fewer.
+  The four iid_big_* kernels (k >= 96) compute the same expressions: S and the four block sums are a per-thread chain,
+  wave_sum_d, block_sum_d and a fold over the 32 blocks in index order -- again trees over k k leaves -- and the per-row
+  logarithm and row term are computed once per row instead of per entry, which removes roundings from no path and adds
+  none.  Same count; n is the larger of the two because they are equal."""
+  return nparts + 2 * k * k + k + 13
+
+
+def stage_bound(ref, mag, k, nparts):
+  """|got - ref| for an fp32 output of the k x k stage: ONE fp32 rounding of a float64 computation,
+      U32 |ref| + 2 n u64 / (1 - 2 n u64) mag,   u64 = 2^-53, n = stage_n(k, nparts).
+  mag: sum of the magnitudes of the terms the output is made of, from the float64 reference (for the two scalars
+  M = sum Pc (|log Pc| + lamb |log p_i| + lamb |log p_j|); for an entry of dR the magnitudes of d's terms plus those of
+  g's, over S) -- a computed value is its exact value times a product of at most n factors (1 + e), |e| <= u64, hence
+  within n u64 / (1 - n u64) of it relative to the magnitudes (Higham, lemma 3.1).  The factor 2: the float64 reference
+  this is compared with performs the same operations in float64 (torch's sums in another grouping, of at most the same
+  depth) and so carries an error of the same form itself -- n for the kernel, n for the reference.  The fp32 store
+  rounds to nearest: half a spacing, which just above a power of two is U32 = 2^-24 of the value -- the first term is
+  attained (measured worst |err| / bound 0.997), so the bound has no room for a second fp32 rounding anywhere.
+  Not covered by the form above, stated rather than hidden: a relative error e in the ARGUMENT of a logarithm is an
+  absolute error e in its value, which mag charges as e |log|; where |log| < 1 (a marginal above 1 / e: k <= 2) that
+  undercounts by at most a factor 1 / |log|, against a count n that charges the k k-term sums at their worst case."""
+  n = 2 * stage_n(k, nparts)
+  assert n * U64 < 1
+  ref, mag = torch.as_tensor(ref, dtype=torch.float64), torch.as_tensor(mag, dtype=torch.float64)
+  return U32 * ref.abs() + (n * U64 / (1.0 - n * U64)) * mag
+
+
+# seg_split8 (csrc/seg_loss.hip): x = h + m + l with h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), each rounded to
+# nearest even, the subtractions exact in fp32.  bf16 has 8 significant bits: for 2^e <= |x| < 2^(e+1) its spacing is
+# 2^(e-7), so |x - h| <= 2^(e-8) <= 2^-8 |x| -- NOT 2^-9 |x|, which holds only in the upper half of a binade -- hence
+# |m| <= 2^-8 |x|, |x - h - m| <= 2^-8 |x - h| <= 2^-16 |x| and |l| <= 2^-16 |x|.  x - h lies on x's grid 2^(e-23) below
+# 2^(e-8) (16 bits), x - h - m on the same grid at or below 2^(e-16): at most 8 bits, so l holds it exactly and
+# x = h + m + l with no remainder (tests/test_iid_stages_cpu.py checks all three on every draw; no underflow: the
+# operands are floored at 2^-60).
+# The product x x' = (h + m + l)(h' + m' + l') has nine terms; seg_mfma6 keeps h h', h m', m h', h l', l h', m m' and
+# drops m l', l m', l l':  |dropped| <= (2 . 2^-8 2^-16 + 2^-32) |x x'| = (2^-23 + 2^-32) |x x'|.
+# The kernel's comment claimed "below 2^-24 of the product".  That is the typical size (m and l are spread over their
+# ranges and enter with both signs), not a bound: the worst case is twice that, and the bound below charges it.
+SPLIT_D = 2.0 ** -23 + 2.0 ** -32
+# sum of the magnitudes of the six kept products <= (|h| + |m| + |l|)(|h'| + |m'| + |l'|)
+#   <= (1 + 2^-8 + 2^-8 + 2^-16)^2 |x x'| < (1 + 2^-5) |x x'|
+SPLIT_KEPT = 1.0 + 2.0 ** -5
+
+
+def split_joint_bound(terms, A):
+  """|sum of fp32 partials - exact joint entry| for seg_joint_bf16_kernel: the six kept products of every pixel product
+  are exact in fp32 (8 x 8 bits) and accumulated in fp32 -- fma_acc_bound over 6 `terms` leaves whose magnitudes sum to
+  at most SPLIT_KEPT A -- plus the dropped products, SPLIT_D A.  A: the contraction on the magnitudes, float64."""
+  return fma_acc_bound_each(6 * torch.as_tensor(terms, dtype=torch.float64), SPLIT_KEPT * A) + SPLIT_D * A
+
+
+def fma_acc_bound_each(terms, A):
+  """fma_acc_bound with a term count per element (`terms` a tensor that broadcasts against A): the shifts of the
+  segmentation joint overlap in different numbers of pixels."""
+  n = torch.as_tensor(terms, dtype=torch.float64) + 1
+  assert float(n.max()) * U32 < 1
+  return (n * U32 / (1.0 - n * U32)) * A

@@ -236,7 +236,9 @@ def test_stream_kernels_match_generic_kernels_bitwise(bn, k, h, w, T, collapsed)
 
 
 @pytest.mark.parametrize("bn,k,h,w,T", [(3, 15, 20, 128, 10), (2, 24, 14, 200, 10), (2, 3, 9, 200, 5), (2, 9, 11, 64, 3),
-                                        (1, 32, 7, 40, 2), (2, 16, 6, 8, 1), (1, 1, 5, 256, 10), (2, 17, 3, 132, 4)])
+                                        (1, 32, 7, 40, 2), (2, 16, 6, 8, 1), (1, 1, 5, 256, 10), (2, 17, 3, 132, 4),
+                                        # three class tiles: the bf16 kernels have none, mode 2 stays on the fp32 ones
+                                        (2, 45, 4, 128, 10), (1, 33, 4, 132, 3)])
 @pytest.mark.parametrize("collapsed", [False, True])
 @pytest.mark.hooks
 def test_bf16_split_kernels_match_the_exact_fp32_mfma_kernels(bn, k, h, w, T, collapsed):
