@@ -302,15 +302,29 @@ __device__ __forceinline__ void seg_joint_ksteps(f32x4 (*acc)[TK], const float* 
   }
 }
 
-template <int TK, int MTMAX, int LW>
-__global__ __launch_bounds__(256, 2) void seg_joint_stream_kernel(
+// LDS of the streaming joint kernels, for the kernels and the launch plan alike: rows of wr pixels (w, or seg_w32(w)
+// on the bf16 pipe) -- sX1 [16*TK][P1] with the T-column halo on either side, then sX2 [16*TK][P2]; the cross-wave
+// reduction [4 waves][TK][256] reuses the same bytes.
+__host__ __device__ __forceinline__ int seg_joint_p1(int wr, int T) { return seg_pitch2(wr + 2 * T); }
+__host__ __device__ __forceinline__ int seg_joint_p2(int wr) { return seg_pitch2(wr); }
+__host__ __device__ __forceinline__ int seg_joint_lds_bytes(int tk, int wr, int T) {
+  const int rows_b = 16 * tk * (seg_joint_p1(wr, T) + seg_joint_p2(wr)) * (int)sizeof(float);
+  const int red_b = 4 * tk * 256 * (int)sizeof(float);
+  return rows_b > red_b ? rows_b : red_b;
+}
+
+// The streaming joint of one workgroup, all but the MFMA loop of a staged row: the work mapping, the row pipeline
+// (the loads of the NEXT row are issued right after the current one is published, and waited for after the MFMA loop)
+// and the cross-wave reduction.  wr = pixels per LDS row; ksteps(acc, sX1, sX2, aoff, P2, mt) consumes one staged row.
+template <int TK, int MTMAX, int LW, class KSteps>
+__device__ __forceinline__ void seg_joint_stream_rows(
     const float* __restrict__ x1, const float* __restrict__ x2, const float* __restrict__ mask,
-    const int* __restrict__ flips, float* __restrict__ part, int bn, int k, int h, int w, int T, int QG) {
+    const int* __restrict__ flips, float* __restrict__ part, int bn, int k, int h, int w, int T, int QG,
+    const int wr, const int wave, KSteps ksteps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int CR = 256 / LW, NJ = (16 * TK + CR - 1) / CR;
   const int nq = 2 * T + 1;
-  const int w4 = w;                                        // w % 4 == 0 here
-  const int P1 = seg_pitch2(w4 + 2 * T), P2 = seg_pitch2(w4);
+  const int P1 = seg_joint_p1(wr, T), P2 = seg_joint_p2(wr);
   float* sX1 = reinterpret_cast<float*>(smem_raw);          // [16*TK][P1]
   float* sX2 = sX1 + 16 * TK * P1;                          // [16*TK][P2]
   // workgroups are dealt round-robin to the 8 XCDs by linear id: keep all (row shift, shift group)
@@ -329,8 +343,8 @@ __global__ __launch_bounds__(256, 2) void seg_joint_stream_kernel(
     grp = pg / (int)gridDim.x;
   }
   const int q0 = grp * QG;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = lane & 15, kk = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int c = lane & 15;
   const int xl = tid % LW, cr = tid / LW, wq = w >> 2;
   const bool xact = xl < wq;
   const long rows = (long)bn * h;
@@ -400,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void seg_joint_stream_kernel(
     __syncthreads();
     const long rn = next_valid(r + 1);
     if (rn < r1) issue(rn);                          // in flight during the MFMA loop below
-    seg_joint_ksteps<TK, MTMAX, (TK == 1 ? 4 : (TK == 2 ? 3 : 2))>(acc, sX1, sX2, aoff, P2, w4 / 4, mt, wave, kk, c);
+    ksteps(acc, sX1, sX2, aoff, P2, mt);
     r = rn;
   }
   // cross-wave reduction, one row tile at a time, through LDS (reuses the row buffers)
@@ -425,6 +439,19 @@ __global__ __launch_bounds__(256, 2) void seg_joint_stream_kernel(
       }
     }
   }
+}
+
+template <int TK, int MTMAX, int LW>
+__global__ __launch_bounds__(256, 2) void seg_joint_stream_kernel(
+    const float* __restrict__ x1, const float* __restrict__ x2, const float* __restrict__ mask,
+    const int* __restrict__ flips, float* __restrict__ part, int bn, int k, int h, int w, int T, int QG) {
+  const int wave = threadIdx.x >> 6;
+  seg_joint_stream_rows<TK, MTMAX, LW>(                    // rows of w pixels: w % 4 == 0 here
+      x1, x2, mask, flips, part, bn, k, h, w, T, QG, w, wave,
+      [&](f32x4 (*acc)[TK], const float* sX1, const float* sX2, const int* aoff, int P2, int mt) {
+        const int lane = threadIdx.x & 63, c = lane & 15, kk = lane >> 4;
+        seg_joint_ksteps<TK, MTMAX, (TK == 1 ? 4 : (TK == 2 ? 3 : 2))>(acc, sX1, sX2, aoff, P2, w / 4, mt, wave, kk, c);
+      });
 }
 
 
@@ -474,140 +501,37 @@ template <int TK, int MTMAX, int LW>
 __global__ __launch_bounds__(256, 2) void seg_joint_bf16_kernel(
     const float* __restrict__ x1, const float* __restrict__ x2, const float* __restrict__ mask,
     const int* __restrict__ flips, float* __restrict__ part, int bn, int k, int h, int w, int T, int QG) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  constexpr int CR = 256 / LW, NJ = (16 * TK + CR - 1) / CR;
-  const int nq = 2 * T + 1;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int w32 = seg_w32(w);
-  const int P1 = seg_pitch2(w32 + 2 * T), P2 = seg_pitch2(w32);
-  float* sX1 = reinterpret_cast<float*>(smem_raw);          // [16*TK][P1]
-  float* sX2 = sX1 + 16 * TK * P1;                          // [16*TK][P2]
-  int p = blockIdx.x, grp = blockIdx.y, split = blockIdx.z;
-  const int S = gridDim.z;
-  if ((S & 7) == 0) {       // (XCD-aware slice mapping: see seg_joint_stream_kernel)
-    const int npg = gridDim.x * gridDim.y;
-    const int L = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    const int xcd = L & 7, j = L >> 3;
-    const int pg = j % npg;
-    split = xcd + 8 * (j / npg);
-    p = pg % (int)gridDim.x;
-    grp = pg / (int)gridDim.x;
-  }
-  const int q0 = grp * QG;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, kg = lane >> 4;
-  const int xl = tid % LW, cr = tid / LW, wq = w >> 2;
-  const bool xact = xl < wq;
-  const long rows = (long)bn * h;
-  const long per = (rows + S - 1) / S;
-  const long r0 = split * per, r1 = min(rows, r0 + per);
-  const int qn = min(QG, nq - q0);
-  const int mrows = qn * k, mt = (mrows + 15) >> 4;
-  const int nst = w32 >> 5;
-
-  f32x4 acc[MTMAX][TK];
-  int aoff[MTMAX];
+  seg_joint_stream_rows<TK, MTMAX, LW>(
+      x1, x2, mask, flips, part, bn, k, h, w, T, QG, w32, wave,
+      [&](f32x4 (*acc)[TK], const float* sX1, const float* sX2, const int* aoff, int P2, int mt) {
+        const int lane = threadIdx.x & 63, c = lane & 15, kg = lane >> 4;
+        const int nst = w32 >> 5;
+        for (int st = wave; st < nst; st += 4) {
+          const int x0 = 32 * st + 8 * kg;
+          bf16x8 bh[TK], bm[TK], bl[TK];
 #pragma unroll
-  for (int ti = 0; ti < MTMAX; ++ti) {
+          for (int tj = 0; tj < TK; ++tj) {
+            float v[8];
 #pragma unroll
-    for (int tj = 0; tj < TK; ++tj) acc[ti][tj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int m = ti * 16 + c, a = m / k, i = m - a * k;
-    aoff[ti] = m < mrows ? i * P1 + q0 + a : (16 * TK - 1) * P1;     // (ragged tiles read the all-zero padding channel)
-  }
-  for (int idx = tid; idx < 16 * TK * (P1 + P2); idx += 256) sX1[idx] = 0.f;
-
-  float4 pre1[NJ], pre2[NJ], m1, m2;
-  int pfx = 0;
-  auto next_valid = [&](long r) {
-    while (r < r1) {
-      const int y1 = (int)(r % h) + p - T;
-      if (y1 >= 0 && y1 < h) break;
-      ++r;
-    }
-    return r;
-  };
-  auto issue = [&](long r) {
-    const int n = (int)(r / h), y = (int)(r - (long)n * h), y1 = y + p - T;
-    const int fx = flips[2 * n], fy = flips[2 * n + 1];
-    const int sy = fy ? h - 1 - y : y, sx = fx ? wq - 1 - xl : xl;
-    pfx = fx;
-    if (xact) {
-      m2 = seg_ld4(mask + ((long)n * h + y) * w + 4 * xl);
-      m1 = seg_ld4(mask + ((long)n * h + y1) * w + 4 * xl);
+            for (int e = 0; e < 8; ++e) v[e] = sX2[(tj * 16 + c) * P2 + x0 + e];
+            seg_split8(v, bh[tj], bm[tj], bl[tj]);
+          }
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = cr + CR * j;
-        if (ch < k) {
-          pre2[j] = seg_ld4(x2 + (((long)n * k + ch) * h + sy) * w + 4 * sx);
-          pre1[j] = seg_ld4(x1 + (((long)n * k + ch) * h + y1) * w + 4 * xl);
+          for (int ti = 0; ti < MTMAX; ++ti) {
+            if (ti < mt) {
+              float v[8];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] = sX1[aoff[ti] + x0 + e];
+              bf16x8 ah, am, al;
+              seg_split8(v, ah, am, al);
+#pragma unroll
+              for (int tj = 0; tj < TK; ++tj) acc[ti][tj] = seg_mfma6(ah, am, al, bh[tj], bm[tj], bl[tj], acc[ti][tj]);
+            }
+          }
         }
-      }
-    }
-  };
-
-  long r = next_valid(r0);
-  if (r < r1) issue(r);
-  while (r < r1) {
-    __syncthreads();
-    if (xact) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = cr + CR * j;
-        if (ch < k) {
-          seg_store4(sX2 + ch * P2 + 4 * xl, pfx ? seg_rev4(pre2[j]) : pre2[j], m2);
-          seg_store4(sX1 + ch * P1 + T + 4 * xl, pre1[j], m1);
-        }
-      }
-    }
-    __syncthreads();
-    const long rn = next_valid(r + 1);
-    if (rn < r1) issue(rn);
-    for (int st = wave; st < nst; st += 4) {
-      const int x0 = 32 * st + 8 * kg;
-      bf16x8 bh[TK], bm[TK], bl[TK];
-#pragma unroll
-      for (int tj = 0; tj < TK; ++tj) {
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = sX2[(tj * 16 + c) * P2 + x0 + e];
-        seg_split8(v, bh[tj], bm[tj], bl[tj]);
-      }
-#pragma unroll
-      for (int ti = 0; ti < MTMAX; ++ti) {
-        if (ti < mt) {
-          float v[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = sX1[aoff[ti] + x0 + e];
-          bf16x8 ah, am, al;
-          seg_split8(v, ah, am, al);
-#pragma unroll
-          for (int tj = 0; tj < TK; ++tj) acc[ti][tj] = seg_mfma6(ah, am, al, bh[tj], bm[tj], bl[tj], acc[ti][tj]);
-        }
-      }
-    }
-    r = rn;
-  }
-  // cross-wave reduction, one row tile at a time, through LDS (reuses the row buffers)
-  float* red = reinterpret_cast<float*>(smem_raw);          // [4 waves][TK][256]
-#pragma unroll
-  for (int ti = 0; ti < MTMAX; ++ti) {
-    if (ti >= mt) continue;
-    __syncthreads();
-#pragma unroll
-    for (int tj = 0; tj < TK; ++tj)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) red[(wave * TK + tj) * 256 + lane * 4 + rr] = acc[ti][tj][rr];
-    __syncthreads();
-    for (int idx = tid; idx < TK * 256; idx += 256) {
-      const int tj = idx >> 8, e = idx & 255, ln = e >> 2, rr = e & 3;
-      const int m = ti * 16 + (ln >> 4) * 4 + rr, j = tj * 16 + (ln & 15);
-      if (m < mrows && j < k) {
-        const int a = m / k, i = m - a * k;
-        float* out = part + (((long)split * nq + p) * nq + q0 + a) * k * k;
-        out[(long)i * k + j] = red[(0 * TK + tj) * 256 + e] + red[(1 * TK + tj) * 256 + e] +
-                               red[(2 * TK + tj) * 256 + e] + red[(3 * TK + tj) * 256 + e];
-      }
-    }
-  }
+      });
 }
 
 // G of one launch, laid out as the gradient kernel's LDS image wants it:
@@ -616,7 +540,7 @@ __global__ __launch_bounds__(256, 2) void seg_joint_bf16_kernel(
 __global__ __launch_bounds__(256) void seg_gprep_kernel(
     const float* __restrict__ dR1, const float* __restrict__ dR2, const float* __restrict__ gl,
     const float* __restrict__ gnl, float* __restrict__ Gp, int k, int nq, int PG, int rowsP,
-    int which, int shift_stride, int k4) {       // k4: classes per shift, padded (4 | 8)
+    int which, int shift_stride, int k4) {
   const int p = blockIdx.x;
   const int idx = blockIdx.y * 256 + threadIdx.x;
   if (idx >= rowsP * PG) return;
@@ -661,47 +585,44 @@ __device__ __forceinline__ void seg_grad_ksteps(f32x4 (&acc)[4 * TK], const floa
   }
 }
 
-// K order of the streaming gradient kernel: (column shift q, class b padded to k4 = roundup4(k)),
-// so the four k-lanes of one MFMA step share q (the column offset is wave-uniform) and no lane
-// does index arithmetic inside the loop; the padded classes multiply zero rows of G and of the
-// source tile.  MFMA work is spread over the waves as (pixel tile, class tile) units, unit =
-// wave + 4u: 13 pixel tiles x 2 class tiles (w = 200, k = 24) split 7/7/6/6 instead of 8/6/6/6.
-template <int TK, int LW>
-__global__ __launch_bounds__(256) void seg_grad_stream_kernel(
+// LDS of the streaming gradient kernels, for the kernels and the launch plan alike: the masked source row
+// sS [k4][PS] with the T-column halo on either side, then, 16-byte aligned, one G slice sG [column shifts * k4][PG].
+__host__ __device__ __forceinline__ int seg_grad_ps(int w, int T) { return seg_pitch16(((w + 15) & ~15) + 2 * T); }
+__host__ __device__ __forceinline__ int seg_grad_g_off(int k4, int PS) { return (k4 * PS + 3) & ~3; }   // in floats
+__host__ __device__ __forceinline__ int seg_grad_slice_f4(int qn, int k4, int PG) { return qn * k4 * (PG / 4); }
+__host__ __device__ __forceinline__ int seg_grad_lds_bytes(int k4, int w, int T, int QC, int PG) {
+  return (seg_grad_g_off(k4, seg_grad_ps(w, T)) + 4 * seg_grad_slice_f4(QC, k4, PG)) * (int)sizeof(float);
+}
+
+// workgroups are dealt round-robin to the 8 XCDs: give each XCD a contiguous band of output rows
+// so that the 2T+1 source rows a workgroup reads are the ones its L2 neighbours just fetched
+__device__ __forceinline__ int seg_grad_row() {
+  const int per8 = gridDim.x >> 3;                         // grid = 8 * ceil(bn*h / 8)
+  return (blockIdx.x & 7) * per8 + (blockIdx.x >> 3);
+}
+
+// The streaming gradient of output row (n, y), all but the MFMA loop of a G slice: items (row shift p, slice ch_)
+// are staged one ahead -- the G slice of every item, the source row with the first slice of a row shift.
+// ksteps(sS, sG, PS, k4, qn, xoff0, sgn) consumes one staged slice of qn column shifts.
+template <int TK, int LW, class KSteps>
+__device__ __forceinline__ void seg_grad_stream_rows(
     const float* __restrict__ src, const float* __restrict__ mask, const int* __restrict__ flips,
-    const float* __restrict__ Gp, float* __restrict__ out, int bn, int k, int h, int w, int T,
-    int which, int src_is_x2, int QC, int rowsP) {
+    const float* __restrict__ Gp, int k, int h, int w, int T, int which, int src_is_x2, int QC, int rowsP,
+    const int n, const int y, KSteps ksteps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int CR = 256 / LW, NJ = (16 * TK + CR - 1) / CR;
   constexpr int PG = 16 * TK;
-  constexpr int NU = 4 * TK;                               // MFMA units per wave (w <= 256)
   const int nq = 2 * T + 1;
   const int k4 = (k + 3) & ~3;
-  const int w16 = (w + 15) & ~15;
-  const int PS = seg_pitch16(w16 + 2 * T);
+  const int PS = seg_grad_ps(w, T);
   float* sS = reinterpret_cast<float*>(smem_raw);          // [k4][PS]     masked source row
-  float* sG = sS + (((long)k4 * PS + 3) & ~3L);            // [slice rows][PG], 16-byte aligned
-  // workgroups are dealt round-robin to the 8 XCDs: give each XCD a contiguous band of output rows
-  // so that the 2T+1 source rows a workgroup reads are the ones its L2 neighbours just fetched
-  const int per8 = gridDim.x >> 3;                         // grid = 8 * ceil(bn*h / 8)
-  const int row = (blockIdx.x & 7) * per8 + (blockIdx.x >> 3);
-  if (row >= bn * h) return;
-  const int n = row / h, y = row - n * h;
-  const int tid = threadIdx.x, lane = tid & 63;
-  // the waves owning one MFMA unit more (units = wave + 4u) sit on different SIMDs in the two
-  // workgroups a CU holds at a time (dispatch fills a CU's second slot 32 workgroups later)
-  const int wave = ((tid >> 6) + 2 * ((blockIdx.x >> 8) & 1)) & 3;
-  const int c = lane & 15, kk = lane >> 4;
+  float* sG = sS + seg_grad_g_off(k4, PS);                 // [slice rows][PG], 16-byte aligned
+  const int tid = threadIdx.x;
   const int xl = tid % LW, cr = tid / LW, wq = w >> 2;
   const bool xact = xl < wq;
   const int sgn = which == 0 ? -1 : 1;
   const int fx = src_is_x2 ? flips[2 * n] : 0, fy = src_is_x2 ? flips[2 * n + 1] : 0;
-  const int nunit = (w16 / 16) * TK;
   const int nch = (nq + QC - 1) / QC;                      // G slices per row shift
-  const int nu = nunit > wave ? (nunit - wave + 3) / 4 : 0;   // units of this wave (uniform)
-  f32x4 acc[NU];
-#pragma unroll
-  for (int u = 0; u < NU; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int idx = tid; idx < k4 * PS; idx += 256) sS[idx] = 0.f;   // halo + padded classes stay zero
 
   float4 pres[NJ], pm, preg[SEG_NG];
@@ -716,7 +637,7 @@ __global__ __launch_bounds__(256) void seg_grad_stream_kernel(
   // item = (row shift p, slice ch_): loads the G slice, plus the source row when ch_ == 0
   auto issue = [&](int p, int ch_) {
     const float* g = Gp + ((long)p * rowsP + (long)ch_ * QC * k4) * PG;
-    const int nf4 = min(QC, nq - ch_ * QC) * k4 * (PG / 4);
+    const int nf4 = seg_grad_slice_f4(min(QC, nq - ch_ * QC), k4, PG);
 #pragma unroll
     for (int j = 0; j < SEG_NG; ++j) {
       const int f = tid + 256 * j;
@@ -735,22 +656,13 @@ __global__ __launch_bounds__(256) void seg_grad_stream_kernel(
       }
     }
   };
-  // per-unit constants: pixel tile -> column base in the source row, class tile -> column in G
-  int ubase[NU], gcol[NU];
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const int unit = wave + 4 * u;
-    const int tile = unit / TK, t = unit - tile * TK;
-    ubase[u] = tile * 16 + c;
-    gcol[u] = t * 16 + c;
-  }
 
   int p = next_valid(0), ch_ = 0;
   if (p < nq) issue(p, 0);
   while (p < nq) {
     __syncthreads();
     {
-      const int nf4 = min(QC, nq - ch_ * QC) * k4 * (PG / 4);
+      const int nf4 = seg_grad_slice_f4(min(QC, nq - ch_ * QC), k4, PG);
 #pragma unroll
       for (int j = 0; j < SEG_NG; ++j) {
         const int f = tid + 256 * j;
@@ -777,42 +689,85 @@ __global__ __launch_bounds__(256) void seg_grad_stream_kernel(
     if (pn < nq) issue(pn, cn);
     {
       const int qc0 = ch_ * QC;
-      const int qn = min(QC, nq - qc0);
-      const int xoff0 = sgn * (qc0 - T) + T;
-      // (a wave's units all use the same class tile: unit = wave + 4u and TK divides 4)
-#define SEG_KS(N_) seg_grad_ksteps<TK, N_>(acc, sS, sG, gcol[0], PS, k4, qn, xoff0, sgn, kk, ubase)
-      switch (nu) {
-        case 1: SEG_KS(1); break;
-        case 2: SEG_KS(2); break;
-        case 3: SEG_KS(3); break;
-        case 4: SEG_KS(4); break;
-        case 5: if (TK == 2) SEG_KS(5); break;
-        case 6: if (TK == 2) SEG_KS(6); break;
-        case 7: if (TK == 2) SEG_KS(7); break;
-        case 8: if (TK == 2) SEG_KS(8); break;
-        default: break;
-      }
-#undef SEG_KS
+      ksteps(sS, sG, PS, k4, min(QC, nq - qc0), sgn * (qc0 - T) + T, sgn);
     }
     p = pn; ch_ = cn;
   }
+}
+
+// One accumulator tile of output row (n, y) -> out: D[row = pixel (lane>>4)*4 + r][col = class a]; x mask; un-flip
+// for d/dx2.
+__device__ __forceinline__ void seg_grad_store(f32x4 v, int tile, int a, float* __restrict__ out,
+                                               const float* __restrict__ mask, const int* __restrict__ flips,
+                                               int n, int y, int k, int h, int w, int which, int src_is_x2, int kk) {
+  if (a >= k) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int x = tile * 16 + kk * 4 + r;
+    if (x < w) {
+      const int oy = (src_is_x2 == 0 && which == 1 && flips[2 * n + 1]) ? h - 1 - y : y;
+      const int ox = (src_is_x2 == 0 && which == 1 && flips[2 * n]) ? w - 1 - x : x;
+      out[(((long)n * k + a) * h + oy) * w + ox] = v[r] * mask[((long)n * h + y) * w + x];
+    }
+  }
+}
+
+// K order of the streaming gradient kernel: (column shift q, class b padded to k4 = roundup4(k)),
+// so the four k-lanes of one MFMA step share q (the column offset is wave-uniform) and no lane
+// does index arithmetic inside the loop; the padded classes multiply zero rows of G and of the
+// source tile.  MFMA work is spread over the waves as (pixel tile, class tile) units, unit =
+// wave + 4u: 13 pixel tiles x 2 class tiles (w = 200, k = 24) split 7/7/6/6 instead of 8/6/6/6.
+template <int TK, int LW>
+__global__ __launch_bounds__(256) void seg_grad_stream_kernel(
+    const float* __restrict__ src, const float* __restrict__ mask, const int* __restrict__ flips,
+    const float* __restrict__ Gp, float* __restrict__ out, int bn, int k, int h, int w, int T,
+    int which, int src_is_x2, int QC, int rowsP) {
+  constexpr int NU = 4 * TK;                               // MFMA units per wave (w <= 256)
+  const int row = seg_grad_row();
+  if (row >= bn * h) return;
+  const int n = row / h, y = row - n * h;
+  const int tid = threadIdx.x, lane = tid & 63;
+  // the waves owning one MFMA unit more (units = wave + 4u) sit on different SIMDs in the two
+  // workgroups a CU holds at a time (dispatch fills a CU's second slot 32 workgroups later)
+  const int wave = ((tid >> 6) + 2 * ((blockIdx.x >> 8) & 1)) & 3;
+  const int c = lane & 15, kk = lane >> 4;
+  const int nunit = (((w + 15) & ~15) / 16) * TK;
+  const int nu = nunit > wave ? (nunit - wave + 3) / 4 : 0;   // units of this wave (uniform)
+  f32x4 acc[NU];
+  // per-unit constants: pixel tile -> column base in the source row, class tile -> column in G
+  int ubase[NU], gcol[NU];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int unit = wave + 4 * u;
+    const int tile = unit / TK, t = unit - tile * TK;
+    ubase[u] = tile * 16 + c;
+    gcol[u] = t * 16 + c;
+  }
+  seg_grad_stream_rows<TK, LW>(
+      src, mask, flips, Gp, k, h, w, T, which, src_is_x2, QC, rowsP, n, y,
+      [&](const float* sS, const float* sG, int PS, int k4, int qn, int xoff0, int sgn) {
+        // (a wave's units all use the same class tile: unit = wave + 4u and TK divides 4)
+#define SEG_KS(N_) seg_grad_ksteps<TK, N_>(acc, sS, sG, gcol[0], PS, k4, qn, xoff0, sgn, kk, ubase)
+        switch (nu) {
+          case 1: SEG_KS(1); break;
+          case 2: SEG_KS(2); break;
+          case 3: SEG_KS(3); break;
+          case 4: SEG_KS(4); break;
+          case 5: if (TK == 2) SEG_KS(5); break;
+          case 6: if (TK == 2) SEG_KS(6); break;
+          case 7: if (TK == 2) SEG_KS(7); break;
+          case 8: if (TK == 2) SEG_KS(8); break;
+          default: break;
+        }
+#undef SEG_KS
+      });
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     const int unit = wave + 4 * u;
     if (unit >= nunit) continue;
     const int tile = unit / TK, t = unit - tile * TK;
-    const int a = t * 16 + c;
-    if (a >= k) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int x = tile * 16 + kk * 4 + r;
-      if (x < w) {
-        const float v = acc[u][r] * mask[((long)n * h + y) * w + x];
-        const int oy = (src_is_x2 == 0 && which == 1 && flips[2 * n + 1]) ? h - 1 - y : y;
-        const int ox = (src_is_x2 == 0 && which == 1 && flips[2 * n]) ? w - 1 - x : x;
-        out[(((long)n * k + a) * h + oy) * w + ox] = v;
-      }
-    }
+    seg_grad_store(acc[u], tile, t * 16 + c, out, mask, flips, n, y, k, h, w, which, src_is_x2, kk);
   }
 }
 
@@ -827,304 +782,64 @@ __global__ __launch_bounds__(256) void seg_grad_stream3_kernel(
     const float* __restrict__ src, const float* __restrict__ mask, const int* __restrict__ flips,
     const float* __restrict__ Gp, float* __restrict__ out, int bn, int k, int h, int w, int T,
     int which, int src_is_x2, int QC, int rowsP) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int TK = 3;
-  constexpr int CR = 256 / LW, NJ = (16 * TK + CR - 1) / CR;
   constexpr int PG = 16 * TK;
   constexpr int NPT = 4;                                   // pixel tiles per wave (w <= 256)
-  const int nq = 2 * T + 1;
-  const int k4 = (k + 3) & ~3;
-  const int w16 = (w + 15) & ~15;
-  const int PS = seg_pitch16(w16 + 2 * T);
-  float* sS = reinterpret_cast<float*>(smem_raw);          // [k4][PS]
-  float* sG = sS + (((long)k4 * PS + 3) & ~3L);            // [slice rows][PG]
-  const int per8 = gridDim.x >> 3;
-  const int row = (blockIdx.x & 7) * per8 + (blockIdx.x >> 3);
+  const int row = seg_grad_row();
   if (row >= bn * h) return;
   const int n = row / h, y = row - n * h;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 15, kk = lane >> 4;
-  const int xl = tid % LW, cr = tid / LW, wq = w >> 2;
-  const bool xact = xl < wq;
-  const int sgn = which == 0 ? -1 : 1;
-  const int fx = src_is_x2 ? flips[2 * n] : 0, fy = src_is_x2 ? flips[2 * n + 1] : 0;
-  const int ntile = w16 / 16;
+  const int ntile = ((w + 15) & ~15) / 16;
   const int npt = ntile > wave ? (ntile - wave + 3) / 4 : 0;      // pixel tiles of this wave (uniform)
-  const int nch = (nq + QC - 1) / QC;
   f32x4 acc[NPT][TK];
-#pragma unroll
-  for (int u = 0; u < NPT; ++u)
-#pragma unroll
-    for (int t = 0; t < TK; ++t) acc[u][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int idx = tid; idx < k4 * PS; idx += 256) sS[idx] = 0.f;
-
-  float4 pres[NJ], pm, preg[SEG_NG];
-  auto next_valid = [&](int p) {
-    while (p < nq) {
-      const int ys = y + sgn * (p - T);
-      if (ys >= 0 && ys < h) break;
-      ++p;
-    }
-    return p;
-  };
-  auto issue = [&](int p, int ch_) {
-    const float* g = Gp + ((long)p * rowsP + (long)ch_ * QC * k4) * PG;
-    const int nf4 = min(QC, nq - ch_ * QC) * k4 * (PG / 4);
-#pragma unroll
-    for (int j = 0; j < SEG_NG; ++j) {
-      const int f = tid + 256 * j;
-      if (f < nf4) preg[j] = seg_ld4(g + 4 * f);
-    }
-    if (ch_ == 0 && xact) {
-      const int ys = y + sgn * (p - T);
-      const int sy = fy ? h - 1 - ys : ys, sx = fx ? wq - 1 - xl : xl;
-      pm = seg_ld4(mask + ((long)n * h + ys) * w + 4 * xl);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = cr + CR * j;
-        if (ch < k) pres[j] = seg_ld4(src + (((long)n * k + ch) * h + sy) * w + 4 * sx);
-      }
-    }
-  };
   int ubase[NPT];
 #pragma unroll
-  for (int u = 0; u < NPT; ++u) ubase[u] = (wave + 4 * u) * 16 + c;
-
-  int p = next_valid(0), ch_ = 0;
-  if (p < nq) issue(p, 0);
-  while (p < nq) {
-    __syncthreads();
-    {
-      const int nf4 = min(QC, nq - ch_ * QC) * k4 * (PG / 4);
+  for (int u = 0; u < NPT; ++u) {
 #pragma unroll
-      for (int j = 0; j < SEG_NG; ++j) {
-        const int f = tid + 256 * j;
-        if (f < nf4) *reinterpret_cast<float4*>(sG + 4 * f) = preg[j];
-      }
-    }
-    if (ch_ == 0 && xact) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = cr + CR * j;
-        if (ch < k) seg_store4(sS + ch * PS + T + 4 * xl, fx ? seg_rev4(pres[j]) : pres[j], pm);
-      }
-    }
-    __syncthreads();
-    int pn = p, cn = ch_ + 1;
-    if (cn == nch) { cn = 0; pn = next_valid(p + 1); }
-    if (pn < nq) issue(pn, cn);
-    {
-      const int qc0 = ch_ * QC;
-      const int qn = min(QC, nq - qc0);
-      const int xoff0 = sgn * (qc0 - T) + T;
-      for (int ql = 0; ql < qn; ++ql) {
-        const int xoff = xoff0 + sgn * ql;
-        const float* sGq = sG + ql * k4 * PG;
-        for (int b0 = 0; b0 < k4; b0 += 4) {
-          const int b = b0 + kk;
-          const float* srow = sS + b * PS + xoff;
-          float bv[TK], av[NPT];
-#pragma unroll
-          for (int t = 0; t < TK; ++t) bv[t] = sGq[b * PG + t * 16 + c];
-#pragma unroll
-          for (int u = 0; u < NPT; ++u) av[u] = u < npt ? srow[ubase[u]] : 0.f;
-#pragma unroll
-          for (int u = 0; u < NPT; ++u)
-            if (u < npt) {
-#pragma unroll
-              for (int t = 0; t < TK; ++t) acc[u][t] = mfma16(av[u], bv[t], acc[u][t]);
-            }
-        }
-      }
-    }
-    p = pn; ch_ = cn;
+    for (int t = 0; t < TK; ++t) acc[u][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    ubase[u] = (wave + 4 * u) * 16 + c;
   }
+  seg_grad_stream_rows<TK, LW>(
+      src, mask, flips, Gp, k, h, w, T, which, src_is_x2, QC, rowsP, n, y,
+      [&](const float* sS, const float* sG, int PS, int k4, int qn, int xoff0, int sgn) {
+        for (int ql = 0; ql < qn; ++ql) {
+          const int xoff = xoff0 + sgn * ql;
+          const float* sGq = sG + ql * k4 * PG;
+          for (int b0 = 0; b0 < k4; b0 += 4) {
+            const int b = b0 + kk;
+            const float* srow = sS + b * PS + xoff;
+            float bv[TK], av[NPT];
+#pragma unroll
+            for (int t = 0; t < TK; ++t) bv[t] = sGq[b * PG + t * 16 + c];
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) av[u] = u < npt ? srow[ubase[u]] : 0.f;
+#pragma unroll
+            for (int u = 0; u < NPT; ++u)
+              if (u < npt) {
+#pragma unroll
+                for (int t = 0; t < TK; ++t) acc[u][t] = mfma16(av[u], bv[t], acc[u][t]);
+              }
+          }
+        }
+      });
 #pragma unroll
   for (int u = 0; u < NPT; ++u) {
     const int tile = wave + 4 * u;
     if (tile >= ntile) continue;
 #pragma unroll
-    for (int t = 0; t < TK; ++t) {
-      const int a = t * 16 + c;
-      if (a >= k) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int x = tile * 16 + kk * 4 + r;
-        if (x < w) {
-          const float v = acc[u][t][r] * mask[((long)n * h + y) * w + x];
-          const int oy = (src_is_x2 == 0 && which == 1 && flips[2 * n + 1]) ? h - 1 - y : y;
-          const int ox = (src_is_x2 == 0 && which == 1 && flips[2 * n]) ? w - 1 - x : x;
-          out[(((long)n * k + a) * h + oy) * w + ox] = v;
-        }
-      }
-    }
-  }
-}
-
-
-// Gradient on the bf16 pipe.  Same staging, unit split and output as seg_grad_stream_kernel; K is ordered (column
-// shift q, class b padded to k8 = roundup8(k)) and consumed 32 at a time: lane (pixel / class column c, k group kg)
-// holds the 8 classes of ONE octet o = 4 s + kg -> (shift ql = o / K8, classes 8 (o % K8) .. + 7), so the column
-// offset is per k group (per lane), not per wave.  Octets past the slice end contribute zeros.
-template <int TK, int LW>
-__global__ __launch_bounds__(256) void seg_grad_bf16_kernel(
-    const float* __restrict__ src, const float* __restrict__ mask, const int* __restrict__ flips,
-    const float* __restrict__ Gp, float* __restrict__ out, int bn, int k, int h, int w, int T,
-    int which, int src_is_x2, int QC, int rowsP) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  constexpr int CR = 256 / LW, NJ = (16 * TK + CR - 1) / CR;
-  constexpr int PG = 16 * TK;
-  constexpr int NU = 4 * TK;
-  const int nq = 2 * T + 1;
-  const int k8 = (k + 7) & ~7, K8 = k8 >> 3;
-  const int w16 = (w + 15) & ~15;
-  const int PS = seg_pitch16(w16 + 2 * T);
-  float* sS = reinterpret_cast<float*>(smem_raw);          // [k8][PS]     masked source row
-  float* sG = sS + (((long)k8 * PS + 3) & ~3L);            // [slice rows][PG]
-  const int per8 = gridDim.x >> 3;
-  const int row = (blockIdx.x & 7) * per8 + (blockIdx.x >> 3);
-  if (row >= bn * h) return;
-  const int n = row / h, y = row - n * h;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = (__builtin_amdgcn_readfirstlane(tid >> 6) + 2 * ((blockIdx.x >> 8) & 1)) & 3;
-  const int c = lane & 15, kg = lane >> 4;
-  const int xl = tid % LW, cr = tid / LW, wq = w >> 2;
-  const bool xact = xl < wq;
-  const int sgn = which == 0 ? -1 : 1;
-  const int fx = src_is_x2 ? flips[2 * n] : 0, fy = src_is_x2 ? flips[2 * n + 1] : 0;
-  const int nunit = (w16 / 16) * TK;
-  const int nch = (nq + QC - 1) / QC;
-  const int nu = nunit > wave ? (nunit - wave + 3) / 4 : 0;
-  f32x4 acc[NU];
-#pragma unroll
-  for (int u = 0; u < NU; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int idx = tid; idx < k8 * PS; idx += 256) sS[idx] = 0.f;   // halo + padded classes stay zero
-
-  float4 pres[NJ], pm, preg[SEG_NG];
-  auto next_valid = [&](int p) {
-    while (p < nq) {
-      const int ys = y + sgn * (p - T);
-      if (ys >= 0 && ys < h) break;
-      ++p;
-    }
-    return p;
-  };
-  auto issue = [&](int p, int ch_) {
-    const float* g = Gp + ((long)p * rowsP + (long)ch_ * QC * k8) * PG;
-    const int nf4 = min(QC, nq - ch_ * QC) * k8 * (PG / 4);
-#pragma unroll
-    for (int j = 0; j < SEG_NG; ++j) {
-      const int f = tid + 256 * j;
-      if (f < nf4) preg[j] = seg_ld4(g + 4 * f);
-    }
-    if (ch_ == 0 && xact) {
-      const int ys = y + sgn * (p - T);
-      const int sy = fy ? h - 1 - ys : ys, sx = fx ? wq - 1 - xl : xl;
-      pm = seg_ld4(mask + ((long)n * h + ys) * w + 4 * xl);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = cr + CR * j;
-        if (ch < k) pres[j] = seg_ld4(src + (((long)n * k + ch) * h + sy) * w + 4 * sx);
-      }
-    }
-  };
-  int ubase[NU];
-#pragma unroll
-  for (int u = 0; u < NU; ++u) ubase[u] = ((wave + 4 * u) / TK) * 16 + c;
-  const int gc = ((wave % TK) * 16) + c;                  // (a wave's units all use one class tile: TK divides 4)
-
-  int p = next_valid(0), ch_ = 0;
-  if (p < nq) issue(p, 0);
-  while (p < nq) {
-    __syncthreads();
-    {
-      const int nf4 = min(QC, nq - ch_ * QC) * k8 * (PG / 4);
-#pragma unroll
-      for (int j = 0; j < SEG_NG; ++j) {
-        const int f = tid + 256 * j;
-        if (f < nf4) {
-          const int rr = (4 * f) / PG, a = 4 * f - rr * PG;
-          const int as = TK == 2 ? (a ^ ((rr & 1) << 4)) : a;
-          *reinterpret_cast<float4*>(sG + rr * PG + as) = preg[j];
-        }
-      }
-    }
-    if (ch_ == 0 && xact) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = cr + CR * j;
-        if (ch < k) seg_store4(sS + ch * PS + T + 4 * xl, fx ? seg_rev4(pres[j]) : pres[j], pm);
-      }
-    }
-    __syncthreads();
-    int pn = p, cn = ch_ + 1;
-    if (cn == nch) { cn = 0; pn = next_valid(p + 1); }
-    if (pn < nq) issue(pn, cn);
-    {
-      const int qc0 = ch_ * QC;
-      const int qn = min(QC, nq - qc0);
-      const int xoff0 = sgn * (qc0 - T) + T;
-      const int noct = qn * K8;
-      // this lane's octet walks o = kg, kg + 4, ...: (ql, oc) kept incrementally (K8 <= 4: at most 4 wraps per step)
-      int ql = 0, oc = kg;
-      while (oc >= K8) { oc -= K8; ++ql; }
-      for (int o0 = 0; o0 < noct; o0 += 4) {
-        const bool kv = o0 + kg < noct;
-        const int b0 = 8 * oc;
-        const float* srow = sS + b0 * PS + xoff0 + sgn * ql;
-        const float* grow = sG + (ql * k8 + b0) * PG;
-        float gv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gv[e] = kv ? grow[e * PG + (TK == 2 ? (gc ^ ((e & 1) << 4)) : gc)] : 0.f;
-        bf16x8 bh, bm, bl;
-        seg_split8(gv, bh, bm, bl);
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-          if (u < nu) {
-            float av[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) av[e] = kv ? srow[e * PS + ubase[u]] : 0.f;
-            bf16x8 ah, am, al;
-            seg_split8(av, ah, am, al);
-            acc[u] = seg_mfma6(ah, am, al, bh, bm, bl, acc[u]);
-          }
-        }
-        oc += 4;
-        while (oc >= K8) { oc -= K8; ++ql; }
-      }
-    }
-    p = pn; ch_ = cn;
-  }
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const int unit = wave + 4 * u;
-    if (unit >= nunit) continue;
-    const int tile = unit / TK, t = unit - tile * TK;
-    const int a = t * 16 + c;
-    if (a >= k) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int x = tile * 16 + kg * 4 + r;
-      if (x < w) {
-        const float v = acc[u][r] * mask[((long)n * h + y) * w + x];
-        const int oy = (src_is_x2 == 0 && which == 1 && flips[2 * n + 1]) ? h - 1 - y : y;
-        const int ox = (src_is_x2 == 0 && which == 1 && flips[2 * n]) ? w - 1 - x : x;
-        out[(((long)n * k + a) * h + oy) * w + ox] = v;
-      }
-    }
+    for (int t = 0; t < TK; ++t)
+      seg_grad_store(acc[u][t], tile, t * 16 + c, out, mask, flips, n, y, k, h, w, which, src_is_x2, kk);
   }
 }
 
 extern "C" {
 
 static int seg_tk(int k) { return (k + 15) / 16; }
+static bool seg_shape_ok(int k, int T) { return k >= 1 && k <= 48 && T >= 0 && T <= 10; }
 // streaming kernels: float4 rows (w % 4 == 0, 16-byte aligned tensors), k <= 48.  A/B: iic_debug_seg_stream(0).
 IIC_SWITCH(g_seg_stream, 1, iic_debug_seg_stream)
-static bool seg_stream_ok(int k, int w, const void* a, const void* b, const void* c) {
-  return g_seg_stream && (w & 3) == 0 && k <= 48 &&
-         ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
-}
 // bf16-split kernels (three-term operands on v_mfma_f32_16x16x32_bf16).  Measured (tools/seg_bf16_ab.py,
 // profiles/r06_seg_bf16_ab.txt; results agree with the exact-fp32 MFMA kernels to 1e-6): the split is done on the
 // fly -- 8 scalar LDS reads and ~36 VALU per 8-element fragment -- and that, not the matrix pipe, then sets the time:
@@ -1133,34 +848,135 @@ static bool seg_stream_ok(int k, int w, const void* a, const void* b, const void
 // (one shared-operand fragment per step in the joint, one per 7 MFMA units in the gradient: the gradient pays a split
 // per product group).  Splitting at staging time instead needs the three bf16 planes in LDS with 16-byte-aligned
 // fragments for every column shift, i.e. the k index across image ROWS and 8 rows of both maps resident (113 + 98 KB
-// at k = 15, w = 128): it does not fit.  Default (1): the joint at k <= 16, T >= 5 -- the only place it pays; the
-// gradient stays on the exact-fp32 MFMA.  iic_debug_seg_bf16(0): fp32 everywhere; (2): bf16 split everywhere (A/B, tests).
+// at k = 15, w = 128): it does not fit.  Hence there is no bf16 gradient kernel: the one measured above is retired, and
+// the gradient runs on the exact-fp32 MFMA under every value of the switch.  Default (1): the joint at k <= 16, T >= 5 --
+// the only place it pays.  iic_debug_seg_bf16(0): fp32 everywhere; (2): the bf16 joint wherever it is instantiated
+// (A/B, tests).
 IIC_SWITCH(g_seg_bf16, 1, iic_debug_seg_bf16)
-// (the bf16 kernels are instantiated for one and two class tiles: 33 <= k <= 48 stays on the fp32 kernels in every mode)
+// (the bf16 joint is instantiated for one and two class tiles: 33 <= k <= 48 stays on the fp32 kernel in every mode)
 static bool seg_bf16_joint_ok(int k, int T) {
   return seg_tk(k) <= 2 && (g_seg_bf16 == 2 || (g_seg_bf16 == 1 && T >= 5 && k <= 16));
 }
-static bool seg_bf16_grad_ok(int k) { return seg_tk(k) <= 2 && g_seg_bf16 == 2; }
 static int seg_qg(int tk) { return tk == 1 ? 21 : (tk == 2 ? 7 : 3); }
 // streaming joint kernel: row tiles per workgroup (accumulators) and the column shifts per group that
 // fill them -- groups balanced over the 2T+1 shifts
 #define SEG_MT1 21
 #define SEG_MT2 11
 #define SEG_MT3 7      // (round 6: 33 <= k <= 48 -- the reference's 15- / 6-class runs overcluster with k_A = 45 / 36, commands.txt:80,89)
+static int seg_mt(int tk) { return tk == 1 ? SEG_MT1 : (tk == 2 ? SEG_MT2 : SEG_MT3); }
 static int seg_stream_groups(int k, int nq, int* qg_out) {
-  const int mt = seg_tk(k) == 1 ? SEG_MT1 : (seg_tk(k) == 2 ? SEG_MT2 : SEG_MT3);
-  int qgmax = mt * 16 / k;
+  int qgmax = seg_mt(seg_tk(k)) * 16 / k;
   if (qgmax < 1) qgmax = 1;
   const int groups = (nq + qgmax - 1) / qgmax;
   if (qg_out) *qg_out = (nq + groups - 1) / groups;
   return groups;
 }
 
+// The launch plans: which kernel, in which form, on which grid and with how much LDS a shape gets.  Filled once per
+// call, under the switches in force; the launches below and the iic_debug_seg_*_plan hooks read nothing else
+// (tests/test_seg_dispatch_cpu.py pins the plans of the shapes the project runs).  `aligned`: every tensor the caller
+// passed is 16-byte aligned.  Fields a kernel does not use are 0; an unsupported shape gives kernel = 0.
+enum { SEGJ_NONE = 0, SEGJ_GENERIC, SEGJ_STREAM, SEGJ_BF16 };
+struct seg_joint_plan {
+  int kernel, tk, mt, lw;     // class tiles, row tiles per workgroup (MTMAX), lanes per staged row (LW)
+  int qg, groups;             // column shifts per workgroup, workgroups per row shift
+  int gx, gy, gz, lds;
+};
+static bool seg_joint_make_plan(int bn, int k, int h, int w, int T, int nsplit, int aligned, seg_joint_plan* P) {
+  *P = seg_joint_plan{};
+  if (bn <= 0 || nsplit <= 0 || !seg_shape_ok(k, T) || w > SEG_MAXW || h < 1) return false;
+  const int nq = 2 * T + 1, tk = seg_tk(k);
+  P->tk = tk;
+  if (g_seg_stream && aligned && (w & 3) == 0) {
+    P->kernel = seg_bf16_joint_ok(k, T) ? SEGJ_BF16 : SEGJ_STREAM;
+    P->mt = seg_mt(tk);
+    P->lw = w > 128 ? 64 : 32;
+    P->groups = seg_stream_groups(k, nq, &P->qg);
+    P->lds = seg_joint_lds_bytes(tk, P->kernel == SEGJ_BF16 ? seg_w32(w) : w, T);
+  } else {
+    const int w4 = (w + 3) & ~3;
+    const int rows_b = 16 * tk * (((w4 + 2 * T) | 1) + (w4 | 1)) * (int)sizeof(float);
+    const int red_b = 4 * tk * tk * 256 * (int)sizeof(float);
+    P->kernel = SEGJ_GENERIC;
+    P->qg = seg_qg(tk);
+    P->groups = (nq + P->qg - 1) / P->qg;
+    P->lds = rows_b > red_b ? rows_b : red_b;
+  }
+  P->gx = nq; P->gy = P->groups; P->gz = nsplit;
+  return true;
+}
+
+enum { SEGG_NONE = 0, SEGG_GENERIC, SEGG_STREAM, SEGG_STREAM3 };
+struct seg_grad_plan {
+  int kernel, tk, lw;         // class tiles, lanes per staged row (LW)
+  int kpad, rowsP, qc;        // classes per shift padded to 4, rows of G per row shift, column shifts per G slice
+  int grid, lds;
+  int prep_gx, prep_gy;       // the seg_gprep_kernel launch
+};
+static bool seg_grad_make_plan(int bn, int k, int h, int w, int T, int aligned, int has_workspace, seg_grad_plan* P) {
+  *P = seg_grad_plan{};
+  if (!seg_shape_ok(k, T) || w > SEG_MAXW || bn <= 0 || h < 1) return false;
+  const int nq = 2 * T + 1, tk = seg_tk(k);
+  if (g_seg_stream && has_workspace && aligned && (w & 3) == 0) {
+    // streaming path: G laid out once per launch (workspace), then one workgroup per output row
+    const int PG = 16 * tk, k4 = (k + 3) & ~3;
+    int QC = (256 * SEG_NG * 4 / PG) / k4;    // column shifts per G slice: SEG_NG float4 per thread
+    if (QC < 1) return false;
+    P->kernel = tk == 3 ? SEGG_STREAM3 : SEGG_STREAM;
+    P->lw = w > 128 ? 64 : (w > 64 ? 32 : 16);
+    P->kpad = k4;
+    P->rowsP = nq * k4;
+    P->qc = QC > nq ? nq : QC;
+    P->grid = 8 * ((bn * h + 7) / 8);
+    P->lds = seg_grad_lds_bytes(k4, w, T, P->qc, PG);
+    P->prep_gx = nq;
+    P->prep_gy = (P->rowsP * PG + 255) / 256;
+  } else {
+    const int w16 = (w + 15) & ~15;
+    const int PS = (w16 + 2 * T) | 1, PG = 16 * tk + 1;
+    int QC = (40 * 1024) / (k * PG * 4);        // G slice kept in LDS per chunk of column shifts
+    if (QC < 1) QC = 1;
+    P->kernel = SEGG_GENERIC;
+    P->qc = QC > nq ? nq : QC;
+    P->grid = bn * h;
+    P->lds = (k * PS + ((P->qc * k + 3) & ~3) * PG) * (int)sizeof(float);
+  }
+  P->tk = tk;
+  return true;
+}
+
+#ifdef IIC_DEBUG_HOOKS
+// The plans under the switches in force, as ints in the structs' order (host code only: needs no device).  An
+// unsupported shape zeroes `out`.
+IIC_HOOK void iic_debug_seg_joint_plan(int bn, int k, int h, int w, int T, int nsplit, int aligned, int* out) {
+  seg_joint_plan p;
+  seg_joint_make_plan(bn, k, h, w, T, nsplit, aligned, &p);
+  const int f[10] = {p.kernel, p.tk, p.mt, p.lw, p.qg, p.groups, p.gx, p.gy, p.gz, p.lds};
+  for (int i = 0; i < 10; ++i) out[i] = f[i];
+}
+IIC_HOOK void iic_debug_seg_grad_plan(int bn, int k, int h, int w, int T, int aligned, int has_workspace, int* out) {
+  seg_grad_plan p;
+  seg_grad_make_plan(bn, k, h, w, T, aligned, has_workspace, &p);
+  const int f[10] = {p.kernel, p.tk, p.lw, p.kpad, p.rowsP, p.qc, p.grid, p.lds, p.prep_gx, p.prep_gy};
+  for (int i = 0; i < 10; ++i) out[i] = f[i];
+}
+#endif
+
+static bool seg_aligned16(const void* a, const void* b, const void* c, const void* d = nullptr) {
+  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
+}
+// plan fields -> template arguments: one case per instantiation
+#define SEG_KEY(KERNEL_, TK_, LW_) ((KERNEL_) * 1000 + (TK_) * 100 + (LW_))
+#define SEG_CASE(KERNEL_, TK_, LW_, ...) \
+  case SEG_KEY(KERNEL_, TK_, LW_): rc = iic_launch_lds<__VA_ARGS__>(grid, dim3(256), (size_t)P.lds, s, SEG_ARGS); break
+
+// The split count sets the summation order of the joint, so it depends on the shape alone, never on the kernel choice
+// (any split count suits either kernel).  1 for a k or T that no kernel serves: the launch then answers
+// IIC_ERR_UNSUPPORTED.
 int iic_seg_joint_nsplit(int bn, int h, int k, int T) {
-  const int nq = 2 * T + 1, tk = seg_tk(k), qg = seg_qg(tk);
-  int groups = nq * ((nq + qg - 1) / qg);
-  if (tk <= 3) groups = nq * seg_stream_groups(k, nq, nullptr);   // (any split count suits either kernel)
-  int s = 1536 / groups;
+  if (!seg_shape_ok(k, T)) return 1;
+  const int nq = 2 * T + 1;
+  int s = 1536 / (nq * seg_stream_groups(k, nq, nullptr));
   if (s < 1) s = 1;
   if (s >= 8) s &= ~7;                        // (multiple of 8: the XCD-aware slice mapping)
   const long rows = (long)bn * h;
@@ -1172,56 +988,38 @@ int iic_seg_joint_raw(const float* x1, const float* x2, const float* mask, const
                       float* partials, int bn, int k, int h, int w, int T, int nsplit,
                       void* stream) {
   if (!x1 || !x2 || !mask || !flips || !partials || bn <= 0 || nsplit <= 0) return IIC_ERR_ARG;
-  if (k < 1 || k > 48 || T < 0 || T > 10 || w > SEG_MAXW || h < 1) return IIC_ERR_UNSUPPORTED;
-  const int nq = 2 * T + 1, tk = seg_tk(k), qg = seg_qg(tk);
-  const int w4 = (w + 3) & ~3;
-  const size_t rows_b = (size_t)16 * tk * (((w4 + 2 * T) | 1) + (w4 | 1)) * sizeof(float);
-  const size_t red_b = (size_t)4 * tk * tk * 256 * sizeof(float);
-  const size_t lds = rows_b > red_b ? rows_b : red_b;
-  dim3 grid(nq, (nq + qg - 1) / qg, nsplit);
+  seg_joint_plan P;
+  if (!seg_joint_make_plan(bn, k, h, w, T, nsplit, seg_aligned16(x1, x2, mask), &P)) return IIC_ERR_UNSUPPORTED;
+  const dim3 grid(P.gx, P.gy, P.gz);
   hipStream_t s = (hipStream_t)stream;
-  int rc = IIC_OK;
-#define SEGJ(TK_, QG_)                                                                          \
-  rc = iic_launch_lds<seg_joint_kernel<TK_, QG_>>(grid, dim3(256), lds, s, x1, x2, mask, flips, \
-                                                  partials, bn, k, h, w, T)
-#define SEGJS(TK_, MT_, LW_)                                                                    \
-  rc = iic_launch_lds<seg_joint_stream_kernel<TK_, MT_, LW_>>(sgrid, dim3(256), lds, s, x1, x2, \
-                                                              mask, flips, partials, bn, k, h, w, T, sqg)
-#define SEGJS_LW(TK_, MT_)                                                                      \
-  do {                                                                                          \
-    if (w > 128) SEGJS(TK_, MT_, 64); else SEGJS(TK_, MT_, 32);                                 \
-  } while (0)
-  if (seg_stream_ok(k, w, x1, x2, mask) && seg_bf16_joint_ok(k, T)) {
-    const int w32 = seg_w32(w);
-    const size_t srows = (size_t)16 * tk * (seg_pitch2(w32 + 2 * T) + seg_pitch2(w32)) * sizeof(float);
-    const size_t sred = (size_t)4 * tk * 256 * sizeof(float);
-    const size_t lds = srows > sred ? srows : sred;
-    int sqg = 1;
-    const int sgroups = seg_stream_groups(k, nq, &sqg);
-    dim3 sgrid(nq, sgroups, nsplit);
-#define SEGJB(TK_, MT_, LW_)                                                                    \
-  rc = iic_launch_lds<seg_joint_bf16_kernel<TK_, MT_, LW_>>(sgrid, dim3(256), lds, s, x1, x2,   \
-                                                            mask, flips, partials, bn, k, h, w, T, sqg)
-    if (tk == 1) { if (w > 128) SEGJB(1, SEG_MT1, 64); else SEGJB(1, SEG_MT1, 32); }
-    else { if (w > 128) SEGJB(2, SEG_MT2, 64); else SEGJB(2, SEG_MT2, 32); }
-  } else if (seg_stream_ok(k, w, x1, x2, mask)) {
-    const size_t srows = (size_t)16 * tk * (seg_pitch2(w + 2 * T) + seg_pitch2(w)) * sizeof(float);
-    const size_t sred = (size_t)4 * tk * 256 * sizeof(float);
-    const size_t lds = srows > sred ? srows : sred;
-    int sqg = 1;
-    const int sgroups = seg_stream_groups(k, nq, &sqg);
-    dim3 sgrid(nq, sgroups, nsplit);
-    if (tk == 1) SEGJS_LW(1, SEG_MT1); else if (tk == 2) SEGJS_LW(2, SEG_MT2); else SEGJS_LW(3, SEG_MT3);
-  } else if (tk == 1) SEGJ(1, 21);
-  else if (tk == 2) SEGJ(2, 7);
-  else SEGJ(3, 3);
+  int rc = IIC_ERR_UNSUPPORTED;
+  switch (SEG_KEY(P.kernel, P.tk, P.lw)) {
+#define SEG_ARGS x1, x2, mask, flips, partials, bn, k, h, w, T
+    SEG_CASE(SEGJ_GENERIC, 1, 0, seg_joint_kernel<1, 21>);
+    SEG_CASE(SEGJ_GENERIC, 2, 0, seg_joint_kernel<2, 7>);
+    SEG_CASE(SEGJ_GENERIC, 3, 0, seg_joint_kernel<3, 3>);
+#undef SEG_ARGS
+#define SEG_ARGS x1, x2, mask, flips, partials, bn, k, h, w, T, P.qg
+    SEG_CASE(SEGJ_STREAM, 1, 32, seg_joint_stream_kernel<1, SEG_MT1, 32>);
+    SEG_CASE(SEGJ_STREAM, 1, 64, seg_joint_stream_kernel<1, SEG_MT1, 64>);
+    SEG_CASE(SEGJ_STREAM, 2, 32, seg_joint_stream_kernel<2, SEG_MT2, 32>);
+    SEG_CASE(SEGJ_STREAM, 2, 64, seg_joint_stream_kernel<2, SEG_MT2, 64>);
+    SEG_CASE(SEGJ_STREAM, 3, 32, seg_joint_stream_kernel<3, SEG_MT3, 32>);
+    SEG_CASE(SEGJ_STREAM, 3, 64, seg_joint_stream_kernel<3, SEG_MT3, 64>);
+    SEG_CASE(SEGJ_BF16, 1, 32, seg_joint_bf16_kernel<1, SEG_MT1, 32>);
+    SEG_CASE(SEGJ_BF16, 1, 64, seg_joint_bf16_kernel<1, SEG_MT1, 64>);
+    SEG_CASE(SEGJ_BF16, 2, 32, seg_joint_bf16_kernel<2, SEG_MT2, 32>);
+    SEG_CASE(SEGJ_BF16, 2, 64, seg_joint_bf16_kernel<2, SEG_MT2, 64>);
+#undef SEG_ARGS
+    default: break;
+  }
   return rc ? rc : iic_launch_status();
 }
 
 long iic_seg_grad_workspace_bytes(int k, int T) {
-  if (k < 1 || k > 48 || T < 0 || T > 10) return 0;
+  if (!seg_shape_ok(k, T)) return 0;
   const int nq = 2 * T + 1, tk = seg_tk(k);
-  return (long)nq * nq * ((k + 7) & ~7) * 16 * tk * (long)sizeof(float);      // (classes padded to 8: the bf16 path)
+  return (long)nq * nq * ((k + 3) & ~3) * 16 * tk * (long)sizeof(float);      // G of one launch: seg_gprep_kernel
 }
 
 int iic_seg_grad(const float* src, const float* mask, const int* flips, const float* dR_loss,
@@ -1229,77 +1027,38 @@ int iic_seg_grad(const float* src, const float* mask, const int* flips, const fl
                  float* out, int bn, int k, int h, int w, int T, int which, int collapsed,
                  float* workspace, void* stream) {
   if (!src || !mask || !flips || !dR_loss || !dR_loss_no_lamb || !g_loss || !out) return IIC_ERR_ARG;
-  if (k < 1 || k > 48 || T < 0 || T > 10 || w > SEG_MAXW || bn <= 0 || h < 1) return IIC_ERR_UNSUPPORTED;
-  const int nq = 2 * T + 1, tk = seg_tk(k);
-  const int w16 = (w + 15) & ~15;
+  seg_grad_plan P;
+  if (!seg_grad_make_plan(bn, k, h, w, T, seg_aligned16(src, mask, out, workspace), workspace != nullptr, &P))
+    return IIC_ERR_UNSUPPORTED;
   const int src_is_x2 = which == 0 ? 1 : 0;   // d/dx1 reads x2m ; d/dx2 reads x1m
+  const int shift_stride = collapsed ? 0 : 1;
+  const dim3 grid(P.grid);
   hipStream_t s = (hipStream_t)stream;
-  int rc = IIC_OK;
-  if (g_seg_stream && workspace && seg_stream_ok(k, w, src, mask, out) && ((uintptr_t)workspace & 15) == 0 &&
-      seg_bf16_grad_ok(k)) {
-    // bf16-split path: as the streaming path below, classes padded to 8 per shift
-    const int PG = 16 * tk, k8 = (k + 7) & ~7, rowsP = nq * k8;
-    int QC = (256 * SEG_NG * 4 / PG) / k8;
-    if (QC < 1) return IIC_ERR_UNSUPPORTED;
-    if (QC > nq) QC = nq;
-    hipLaunchKernelGGL(seg_gprep_kernel, dim3(nq, (rowsP * PG + 255) / 256), dim3(256), 0, s,
-                       dR_loss, dR_loss_no_lamb, g_loss, g_loss_no_lamb, workspace, k, nq, PG, rowsP,
-                       which, collapsed ? 0 : 1, k8);
-    const int PS = seg_pitch16(w16 + 2 * T);
-    const size_t lds = ((((size_t)k8 * PS + 3) & ~(size_t)3) + (size_t)QC * k8 * PG) * sizeof(float);
-#define SEGGB(TK_, LW_)                                                                         \
-  rc = iic_launch_lds<seg_grad_bf16_kernel<TK_, LW_>>(dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, mask, \
-                                                      flips, workspace, out, bn, k, h, w, T, which, src_is_x2, QC, \
-                                                      rowsP)
-#define SEGGB_LW(TK_)                                                                           \
-  do {                                                                                          \
-    if (w > 128) SEGGB(TK_, 64); else if (w > 64) SEGGB(TK_, 32); else SEGGB(TK_, 16);          \
-  } while (0)
-    if (tk == 1) SEGGB_LW(1); else SEGGB_LW(2);
-    return rc ? rc : iic_launch_status();
+  if (P.kernel != SEGG_GENERIC)
+    hipLaunchKernelGGL(seg_gprep_kernel, dim3(P.prep_gx, P.prep_gy), dim3(256), 0, s, dR_loss, dR_loss_no_lamb,
+                       g_loss, g_loss_no_lamb, workspace, k, 2 * T + 1, 16 * P.tk, P.rowsP, which, shift_stride,
+                       P.kpad);
+  int rc = IIC_ERR_UNSUPPORTED;
+  switch (SEG_KEY(P.kernel, P.tk, P.lw)) {
+#define SEG_ARGS src, mask, flips, dR_loss, dR_loss_no_lamb, g_loss, g_loss_no_lamb, out, bn, k, h, w, T, which, \
+                 shift_stride, src_is_x2, P.qc
+    SEG_CASE(SEGG_GENERIC, 1, 0, seg_grad_kernel<1>);
+    SEG_CASE(SEGG_GENERIC, 2, 0, seg_grad_kernel<2>);
+    SEG_CASE(SEGG_GENERIC, 3, 0, seg_grad_kernel<3>);
+#undef SEG_ARGS
+#define SEG_ARGS src, mask, flips, workspace, out, bn, k, h, w, T, which, src_is_x2, P.qc, P.rowsP
+    SEG_CASE(SEGG_STREAM, 1, 16, seg_grad_stream_kernel<1, 16>);
+    SEG_CASE(SEGG_STREAM, 1, 32, seg_grad_stream_kernel<1, 32>);
+    SEG_CASE(SEGG_STREAM, 1, 64, seg_grad_stream_kernel<1, 64>);
+    SEG_CASE(SEGG_STREAM, 2, 16, seg_grad_stream_kernel<2, 16>);
+    SEG_CASE(SEGG_STREAM, 2, 32, seg_grad_stream_kernel<2, 32>);
+    SEG_CASE(SEGG_STREAM, 2, 64, seg_grad_stream_kernel<2, 64>);
+    SEG_CASE(SEGG_STREAM3, 3, 16, seg_grad_stream3_kernel<16>);
+    SEG_CASE(SEGG_STREAM3, 3, 32, seg_grad_stream3_kernel<32>);
+    SEG_CASE(SEGG_STREAM3, 3, 64, seg_grad_stream3_kernel<64>);
+#undef SEG_ARGS
+    default: break;
   }
-  if (g_seg_stream && workspace && seg_stream_ok(k, w, src, mask, out) && ((uintptr_t)workspace & 15) == 0) {
-    // streaming path: G laid out once per launch (workspace), then one workgroup per output row
-    const int PG = 16 * tk, k4 = (k + 3) & ~3, rowsP = nq * k4;
-    int QC = (256 * SEG_NG * 4 / PG) / k4;    // column shifts per G slice: SEG_NG float4 per thread
-    if (QC < 1) return IIC_ERR_UNSUPPORTED;
-    if (QC > nq) QC = nq;
-    hipLaunchKernelGGL(seg_gprep_kernel, dim3(nq, (rowsP * PG + 255) / 256), dim3(256), 0, s,
-                       dR_loss, dR_loss_no_lamb, g_loss, g_loss_no_lamb, workspace, k, nq, PG, rowsP,
-                       which, collapsed ? 0 : 1, k4);
-    const int PS = seg_pitch16(w16 + 2 * T);
-    const size_t lds = ((((size_t)k4 * PS + 3) & ~(size_t)3) + (size_t)QC * k4 * PG) * sizeof(float);
-#define SEGGS(TK_, LW_)                                                                         \
-  rc = iic_launch_lds<seg_grad_stream_kernel<TK_, LW_>>(dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, mask, \
-                                                        flips, workspace, out, bn, k, h, w, T, which, src_is_x2,   \
-                                                        QC, rowsP)
-#define SEGGS_LW(TK_)                                                                           \
-  do {                                                                                          \
-    if (w > 128) SEGGS(TK_, 64); else if (w > 64) SEGGS(TK_, 32); else SEGGS(TK_, 16);          \
-  } while (0)
-    if (tk == 1) SEGGS_LW(1);
-    else if (tk == 2) SEGGS_LW(2);
-    else {
-#define SEGG3(LW_)                                                                              \
-  rc = iic_launch_lds<seg_grad_stream3_kernel<LW_>>(dim3(8 * ((bn * h + 7) / 8)), dim3(256), lds, s, src, mask, \
-                                                    flips, workspace, out, bn, k, h, w, T, which, src_is_x2, QC, \
-                                                    rowsP)
-      if (w > 128) SEGG3(64); else if (w > 64) SEGG3(32); else SEGG3(16);
-    }
-    return rc ? rc : iic_launch_status();
-  }
-  const int PS = (w16 + 2 * T) | 1, PG = 16 * tk + 1;
-  int QC = (40 * 1024) / (k * PG * 4);        // G slice kept in LDS per chunk of column shifts
-  if (QC < 1) QC = 1;
-  if (QC > nq) QC = nq;
-  const size_t lds = ((size_t)k * PS + (size_t)((QC * k + 3) & ~3) * PG) * sizeof(float);
-#define SEGG(TK_)                                                                               \
-  rc = iic_launch_lds<seg_grad_kernel<TK_>>(dim3(bn * h), dim3(256), lds, s, src, mask, flips, dR_loss, \
-                                            dR_loss_no_lamb, g_loss, g_loss_no_lamb, out, bn, k, h, w, T, which, \
-                                            collapsed ? 0 : 1, src_is_x2, QC)
-  if (tk == 1) SEGG(1);
-  else if (tk == 2) SEGG(2);
-  else SEGG(3);
   return rc ? rc : iic_launch_status();
 }
 

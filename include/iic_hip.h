@@ -68,6 +68,8 @@ int iic_iid_grad(const float* z, const float* zt, const float* dR_loss,
  * Exact fp32 MFMA (16x16x4).  k <= 48, T <= 10, w <= 256.  Rows with w % 4 == 0 (any served k) and
  * 16-byte aligned tensors take the streaming kernels (float4 rows prefetched under the MFMA loop);
  * anything else the element-wise generic ones -- same results (bit-identical joint).
+ * iic_seg_joint_nsplit: the recommended split count, a function of the shape alone; 1 for a k or T
+ * outside the served range (the launch then answers IIC_ERR_UNSUPPORTED).
  * ------------------------------------------------------------------------------- */
 int iic_seg_joint_nsplit(int bn, int h, int k, int T);
 int iic_seg_joint_raw(const float* x1, const float* x2, const float* mask, const int* flips,
@@ -82,8 +84,9 @@ int iic_seg_loss_from_joint(const float* partials, int nparts, int H, int k, dou
 /* which = 0: out = dLoss/dx1 (src = x2);  which = 1: out = dLoss/dx2 (src = x1).
  * g_loss / g_loss_no_lamb: DEVICE arrays [H] of upstream gradients per shift ([1] if collapsed).
  * workspace: iic_seg_grad_workspace_bytes(k, T) bytes, 16-byte aligned, caller-owned scratch of
- * this launch (the per-shift gradient matrices laid out for the streaming kernel); NULL selects
- * the generic kernel (any w, k <= 48), which needs none.                                     */
+ * this launch (the per-shift gradient matrices laid out for the streaming kernel, classes padded
+ * to a multiple of 4: (2T+1)^2 * roundup4(k) * 16 * ceil(k / 16) floats; 0 outside the served
+ * range); NULL selects the generic kernel (any w, k <= 48), which needs none.                */
 long iic_seg_grad_workspace_bytes(int k, int T);
 int iic_seg_grad(const float* src, const float* mask, const int* flips, const float* dR_loss,
                  const float* dR_loss_no_lamb, const float* g_loss, const float* g_loss_no_lamb,

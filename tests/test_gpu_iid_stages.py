@@ -36,7 +36,8 @@ def nan_like(shape):
 
 
 # ---- segmentation joint and gradients, exact ---------------------------------------------------------------------------------
-# dispatch modes: the product library's default, and the instrumented library's switches
+# dispatch modes: the product library's default, and the instrumented library's switches (iic_debug_seg_bf16 chooses the
+# JOINT kernel only: the gradient is the fp32 MFMA kernel under every value, so its "bf16" cases run that one again)
 MODES = [pytest.param("default", id="default"),
          pytest.param("generic", id="stream0", marks=HOOKS),
          pytest.param("fp32", id="bf16_0", marks=HOOKS),

@@ -237,15 +237,16 @@ def test_stream_kernels_match_generic_kernels_bitwise(bn, k, h, w, T, collapsed)
 
 @pytest.mark.parametrize("bn,k,h,w,T", [(3, 15, 20, 128, 10), (2, 24, 14, 200, 10), (2, 3, 9, 200, 5), (2, 9, 11, 64, 3),
                                         (1, 32, 7, 40, 2), (2, 16, 6, 8, 1), (1, 1, 5, 256, 10), (2, 17, 3, 132, 4),
-                                        # three class tiles: the bf16 kernels have none, mode 2 stays on the fp32 ones
+                                        # three class tiles: the bf16 joint has none, mode 2 stays on the fp32 one
                                         (2, 45, 4, 128, 10), (1, 33, 4, 132, 3)])
 @pytest.mark.parametrize("collapsed", [False, True])
 @pytest.mark.hooks
 def test_bf16_split_kernels_match_the_exact_fp32_mfma_kernels(bn, k, h, w, T, collapsed):
-  """Round 6: the joint / gradient on the bf16 matrix pipe (every fp32 operand element as three bf16 terms, six
-  v_mfma_f32_16x16x32_bf16 per product; the product path uses the joint form at k <= 16, T >= 5) against the exact-fp32
-  MFMA kernels on the same inputs -- per-image flips, a blob mask, ragged class counts and widths: the dropped terms are
-  below 2^-24 of a product, so the two agree to fp32 summation noise."""
+  """Round 6: the joint on the bf16 matrix pipe (every fp32 operand element as three bf16 terms, six
+  v_mfma_f32_16x16x32_bf16 per product; the product path uses it at k <= 16, T >= 5) against the exact-fp32 MFMA kernel
+  on the same inputs -- per-image flips, a blob mask, ragged class counts and widths: the dropped terms are below 2^-24
+  of a product, so the two agree to fp32 summation noise.  The switch serves the joint only: the gradient has no bf16
+  kernel (retired, LAB.md S17), so under mode 2 the gradient cases check the fp32 kernels a second time."""
   import ctypes
   from iic_amd import _lib
   from iic_amd._lib import check, lib, ptr, stream_ptr
