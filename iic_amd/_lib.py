@@ -51,6 +51,12 @@ _SIGNATURES = {
   "iic_seg_loss_from_joint": (c_int, [_P, c_int, c_int, c_int, c_double, c_double, _P, _P, _P, _P, _P, c_int, _P]),
   "iic_seg_grad_workspace_bytes": (c_long, [c_int, c_int]),
   "iic_seg_grad": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+  "iic_seg_loss_path": (c_int, [c_int, c_int, c_int]),
+  "iic_seg_tiled_limit": (c_int, [c_int]),
+  "iic_seg_tiled_joint_nsplit": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+  "iic_seg_tiled_joint_raw": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_seg_tiled_grad_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+  "iic_seg_tiled_grad": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
   "iic_affine_warp_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_affine_warp_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_conv_lds_bytes": (c_long, [POINTER(ConvGeom), c_int]),
@@ -120,6 +126,7 @@ _SIGNATURES = {
   "iic_seg_head_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_seg_head_bwd_dx": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_seg_head_wgrad": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_seg_window_wgrad": (c_int, [_P, _P, _P, c_long, c_int, c_int, _P]),
   "iic_bilinear_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_bilinear_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_softmax_fwd": (c_int, [_P, _P, c_int, c_int, _P]),

@@ -96,10 +96,21 @@ class _SegHeadFn(torch.autograd.Function):
       check(L.iic_colsum_f32(ptr(part), ptr(dW), nch, k * C, 0, s), "iic_colsum_f32")
       check(L.iic_seg_head_bwd_dx(ptr(dlog), ptr(W2), ptr(dx), N, Hw, Ww, Hp, Wp, off, C, k, s), "iic_seg_head_bwd_dx")
       return dx, dW.view(k, C, 1, 1), None, None
-    dW = torch.zeros((k, C), dtype=F32, device=dout.device)
-    splitk = max(1, min(512, M // 2048))
-    check(L.iic_gemm_f32_splitk(ptr(dlog), 1, k, ptr(Fm), C, 1, ptr(dW), C, k, C, M, splitk, s),
-          "iic_gemm_f32_splitk")
+    # per-chunk partials folded in chunk order: bit-reproducible (the atomic split-K GEMM is not)
+    nch = L.iic_seg_head_wgrad_chunks(M)
+    part = torch.empty((nch, k * C), dtype=F32, device=dout.device)
+    rc = L.iic_seg_window_wgrad(ptr(dlog), ptr(Fm), ptr(part), M, C, k, s)
+    if rc == 0:
+      dW = torch.empty((k, C), dtype=F32, device=dout.device)
+      check(L.iic_colsum_f32(ptr(part), ptr(dW), nch, k * C, 0, s), "iic_colsum_f32")
+    elif rc == -3:      # IIC_ERR_UNSUPPORTED: a channel count other than 256 / 512
+      del part
+      dW = torch.zeros((k, C), dtype=F32, device=dout.device)
+      splitk = max(1, min(512, M // 2048))
+      check(L.iic_gemm_f32_splitk(ptr(dlog), 1, k, ptr(Fm), C, 1, ptr(dW), C, k, C, M, splitk, s),
+            "iic_gemm_f32_splitk")
+    else:
+      check(rc, "iic_seg_window_wgrad")
     dF = torch.empty((M, C), dtype=F32, device=dout.device)
     ops.gemm_f32(dlog, k, 1, W2, C, 1, dF, C, M, C, k)
     if dx.dtype == F32:

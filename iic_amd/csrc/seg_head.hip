@@ -168,6 +168,133 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
   for (int i = threadIdx.x; i < Wl * k; i += blockDim.x) o[i] = sres[i];
 }
 
+// ------------------------------------------------------------------------------------
+// Column-windowed forms of the two kernels above, for the shapes whose rows do not fit the 64 KB those keep resident
+// (2 Wl k floats forward, Wl k backward: S = 320 with k = 45, S = 512 with k = 24, any k >= 49 at the usual sizes).
+// A workgroup owns a window of columns of one row and stages only the source columns that window touches.  Each
+// element is computed by the operations of the resident kernels in their order, so the two forms agree bit for bit
+// (tests/test_gpu_seg_tiled.py forces this form on shapes both serve) -- pinned operation by operation, as
+// csrc/seg_eval.hip pins the forward's, not left to -ffp-contract: what the resident kernels' code objects compute
+// for gfx950, read from their disassembly, is
+//   forward : s = fma(d + 0.5, scale, -0.5); top = fma(v01, lx, v00 (1 - lx)); bot = fma(v10, 1 - lx, v11 lx);
+//             out = (1 - ly) top + ly bot
+//   backward: the same s; acc = fma(wy wx, g, acc), y outer, x inner.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ void blw_src(int d, float scale, int in, int& i0, int& i1, float& lam) {
+#pragma clang fp contract(off)
+  float s = __builtin_fmaf((float)d + 0.5f, scale, -0.5f);
+  if (s < 0.f) s = 0.f;
+  i0 = (int)s;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  lam = s - (float)i0;
+}
+
+// grid = (N * S, ceil(S / XW)): output columns [xa, xa + XW) of output row (n, y); CAP = source columns the LDS holds
+__global__ __launch_bounds__(256) void bilinear_fwd_win_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                               int N, int Hl, int Wl, int k, int S, int XW, int CAP) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* s0 = reinterpret_cast<float*>(smem_raw);            // [CAP][k] row y0, columns c0 ..
+  float* s1 = s0 + CAP * k;                                  // [CAP][k] row y1
+  const float sy = (float)Hl / (float)S, sx = (float)Wl / (float)S;
+  const int n = blockIdx.x / S, y = blockIdx.x - n * S;
+  const int xa = blockIdx.y * XW, nx = min(XW, S - xa);
+  int y0, y1, c0, c1, t;
+  float ly, l;
+  blw_src(y, sy, Hl, y0, y1, ly);
+  blw_src(xa, sx, Wl, c0, t, l);
+  blw_src(xa + nx - 1, sx, Wl, t, c1, l);                    // (source columns are monotone in x)
+  const int ncol = c1 - c0 + 1;
+  if (ncol > CAP) return;                                    // (the host's XW rules this out: never past the LDS)
+  const float* r0 = in + (((long)n * Hl + y0) * Wl + c0) * k;
+  const float* r1 = in + (((long)n * Hl + y1) * Wl + c0) * k;
+  for (int i = threadIdx.x; i < ncol * k; i += blockDim.x) {
+    s0[i] = r0[i];
+    s1[i] = r1[i];
+  }
+  __syncthreads();
+  float* o = out + (long)n * k * S * S + (long)y * S + xa;
+  for (int i = threadIdx.x; i < k * nx; i += blockDim.x) {
+    const int c = i / nx, x = i - c * nx;
+    int x0, x1;
+    float lx;
+    blw_src(xa + x, sx, Wl, x0, x1, lx);
+    const float v00 = s0[(x0 - c0) * k + c], v01 = s0[(x1 - c0) * k + c];
+    const float v10 = s1[(x0 - c0) * k + c], v11 = s1[(x1 - c0) * k + c];
+    const float top = __builtin_fmaf(v01, lx, v00 * (1.f - lx));
+    const float bot = __builtin_fmaf(v10, 1.f - lx, v11 * lx);
+    o[(long)c * S * S + x] = (1.f - ly) * top + ly * bot;
+  }
+}
+
+// grid = (N * Hl, ceil(Wl / CW)): input columns [xw, xw + CW) of input row (n, yl)
+__global__ __launch_bounds__(256) void bilinear_bwd_win_kernel(const float* __restrict__ dout, float* __restrict__ din,
+                                                               int N, int Hl, int Wl, int k, int S, int CW) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* sres = reinterpret_cast<float*>(smem_raw);          // [CW][k]
+  const float sy = (float)Hl / (float)S, sx = (float)Wl / (float)S;
+  const float ry = (float)S / (float)Hl, rx = (float)S / (float)Wl;
+  const int n = blockIdx.x / Hl, yl = blockIdx.x - n * Hl;
+  const int xw = blockIdx.y * CW, nx = min(CW, Wl - xw);
+  // candidate rows / columns: a superset of the footprint (weights outside it are zero), as in the resident kernel
+  int ya = (int)floorf(__builtin_fmaf((float)yl - 1.f + 0.5f, ry, -0.5f)) - 1;
+  int yb = (int)ceilf(__builtin_fmaf((float)yl + 1.f + 0.5f, ry, -0.5f)) + 1;
+  if (ya < 0) ya = 0;
+  if (yb > S - 1) yb = S - 1;
+  constexpr int BLW = 12;
+  float wyv[BLW];
+#pragma unroll
+  for (int j = 0; j < BLW; ++j) {
+    const int y = ya + j;
+    float wy = 0.f;
+    if (y <= yb) {
+      int y0, y1;
+      float ly;
+      blw_src(y, sy, Hl, y0, y1, ly);
+      if (y0 == yl) wy += 1.f - ly;
+      if (y1 == yl) wy += ly;
+    }
+    wyv[j] = wy;
+  }
+  for (int i = threadIdx.x; i < k * nx; i += blockDim.x) {
+    const int c = i / nx, xl = xw + i - c * nx;
+    int xa = (int)floorf(__builtin_fmaf((float)xl - 1.f + 0.5f, rx, -0.5f)) - 1;
+    int xb = (int)ceilf(__builtin_fmaf((float)xl + 1.f + 0.5f, rx, -0.5f)) + 1;
+    if (xa < 0) xa = 0;
+    if (xb > S - 1) xb = S - 1;
+    float wxv[BLW];
+#pragma unroll
+    for (int j = 0; j < BLW; ++j) {
+      const int x = xa + j;
+      float wx = 0.f;
+      if (x <= xb) {
+        int x0, x1;
+        float lx;
+        blw_src(x, sx, Wl, x0, x1, lx);
+        if (x0 == xl) wx += 1.f - lx;
+        if (x1 == xl) wx += lx;
+      }
+      wxv[j] = wx;
+    }
+    const float* g = dout + ((long)n * k + c) * S * S;
+    float acc = 0.f;
+#pragma unroll
+    for (int jy = 0; jy < BLW; ++jy) {
+      if (wyv[jy] == 0.f) continue;
+      const float* gr = g + (long)(ya + jy) * S + xa;
+#pragma unroll
+      for (int jx = 0; jx < BLW; ++jx)
+        if (wxv[jx] != 0.f) acc = __builtin_fmaf(wyv[jy] * wxv[jx], gr[jx], acc);
+    }
+    sres[(xl - xw) * k + c] = acc;
+  }
+  __syncthreads();
+  float* o = din + (((long)n * Hl + yl) * Wl + xw) * k;
+  for (int i = threadIdx.x; i < nx * k; i += blockDim.x) o[i] = sres[i];
+}
+
 // ====================================================================================
 // Fused head GEMMs on the bf16 PT tensor itself (round 2).  The gather -> fp32 GEMM -> scatter
 // chain above moves the 512-channel feature window three times in fp32 (1.5 GB each at the
@@ -369,6 +496,67 @@ __global__ __launch_bounds__(256) void seg_head_wgrad_kernel(const float* __rest
   }
 }
 
+// The same partial weight gradients from the fp32 window matrix F [M][C] of the gather + GEMM chain (k > 32, where the
+// fused kernels above do not serve): part[chunk][j][c] = sum over the chunk's rows of dlog[m][j] * F[m][c], folded by
+// the caller in chunk order (iic_colsum_f32) -- a fixed summation order, where the atomic split-K GEMM this chain used
+// left the order of its K slices to the scheduler.  grid = (chunks, ceil(k / (16 TK))): a workgroup owns TK class tiles.
+template <int TK>
+__global__ __launch_bounds__(256) void seg_window_wgrad_kernel(const float* __restrict__ dlog,
+                                                               const float* __restrict__ Fm,
+                                                               float* __restrict__ part, long M, int C, int k) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, kk = lane >> 4;
+  const int cw = C / 4;
+  const int NG = cw / 64;                                     // 64-channel groups per wave (C = 512: 2)
+  const int j0 = blockIdx.y * 16 * TK;
+  const long m_lo = (long)blockIdx.x * SHW_ROWS, m_hi = min(M, m_lo + SHW_ROWS);
+  f32x4 acc[2][TK][4];                                        // [group][class tile][channel tile]  (C <= 512)
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int tj = 0; tj < TK; ++tj)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc[g][tj][u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (long m0 = m_lo; m0 < m_hi; m0 += 4) {
+    const long m = m0 + kk;
+    const bool vm = m < m_hi;
+    const long mm = vm ? m : m_hi - 1;
+    const float* xp = Fm + mm * C + wave * cw + 4 * c;
+    float a[TK];
+#pragma unroll
+    for (int tj = 0; tj < TK; ++tj) {
+      const int j = j0 + tj * 16 + c;
+      a[tj] = (vm && j < k) ? dlog[mm * k + j] : 0.f;
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      if (g < NG) {
+        const float4 v = *reinterpret_cast<const float4*>(xp + 64 * g);
+        const float b[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int tj = 0; tj < TK; ++tj)
+#pragma unroll
+          for (int u = 0; u < 4; ++u) acc[g][tj][u] = sh_mfma16(a[tj], b[u], acc[g][tj][u]);
+      }
+    }
+  }
+  float* o = part + (long)blockIdx.x * k * C;
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    if (g >= NG) break;
+#pragma unroll
+    for (int tj = 0; tj < TK; ++tj)
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int j = j0 + tj * 16 + kk * 4 + r;            // D row = class
+          const int ch = wave * cw + 64 * g + 4 * c + u;      // D column c of tile u
+          if (j < k) o[(long)j * C + ch] = acc[g][tj][u][r];
+        }
+  }
+}
+
 static int grid_for(long total) {
   long g = (total + 255) / 256;
   if (g > 16384) g = 16384;
@@ -394,11 +582,30 @@ int iic_seg_window_scatter(const float* in, void* pt, int N, int Hw, int Ww, int
   return iic_launch_status();
 }
 
+// rows of at most this many bytes stay resident in LDS (today's kernels, today's bits); larger ones take the windowed forms
+static constexpr size_t BL_RESIDENT_BYTES = 64 * 1024;
+// iic_debug_bilinear_window(1): the windowed forms on every shape, with small windows (the bit-identity test)
+IIC_SWITCH(g_bl_window, 0, iic_debug_bilinear_window)
+
 int iic_bilinear_fwd(const float* in_nhwc, float* out_nchw, int N, int Hl, int Wl, int k, int S,
                      void* stream) {
   if (!in_nhwc || !out_nchw || N <= 0 || Hl <= 0 || Wl <= 0 || k <= 0 || S <= 0) return IIC_ERR_ARG;
   const size_t lds = (size_t)2 * Wl * k * sizeof(float);
-  if (lds > 64 * 1024) return IIC_ERR_UNSUPPORTED;
+  if (lds > BL_RESIDENT_BYTES || g_bl_window) {
+    // windowed form: CAP source columns of both rows in LDS; XW output columns span at most (XW - 1) Wl / S + 3 of them
+    int cap = (int)(BL_RESIDENT_BYTES / sizeof(float) / 2) / k;
+    if (g_bl_window && cap > 8) cap = 8;                     // (forced on a small shape: still several windows)
+    if (cap < 4) return IIC_ERR_UNSUPPORTED;                 // k > 2048
+    long xw = (long)(cap - 3) * S / Wl;
+    if (xw < 1) xw = 1;
+    if (xw > S) xw = S;
+    const int nwin = (int)((S + xw - 1) / xw);
+    if (nwin > 65535) return IIC_ERR_UNSUPPORTED;
+    const int rc = iic_launch_lds<bilinear_fwd_win_kernel>(dim3(N * S, nwin), dim3(256), (size_t)2 * cap * k * sizeof(float),
+                                                           (hipStream_t)stream, in_nhwc, out_nchw, N, Hl, Wl, k, S, (int)xw,
+                                                           cap);
+    return rc ? rc : iic_launch_status();
+  }
   const int rc = iic_launch_lds<bilinear_fwd_kernel>(dim3(N * S), dim3(256), lds, (hipStream_t)stream, in_nhwc,
                                                      out_nchw, N, Hl, Wl, k, S);
   return rc ? rc : iic_launch_status();
@@ -408,9 +615,19 @@ int iic_bilinear_bwd(const float* dout_nchw, float* din_nhwc, int N, int Hl, int
                      void* stream) {
   if (!dout_nchw || !din_nhwc || N <= 0 || Hl <= 0 || Wl <= 0 || k <= 0 || S <= 0) return IIC_ERR_ARG;
   const size_t lds = (size_t)Wl * k * sizeof(float);
-  if (lds > 64 * 1024) return IIC_ERR_UNSUPPORTED;
-  // (the kernel tabulates 12 candidate rows / columns per input pixel: up-sampling factors up to 3.5)
+  // (the kernels tabulate 12 candidate rows / columns per input pixel: up-sampling factors up to 3.5)
   if (2 * S > 7 * Hl || 2 * S > 7 * Wl) return IIC_ERR_UNSUPPORTED;
+  if (lds > BL_RESIDENT_BYTES || g_bl_window) {
+    int cw = (int)(BL_RESIDENT_BYTES / sizeof(float)) / k;   // input columns whose results the LDS holds
+    if (g_bl_window && cw > 5) cw = 5;
+    if (cw < 1) return IIC_ERR_UNSUPPORTED;                  // k > 16384
+    if (cw > Wl) cw = Wl;
+    const int nwin = (Wl + cw - 1) / cw;
+    if (nwin > 65535) return IIC_ERR_UNSUPPORTED;
+    const int rc = iic_launch_lds<bilinear_bwd_win_kernel>(dim3(N * Hl, nwin), dim3(256), (size_t)cw * k * sizeof(float),
+                                                           (hipStream_t)stream, dout_nchw, din_nhwc, N, Hl, Wl, k, S, cw);
+    return rc ? rc : iic_launch_status();
+  }
   const int rc = iic_launch_lds<bilinear_bwd_kernel>(dim3(N * Hl), dim3(256), lds, (hipStream_t)stream, dout_nchw,
                                                      din_nhwc, N, Hl, Wl, k, S);
   return rc ? rc : iic_launch_status();
@@ -465,6 +682,22 @@ int iic_seg_head_wgrad(const float* dlog, const void* pt, float* partials, int N
   else
     hipLaunchKernelGGL((seg_head_wgrad_kernel<2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dlog,
                        (const bf16_t*)pt, partials, M, Hw, Ww, Hp, Wp, off, C, k);
+  return iic_launch_status();
+}
+
+int iic_seg_window_wgrad(const float* dlog, const float* window, float* partials, long M, int C, int k,
+                         void* stream) {
+  if (!dlog || !window || !partials || M <= 0 || k <= 0) return IIC_ERR_ARG;
+  // (each of the 4 waves owns C/4 channels in 64-channel groups, 16-byte loads of a row: C = 256 or 512, aligned rows)
+  if (C % 256 != 0 || C > 512 || (((uintptr_t)window) & 15)) return IIC_ERR_UNSUPPORTED;
+  const int tiles = (k + 15) / 16;
+  const int tk = tiles < 4 ? tiles : 4;
+  const dim3 grid(iic_seg_head_wgrad_chunks(M), (tiles + tk - 1) / tk);
+  if (grid.y > 65535) return IIC_ERR_UNSUPPORTED;
+#define SWW(TK_) \
+  hipLaunchKernelGGL((seg_window_wgrad_kernel<TK_>), grid, dim3(256), 0, (hipStream_t)stream, dlog, window, partials, M, C, k)
+  if (tk == 1) SWW(1); else if (tk == 2) SWW(2); else if (tk == 3) SWW(3); else SWW(4);
+#undef SWW
   return iic_launch_status();
 }
 

@@ -1,5 +1,6 @@
 """Drop-in IID_segmentation_loss / IID_segmentation_loss_uncollapsed on the HIP kernels
-(iic_amd/csrc/seg_loss.hip + the k x k stage of iid_loss.hip).
+(iic_amd/csrc/seg_loss.hip, beyond 48 classes or 256-pixel rows iic_amd/csrc/seg_loss_tiled.hip, + the k x k stage of
+iid_loss.hip).
 
 Mirrors /root/reference/code/utils/segmentation/IID_losses.py:14-159 -- same keyword
 signature, same asserts (inputs require grad; affine / mask do not), returns
@@ -17,7 +18,7 @@ import torch
 
 from . import dist as iic_dist
 from . import ops
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import IICLibraryError, check, lib, ptr, stream_ptr
 
 EPS = float_info.epsilon
 F32 = torch.float32
@@ -104,6 +105,18 @@ def _draw_sparse_shift(half_side_min, half_side_max):
   return int(t[0]), int(t[1])
 
 
+def _seg_path(L, k, w, T):
+  """False: the kernels of csrc/seg_loss.hip serve (k, w, T); True: the tiled ones of csrc/seg_loss_tiled.hip.  The
+  library decides (iic_seg_loss_path) and names its own limits when neither does."""
+  path = L.iic_seg_loss_path(k, w, T)
+  if path == 0:
+    raise IICLibraryError("IID_segmentation_loss: k = %d classes, rows of w = %d pixels, half_T_side_dense = %d: no kernel "
+                          "serves this (IIC_ERR_UNSUPPORTED); the limits are 1 <= k <= %d, 0 <= half_T_side_dense <= %d, "
+                          "1 <= w <= %d" % (k, w, T, L.iic_seg_tiled_limit(0), L.iic_seg_tiled_limit(1),
+                                           L.iic_seg_tiled_limit(2)))
+  return path == 2
+
+
 class _SegLossFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, x1, x2, flips, mask, lamb, T, collapsed):
@@ -113,10 +126,17 @@ class _SegLossFn(torch.autograd.Function):
     bn, k, h, w = x1.shape
     L, s = lib(), stream_ptr()
     nq = 2 * T + 1
-    ns = L.iic_seg_joint_nsplit(bn, h, k, T)
-    part = torch.empty((ns, nq * nq, k, k), dtype=F32, device=x1.device)
-    check(L.iic_seg_joint_raw(ptr(x1), ptr(x2), ptr(mask), ptr(flips), ptr(part), bn, k, h, w, T,
-                              ns, s), "iic_seg_joint_raw")
+    tiled = _seg_path(L, k, w, T)
+    if tiled:
+      ns = L.iic_seg_tiled_joint_nsplit(bn, h, w, k, T)
+      part = torch.empty((ns, nq * nq, k, k), dtype=F32, device=x1.device)
+      check(L.iic_seg_tiled_joint_raw(ptr(x1), ptr(x2), ptr(mask), ptr(flips), ptr(part), bn, k, h, w, T,
+                                      ns, s), "iic_seg_tiled_joint_raw")
+    else:
+      ns = L.iic_seg_joint_nsplit(bn, h, k, T)
+      part = torch.empty((ns, nq * nq, k, k), dtype=F32, device=x1.device)
+      check(L.iic_seg_joint_raw(ptr(x1), ptr(x2), ptr(mask), ptr(flips), ptr(part), bn, k, h, w, T,
+                                ns, s), "iic_seg_joint_raw")
     if iic_dist.enabled():
       R = torch.empty((1, nq * nq, k, k), dtype=F32, device=x1.device)
       check(L.iic_colsum_f32(ptr(part), ptr(R), ns, nq * nq * k * k, 0, s), "iic_colsum_f32")
@@ -133,23 +153,29 @@ class _SegLossFn(torch.autograd.Function):
                                     ptr(loss), ptr(loss_nl), ptr(dR1), ptr(dR2),
                                     1 if collapsed else 0, s), "iic_seg_loss_from_joint")
     ctx.save_for_backward(x1, x2, flips, mask, dR1, dR2)
-    ctx.meta = (T, collapsed)
+    ctx.meta = (T, collapsed, tiled)
     return loss, loss_nl
 
   @staticmethod
   def backward(ctx, g_loss, g_nl):
     x1, x2, flips, mask, dR1, dR2 = ctx.saved_tensors
-    T, collapsed = ctx.meta
+    T, collapsed, tiled = ctx.meta
     bn, k, h, w = x1.shape
     g_loss, g_nl = g_loss.contiguous().to(F32), g_nl.contiguous().to(F32)
     dx1, dx2 = torch.empty_like(x1), torch.empty_like(x2)
     L, s = lib(), stream_ptr()
+    c = 1 if collapsed else 0
     # scratch of the two launches (stream-ordered, so they share it): per-shift gradient matrices
-    ws = torch.empty(L.iic_seg_grad_workspace_bytes(k, T) // 4, dtype=F32, device=x1.device)
-    check(L.iic_seg_grad(ptr(x2), ptr(mask), ptr(flips), ptr(dR1), ptr(dR2), ptr(g_loss), ptr(g_nl),
-                         ptr(dx1), bn, k, h, w, T, 0, 1 if collapsed else 0, ptr(ws), s), "iic_seg_grad")
-    check(L.iic_seg_grad(ptr(x1), ptr(mask), ptr(flips), ptr(dR1), ptr(dR2), ptr(g_loss), ptr(g_nl),
-                         ptr(dx2), bn, k, h, w, T, 1, 1 if collapsed else 0, ptr(ws), s), "iic_seg_grad")
+    if tiled:
+      grad, name = L.iic_seg_tiled_grad, "iic_seg_tiled_grad"
+      ws = torch.empty(L.iic_seg_tiled_grad_workspace_bytes(k, T, c) // 4, dtype=F32, device=x1.device)
+    else:
+      grad, name = L.iic_seg_grad, "iic_seg_grad"
+      ws = torch.empty(L.iic_seg_grad_workspace_bytes(k, T) // 4, dtype=F32, device=x1.device)
+    check(grad(ptr(x2), ptr(mask), ptr(flips), ptr(dR1), ptr(dR2), ptr(g_loss), ptr(g_nl),
+               ptr(dx1), bn, k, h, w, T, 0, c, ptr(ws), s), name)
+    check(grad(ptr(x1), ptr(mask), ptr(flips), ptr(dR1), ptr(dR2), ptr(g_loss), ptr(g_nl),
+               ptr(dx2), bn, k, h, w, T, 1, c, ptr(ws), s), name)
     return dx1, dx2, None, None, None, None, None
 
 

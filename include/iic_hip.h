@@ -92,6 +92,48 @@ int iic_seg_grad(const float* src, const float* mask, const int* flips, const fl
                  const float* dR_loss_no_lamb, const float* g_loss, const float* g_loss_no_lamb,
                  float* out, int bn, int k, int h, int w, int T, int which, int collapsed,
                  float* workspace, void* stream);
+/* ---------------------------------------------------------------------------------
+ * The same two contractions beyond k = 48 and w = 256 (csrc/seg_loss_tiled.hip) -- replace the same
+ * lines, code/utils/segmentation/IID_losses.py:45-55 and :115-125 (mask multiplies, permutes, the
+ * giant-filter F.conv2d and its backward), for the shapes the reference's overclustering rule
+ * k_A = 3 gt_k and --input_sz 320 / 512 give.  Class blocks of at most 3 x 3 tiles of 16 and column
+ * windows of at most 256 pixels with a +-T halo; exact fp32 MFMA (16x16x4), fixed summation order, no
+ * float atomics: bit-reproducible, and ONE element-wise form whatever the alignment or w % 4.
+ * Range: 1 <= k <= IIC_SEG_TILED_MAX_K, 0 <= T <= IIC_SEG_TILED_MAX_T, 1 <= w <= IIC_SEG_TILED_MAX_W,
+ * any h >= 1 -- shapes the entries above serve included (same layouts, same meaning of every
+ * argument; on full-mantissa operands the bits may differ from theirs: another summation order).
+ * The entries above keep every answer they give, the refusals included.
+ *
+ * iic_seg_loss_path(k, w, T): which family serves the shape -- IIC_SEG_PATH_RESIDENT (the entries
+ *   above), IIC_SEG_PATH_TILED (the entries below) or IIC_SEG_PATH_NONE.
+ * iic_seg_tiled_limit(which): 0 -> the largest k, 1 -> the largest T, 2 -> the largest w (else 0).
+ * iic_seg_tiled_joint_nsplit: the recommended split count, a function of the shape alone; at most
+ *   bn h, and no more splits than keep the partial buffer within IIC_SEG_TILED_PART_CAP_BYTES (64 MB)
+ *   -- never below 1, so the buffer is max(64 MB, one partial) at most; one partial is (2T+1)^2 k^2
+ *   floats, 115 MB at k = 255, T = 10, where the answer is 1; 1 outside the range.  Windows and class
+ *   blocks add no partials: partials[nsplit][(2T+1)^2][k][k], fed to iic_seg_loss_from_joint as above.
+ * iic_seg_tiled_grad_workspace_bytes(k, T, collapsed): the gradient matrices G = g dR1 + gnl dR2 laid
+ *   out [shift][source class][output class, padded to whole class blocks]: one shift when collapsed,
+ *   (2T+1)^2 otherwise; 0 outside the range.  The workspace is mandatory here (NULL: IIC_ERR_ARG).
+ * ------------------------------------------------------------------------------- */
+#define IIC_SEG_TILED_MAX_K 255
+#define IIC_SEG_TILED_MAX_T 10
+#define IIC_SEG_TILED_MAX_W 4096
+#define IIC_SEG_TILED_PART_CAP_BYTES (64L << 20)
+#define IIC_SEG_PATH_NONE 0
+#define IIC_SEG_PATH_RESIDENT 1
+#define IIC_SEG_PATH_TILED 2
+int iic_seg_loss_path(int k, int w, int T);
+int iic_seg_tiled_limit(int which);
+int iic_seg_tiled_joint_nsplit(int bn, int h, int w, int k, int T);
+int iic_seg_tiled_joint_raw(const float* x1, const float* x2, const float* mask, const int* flips,
+                            float* partials, int bn, int k, int h, int w, int T, int nsplit,
+                            void* stream);
+long iic_seg_tiled_grad_workspace_bytes(int k, int T, int collapsed);
+int iic_seg_tiled_grad(const float* src, const float* mask, const int* flips, const float* dR_loss,
+                       const float* dR_loss_no_lamb, const float* g_loss, const float* g_loss_no_lamb,
+                       float* out, int bn, int k, int h, int w, int T, int which, int collapsed,
+                       float* workspace, void* stream);
 /* General case of the second view's warp -- perform_affine_tf (code/utils/segmentation/
  * transforms.py:131-143: affine_grid + grid_sample, bilinear, zero padding) followed by the
  * whole-batch integer shift of random_translation_multiple (transforms.py:145-165; IID_losses.py:
@@ -371,6 +413,17 @@ int iic_seg_head_bwd_dx(const float* dlog, const float* w, void* pt_dx, int N, i
                         int Wp, int off, int C, int k, void* stream);
 int iic_seg_head_wgrad(const float* dlog, const void* pt, float* partials, int N, int Hw, int Ww,
                        int Hp, int Wp, int off, int C, int k, void* stream);
+/* The head's weight gradient on the gather + GEMM chain (k > 32; net10a.py:44-48, the backward of the 1x1 conv
+ * w.r.t. its weight): partials[chunk][k][C] = sum over the chunk's rows of dlog[m][j] * window[m][c], window the
+ * fp32 matrix iic_seg_window_gather wrote ([M][C], 16-byte aligned), iic_seg_head_wgrad_chunks(M) chunks; fold
+ * them in order with iic_colsum_f32: a fixed summation order, no float atomics.  Any k >= 1; C = 256 or 512
+ * (else IIC_ERR_UNSUPPORTED: iic_gemm_f32_splitk then).                                                      */
+int iic_seg_window_wgrad(const float* dlog, const float* window, float* partials, long M, int C, int k,
+                         void* stream);
+/* Bilinear up-sampling [N][Hl][Wl][k] -> [N][k][S][S], align_corners = False (net10a.py:55-59, F.interpolate),
+ * and its adjoint.  Rows that fit 64 KB of LDS (2 Wl k floats forward, Wl k backward) run the resident-row
+ * kernels; longer ones column-windowed kernels that compute every element by the same operations in the same
+ * order (bit-identical).  Forward: any Hl, Wl, S, k <= 2048.  Backward: S <= 3.5 Hl and S <= 3.5 Wl, k <= 16384. */
 int iic_bilinear_fwd(const float* in_nhwc, float* out_nchw, int N, int Hl, int Wl, int k, int S,
                      void* stream);
 int iic_bilinear_bwd(const float* dout_nchw, float* din_nhwc, int N, int Hl, int Wl, int k, int S,
