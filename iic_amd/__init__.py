@@ -6,7 +6,7 @@ implemented on hand-written HIP kernels behind the C ABI of ``libiic_hip.so``
 (include/iic_hip.h).  ``iic_amd.install.install()`` registers them under the reference's
 module names so its training scripts import them unchanged.
 
-Submodules: losses, seg_losses, transforms, archs, optim, dist, install, geom, ops, branches, pool, augment, seg_augment, seg_ragged, seg_prescale, _lib.
+Submodules: losses, seg_losses, transforms, archs, optim, dist, install, geom, ops, branches, pool, augment, seg_augment, seg_ragged, seg_prescale, semisup, _lib.
 """
 import importlib
 
@@ -15,6 +15,8 @@ _LAZY = {
   "IID_loss_heads": ("losses", "IID_loss_heads"),
   "sobel_process": ("transforms", "sobel_process"),
   "Adam": ("optim", "Adam"),
+  "SupHead5": ("semisup", "SupHead5"),
+  "TenCropEvaluator": ("semisup", "TenCropEvaluator"),
   "SegPairedAugmenter": ("seg_augment", "SegPairedAugmenter"),
   "SegRaggedAugmenter": ("seg_ragged", "SegRaggedAugmenter"),
   "prescale_dataset": ("seg_prescale", "prescale_dataset"),

@@ -152,6 +152,16 @@ _SIGNATURES = {
   "iic_f32_window_gather": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_f32_window_scatter": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_f32_nchw_to_pt": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_sup_weight_prep": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+  "iic_sup_fwd_nsplit": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+  "iic_sup_linear_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_sup_dy_cast": (c_int, [_P, _P, _P, c_int, c_int, _P]),
+  "iic_sup_linear_bwd_dx": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_sup_linear_wgrad": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_sup_bn_relu_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P]),
+  "iic_sup_bn_relu_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+  "iic_sup_cross_entropy": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
+  "iic_sup_tencrop_acc": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
   "iic_probe_tr16": (c_int, [_P, _P]),
 }
 

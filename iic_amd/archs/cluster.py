@@ -617,6 +617,10 @@ class ClusterNet5gHead(nn.Module):
 # trunk  (net5g.py:10-58, residual.py:46-68)
 # ------------------------------------------------------------------------------------
 class ClusterNet5gTrunk(nn.Module):
+  # internal (iic_amd.semisup.SupHead5 sets it on the instance around its own call): penultimate_features hands over the
+  # bf16 PT tensor itself instead of its fp32 NCHW copy.  The public behaviour of the flag is unchanged.
+  _pt_tap = False
+
   def __init__(self, config):
     super(ClusterNet5gTrunk, self).__init__()
     self.batchnorm_track = config.batchnorm_track
@@ -649,7 +653,7 @@ class ClusterNet5gTrunk(nn.Module):
     x = shard_batch(x, self)
     asserted = _ASSERTED_REPLICAS[0] > 1
     r = _ASSERTED_REPLICAS[0] if asserted else DEDUP[0]
-    if r > 1 and self.training and x.size(0) % r == 0 and x.size(0) >= 2 * r:
+    if r > 1 and self.training and x.size(0) % r == 0 and x.size(0) >= 2 * r and not self._pt_tap:
       u = x.size(0) // r
       if asserted or all(bool(torch.equal(x[:u], x[i * u:(i + 1) * u])) for i in range(1, r)):
         ops.BN_REPLICAS[0] = r
@@ -687,6 +691,8 @@ class ClusterNet5gTrunk(nn.Module):
       if taps is not None:
         taps.append(x)
       if penultimate_features:
+        if self._pt_tap and x.dtype is ops.BF16:
+          return x        # iic_amd.semisup: its head reads layer 3's PT tensor in place (csrc/sup_head.hip)
         return ops.pt_to_nchw(x, 1).reshape(x.size(0), -1)
       x = self.layer4(x)
       return _AvgPoolFn.apply(x, chain)   # avg_pool_sz == final spatial size for 96 / 64 / 32 inputs

@@ -1,8 +1,8 @@
 """Paired augmentation on the GPU.
 
 Host side of csrc/augment.hip.  `PairedAugmenter` mirrors the three transform pipelines the reference builds in
-/root/reference/code/utils/cluster/transforms.py:107-217 (`sobel_make_transforms`, default
-branch -- crop_orig, no fluid_warp / cutout / random affine / demean):
+/root/reference/code/utils/cluster/transforms.py:107-217 (`sobel_make_transforms`: crop_orig; the
+cutout, fluid_warp and demean branches are built and optional, see `PairedAugmenter`; random affine is not):
 
   tf1  RandomCrop(rand_crop_sz) -> Resize(input_sz) -> custom_greyscale_to_tensor(include_rgb)
   tf2  RandomCrop -> Resize -> RandomHorizontalFlip -> ColorJitter(0.4, 0.4, 0.4, 0.125)
@@ -213,7 +213,10 @@ class PairedAugmenter(_AugmenterBase):
     demean (--demean, :196-204): Normalize(data_mean, data_std) at the end of tf1 / tf2 / tf3.
   per_img_demean (:98-104, :206-212) asserts a 3-channel tensor and therefore cannot run behind
   custom_greyscale_to_tensor (1 or 4 channels) in the reference either: not built.  random_affine
-  is never switched on by the reference's data layer (data.py calls sobel_make_transforms(config)).
+  is never switched on by the reference's clustering data layer (data.py calls sobel_make_transforms(config)); the
+  semi-supervised script can switch it on (--random_affine): not built, those crops stay on the host.  Its tf2 without
+  that flag is `PairedAugmenter(..., cutout=True, cutout_p=..., cutout_max_box=...).jittered(idx)`, and its ten-crop
+  test batches are `iic_amd.semisup.ten_crop_params` through `apply` (crop size = input size: no new kernel).
   """
 
   def __init__(self, images_u8, rand_crop_sz, input_sz, include_rgb, jitter=(0.4, 0.4, 0.4, 0.125),

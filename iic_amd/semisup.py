@@ -1,0 +1,389 @@
+"""Semi-supervised fine-tuning on the device: the SupHead5 training step and the ten-crop evaluation.
+
+Host side of csrc/sup_head.hip.  What the reference's IID_semisup_STL10 script (examples/commands.txt §1.3, model 698)
+runs after the trunk:
+
+  SupHead5            code/archs/semisup/sup_head5.py: Linear(dlen, 2048) -> BatchNorm1d -> ReLU ->
+                      Linear(2048, gt_k) on trunk(x, trunk_features=True, penultimate_features=...)
+  cross_entropy       the script's nn.CrossEntropyLoss on the head's logits
+  TenCropEvaluator    code/utils/semisup/general.py:46-93 (assess_acc_block) over code/utils/semisup/dataset.py's
+                      TenCropAndFinish: TenCrop(input_sz) + custom_greyscale_to_tensor per crop, the ten logit rows of an
+                      image summed in float64, arg-max, compared with the label
+
+With penultimate_features=True the first Linear reads layer 3's bf16 PT tensor in place on the bf16 MFMA pipe: no fp32
+NCHW copy of the activation, its bf16 operand refreshed once per optimiser step (the rule ops.PreppedWeights applies
+to the conv weights).  Under ops.fp32_mode() the whole head runs exact fp32 (pt_to_nchw + iic_gemm_f32): the parity tier.
+
+Out of scope here: RandomAffine (with --random_affine the training crops stay on the host), install.PATCHES and the
+strict installer, graph capture of this step, data parallelism / grad_groups for SupHead5.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._lib import IICLibraryError, check, lib, ptr, stream_ptr
+from .archs import cluster as _cl
+from .augment import FPARAMS, IPARAMS, PairedAugmenter
+from .transforms import sobel_process
+
+F32, BF16 = torch.float32, torch.bfloat16
+SUP_WS = ops.Scratch()      # partial matrices of the forward's K split
+
+__all__ = ["SupHead5", "cross_entropy", "CrossEntropyLoss", "ten_crop_params", "TenCropAccumulator",
+           "TenCropEvaluator", "permute_columns", "unpermute_columns"]
+
+
+# ------------------------------------------------------------------------------------
+# the first Linear's operand: (c, h, w) columns <-> the PT interior order (h, w, c)
+# ------------------------------------------------------------------------------------
+def permute_columns(C, H, W):
+  """index [K]: column j of the kernels' operand (PT interior order, j = (h W + w) C + c) is column index[j] of the
+  parameter ((c, h, w) flatten order of net5g.py:56, c H W + h W + w)."""
+  j = np.arange(C * H * W, dtype=np.int64)
+  c, p = j % C, j // C
+  return c * (H * W) + p
+
+
+def unpermute_columns(C, H, W):
+  """The inverse: parameter column i is operand column index[i]."""
+  i = np.arange(C * H * W, dtype=np.int64)
+  c, p = i // (H * W), i % (H * W)
+  return p * C + c
+
+
+class _LinearOperands(object):
+  """bf16 operands (wb [F][K], wt [K][F]) of one nn.Linear over a PT tensor, per branch; re-written in place when the
+  parameter has changed since they were made (data pointer, version counter, optimiser epoch)."""
+
+  def __init__(self):
+    self._ent = {}      # branch -> [key, wb, wt]
+
+  def get(self, w, C, H, W):
+    b = ops.current_branch()
+    key = (w.data_ptr(), w._version, _cl._WEIGHTS_EPOCH[0], C, H, W)
+    ent = self._ent.get(b)
+    if ent is not None and ent[0] == key:
+      return ent[1], ent[2]
+    Fo, K = w.shape
+    if ent is None or ent[1].device != w.device or ent[1].numel() != w.numel():
+      ent = self._ent[b] = [None, torch.empty((Fo, K), dtype=BF16, device=w.device),
+                            torch.empty((K, Fo), dtype=BF16, device=w.device)]
+    check(lib().iic_sup_weight_prep(ptr(w), ptr(ent[1]), ptr(ent[2]), Fo, C, H, W, stream_ptr()), "iic_sup_weight_prep")
+    ent[0] = key
+    return ent[1], ent[2]
+
+
+def linear_pt_forward(x_pt, wb, bias, F):
+  """y fp32 [N, F] = interior(x_pt) . wb^T + bias (iic_sup_linear_fwd)."""
+  N, Hp, Wp, C = x_pt.shape
+  H, W = Hp - 2, Wp - 2
+  S = lib().iic_sup_fwd_nsplit(N, F, C, H, W)
+  if S < 1:
+    raise IICLibraryError("iic_sup_linear_fwd: unsupported shape C = %d, F = %d (multiples of 64 only)" % (C, F))
+  y = torch.empty((N, F), dtype=F32, device=x_pt.device)
+  ws = SUP_WS.get(x_pt.device, S * N * F) if S > 1 else None
+  check(lib().iic_sup_linear_fwd(ptr(x_pt), ptr(wb), ptr(bias), ptr(y), ptr(ws), N, F, C, H, W, stream_ptr()),
+        "iic_sup_linear_fwd")
+  return y
+
+
+def dy_cast(dy):
+  """(dyb [N, F], dyt [F, Np]) bf16 of an fp32 [N, F] gradient (iic_sup_dy_cast)."""
+  N, F = dy.shape
+  Np = (N + 63) // 64 * 64
+  dyb = torch.empty((N, F), dtype=BF16, device=dy.device)
+  dyt = torch.empty((F, Np), dtype=BF16, device=dy.device)
+  check(lib().iic_sup_dy_cast(ptr(dy), ptr(dyb), ptr(dyt), N, F, stream_ptr()), "iic_sup_dy_cast")
+  return dyb, dyt
+
+
+def linear_pt_bwd_dx(dyb, wt, dx_pt):
+  N, Hp, Wp, C = dx_pt.shape
+  check(lib().iic_sup_linear_bwd_dx(ptr(dyb), ptr(wt), ptr(dx_pt), N, dyb.shape[1], C, Hp - 2, Wp - 2, stream_ptr()),
+        "iic_sup_linear_bwd_dx")
+  return dx_pt
+
+
+def linear_pt_wgrad(dyt, x_pt, N):
+  _, Hp, Wp, C = x_pt.shape
+  F = dyt.shape[0]
+  dW = torch.empty((F, C * (Hp - 2) * (Wp - 2)), dtype=F32, device=x_pt.device)
+  check(lib().iic_sup_linear_wgrad(ptr(dyt), ptr(x_pt), ptr(dW), N, F, C, Hp - 2, Wp - 2, stream_ptr()),
+        "iic_sup_linear_wgrad")
+  return dW
+
+
+class _LinearPTFn(torch.autograd.Function):
+  """Linear over layer 3's bf16 PT tensor [N, H+2, W+2, C] -> fp32 [N, F]."""
+
+  @staticmethod
+  def forward(ctx, x_pt, w, b, operands):
+    assert x_pt.dtype is BF16 and x_pt.is_contiguous() and x_pt.dim() == 4
+    N, Hp, Wp, C = x_pt.shape
+    wb, wt = operands.get(w.detach(), C, Hp - 2, Wp - 2)
+    ctx.save_for_backward(x_pt, wt)
+    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
+    return linear_pt_forward(x_pt, wb, b.detach() if b is not None else None, w.shape[0])
+
+  @ops.branch_backward
+  def backward(ctx, dy):
+    x_pt, wt = ctx.saved_tensors
+    N, Hp, Wp, C = x_pt.shape
+    dy = dy.contiguous()
+    dyb, dyt = dy_cast(dy)
+    dx = None
+    if ctx.needs_input_grad[0]:
+      dx = linear_pt_bwd_dx(dyb, wt, ops.pt_alloc(N, Hp - 2, Wp - 2, C, 1, dy.device))
+    dW = linear_pt_wgrad(dyt, x_pt, N)
+    db = ops.colsum(dy, N, dy.shape[1]) if ctx.needs_input_grad[2] else None
+    return dx, dW, db, None
+
+
+class _LinearF32Fn(torch.autograd.Function):
+  """nn.Linear on fp32 features, exact fp32 (iic_gemm_f32): feats [N, K], w [F, K], b [F] -> [N, F]."""
+
+  @staticmethod
+  def forward(ctx, feats, w, b):
+    feats, w = feats.contiguous(), w.contiguous()
+    N, K = feats.shape
+    Fo = w.shape[0]
+    y = torch.empty((N, Fo), dtype=F32, device=feats.device)
+    ops.gemm_f32(feats, K, 1, w, 1, K, y, Fo, N, Fo, K, bias=b.contiguous())
+    ctx.save_for_backward(feats, w)
+    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
+    return y
+
+  @ops.branch_backward
+  def backward(ctx, dy):
+    feats, w = ctx.saved_tensors
+    N, K = feats.shape
+    Fo = w.shape[0]
+    dy = dy.contiguous()
+    dW = torch.empty((Fo, K), dtype=F32, device=dy.device)
+    ops.gemm_f32(dy, 1, Fo, feats, K, 1, dW, K, Fo, K, N)
+    db = ops.colsum(dy, N, Fo)
+    dfe = None
+    if ctx.needs_input_grad[0]:
+      dfe = torch.empty((N, K), dtype=F32, device=dy.device)
+      ops.gemm_f32(dy, Fo, 1, w, K, 1, dfe, K, N, K, Fo)
+    return dfe, dW, db
+
+
+def bn_relu_forward(x, gamma, beta, running_mean, running_var, training, momentum, eps):
+  """(y, save_mean, save_invstd) of BatchNorm1d + ReLU over fp32 [N, F] (iic_sup_bn_relu_fwd)."""
+  N, F = x.shape
+  if training and N < 2:
+    raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+  y = torch.empty_like(x)
+  mean = torch.empty(F, dtype=F32, device=x.device)
+  inv = torch.empty(F, dtype=F32, device=x.device)
+  check(lib().iic_sup_bn_relu_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), ptr(y), ptr(mean),
+                                  ptr(inv), N, F, 1 if training else 0, float(momentum), float(eps), stream_ptr()),
+        "iic_sup_bn_relu_fwd")
+  return y, mean, inv
+
+
+def bn_relu_backward(dout, x, y, gamma, mean, inv, training):
+  """(dx, dgamma, dbeta) (iic_sup_bn_relu_bwd)."""
+  N, F = x.shape
+  dx = torch.empty_like(x)
+  dg = torch.empty(F, dtype=F32, device=x.device)
+  db = torch.empty(F, dtype=F32, device=x.device)
+  check(lib().iic_sup_bn_relu_bwd(ptr(dout), ptr(x), ptr(y), ptr(gamma), ptr(mean), ptr(inv), ptr(dx), ptr(dg), ptr(db),
+                                  N, F, 1 if training else 0, stream_ptr()), "iic_sup_bn_relu_bwd")
+  return dx, dg, db
+
+
+class _BNReLUFn(torch.autograd.Function):
+  @staticmethod
+  def forward(ctx, x, gamma, beta, bn):
+    x = x.contiguous()
+    training = bn.training or not bn.track_running_stats
+    if bn.momentum is None:
+      raise NotImplementedError("BatchNorm1d(momentum=None): the cumulative average is not built (sup_head5.py uses 0.1)")
+    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
+    y, mean, inv = bn_relu_forward(x, gamma.detach(), beta.detach(), rm, rv, training, bn.momentum, bn.eps)
+    if training and bn.track_running_stats:
+      bn.num_batches_tracked += 1
+    ctx.save_for_backward(x, y, gamma, mean, inv)
+    ctx.training = training
+    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
+    return y
+
+  @ops.branch_backward
+  def backward(ctx, dout):
+    x, y, gamma, mean, inv = ctx.saved_tensors
+    dx, dg, db = bn_relu_backward(dout.contiguous(), x, y, gamma.detach(), mean, inv, ctx.training)
+    return dx, dg, db, None
+
+
+# ------------------------------------------------------------------------------------
+# cross-entropy
+# ------------------------------------------------------------------------------------
+def cross_entropy_raw(logits, targets):
+  """(loss [1], dlogits [N, k]) from one launch (iic_sup_cross_entropy); targets int64 on the device, range unchecked."""
+  N, k = logits.shape
+  loss = torch.empty(1, dtype=F32, device=logits.device)
+  dl = torch.empty_like(logits)
+  check(lib().iic_sup_cross_entropy(ptr(logits), ptr(targets), ptr(loss), ptr(dl), N, k, stream_ptr()),
+        "iic_sup_cross_entropy")
+  return loss, dl
+
+
+class _CrossEntropyFn(torch.autograd.Function):
+  @staticmethod
+  def forward(ctx, logits, targets):
+    loss, dl = cross_entropy_raw(logits, targets)
+    ctx.save_for_backward(dl)
+    return loss.view(())
+
+  @staticmethod
+  def backward(ctx, g):
+    dl, = ctx.saved_tensors
+    return dl * g, None
+
+
+def cross_entropy(logits, targets):
+  """nn.CrossEntropyLoss() (mean reduction) of fp32 logits [N, k] on the device and integer targets [N] (host or
+  device).  A target outside [0, k) raises here, on the host, before anything is launched."""
+  assert logits.is_cuda and logits.dim() == 2 and logits.dtype is F32, "fp32 [N, k] logits on the GPU (no CPU path)"
+  N, k = logits.shape
+  targets = torch.as_tensor(targets)
+  if targets.dim() != 1 or targets.shape[0] != N:
+    raise ValueError("targets: expected shape (%d,), got %s" % (N, tuple(targets.shape)))
+  if targets.dtype.is_floating_point or targets.dtype is torch.bool:
+    raise ValueError("targets must be integer class indices")
+  lo, hi = (int(v) for v in torch.aminmax(targets))
+  if lo < 0 or hi >= k:
+    raise IndexError("Target %d is out of bounds for %d classes" % (lo if lo < 0 else hi, k))
+  targets = targets.to(device=logits.device, dtype=torch.int64).contiguous()
+  return _CrossEntropyFn.apply(logits.contiguous(), targets)
+
+
+class CrossEntropyLoss(nn.Module):
+  """Module twin of cross_entropy (the script's `criterion = nn.CrossEntropyLoss().cuda()`)."""
+
+  def forward(self, logits, targets):
+    return cross_entropy(logits, targets)
+
+
+# ------------------------------------------------------------------------------------
+# SupHead5
+# ------------------------------------------------------------------------------------
+class SupHead5(nn.Module):
+  """sup_head5.py with its arithmetic on the HIP kernels.  `trunk` is the whole feature network (ClusterNet5g or
+  ClusterNet5gTwoHead), `head` a plain nn.Sequential(Linear, BatchNorm1d, ReLU, Linear) that only HOLDS the
+  parameters and buffers: state_dict() keys and shapes are the reference's, checkpoints interchange."""
+
+  def __init__(self, net_features, dlen=None, gt_k=None):
+    super(SupHead5, self).__init__()
+    self.trunk = net_features
+    self.head = nn.Sequential(nn.Linear(dlen, 2048), nn.BatchNorm1d(2048), nn.ReLU(), nn.Linear(2048, gt_k))
+    dev = next(net_features.parameters()).device
+    if dev.type == "cuda":
+      self.head.to(dev)                       # (sup_head5.py:21: net_head.cuda())
+    for m in self.head.modules():             # sup_head5.py:24-31
+      if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d)):
+        m.weight.data.fill_(1)
+        m.bias.data.zero_()
+      elif isinstance(m, nn.Linear):
+        m.weight.data.normal_(0, 0.01)
+        m.bias.data.zero_()
+    self._operands = _LinearOperands()
+
+  def _features(self, x, penultimate_features):
+    tr = self.trunk.trunk
+    tr._pt_tap = bool(penultimate_features)
+    try:
+      return self.trunk(x, trunk_features=True, penultimate_features=penultimate_features)
+    finally:
+      tr._pt_tap = False
+
+  def forward(self, x, penultimate_features=False):
+    pv = ops.pv
+    lin1, bn, _, lin2 = self.head
+    f = self._features(x, penultimate_features)
+    if f.dim() == 4:       # layer 3's bf16 PT tensor (under torch.no_grad() the trunk has already handed it back to the
+      #                      pool: nothing re-uses it before the next trunk forward, enqueued behind this launch)
+      if f.shape[3] * (f.shape[1] - 2) * (f.shape[2] - 2) != lin1.in_features:
+        raise ValueError("SupHead5: dlen = %d, the trunk gives %d features" % (
+          lin1.in_features, f.shape[3] * (f.shape[1] - 2) * (f.shape[2] - 2)))
+      h = _LinearPTFn.apply(f, pv(lin1.weight), pv(lin1.bias), self._operands)
+    else:                  # fp32 features: the 512 pooled ones, or the exact tier (ops.fp32_mode())
+      h = _LinearF32Fn.apply(f, pv(lin1.weight), pv(lin1.bias))
+    h = _BNReLUFn.apply(h, pv(bn.weight), pv(bn.bias), bn)
+    return _LinearF32Fn.apply(h, pv(lin2.weight), pv(lin2.bias))     # no softmax (sup_head5.py:36)
+
+
+# ------------------------------------------------------------------------------------
+# ten-crop evaluation
+# ------------------------------------------------------------------------------------
+def ten_crop_params(idx, W, H, S):
+  """(iparams int32 [10 n, 20], fparams float32 [10 n, 4]) for PairedAugmenter(images, S, S, ...).apply: the ten crops
+  of torchvision 0.2.1 TenCrop(S) per image of idx, image-major -- tl, tr, bl, br, centre (F.center_crop:
+  int(round((H - S) / 2.))) of the image, then the same five of the mirrored image, i.e. the crop at x -> W - S - x of
+  the image itself with the flip bit set.  Crop size = input size: the resize is the identity."""
+  idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+  assert S <= W and S <= H
+  cx, cy = int(round((W - S) / 2.)), int(round((H - S) / 2.))
+  five = [(0, 0), (W - S, 0), (0, H - S), (W - S, H - S), (cx, cy)]
+  rows = [(x, y, 0) for x, y in five] + [(W - S - x, y, 1) for x, y in five]
+  ip = np.zeros((idx.shape[0], 10, IPARAMS), np.int32)
+  ip[:, :, 0] = idx[:, None]
+  ip[:, :, 1:4] = np.asarray(rows, np.int32)[None]
+  return ip.reshape(-1, IPARAMS), np.zeros((idx.shape[0] * 10, FPARAMS), np.float32)
+
+
+class TenCropAccumulator(object):
+  """Streaming assess_acc_block: update(logits [B * crops, k], targets [B]) adds to a device-resident int64 pair
+  (correct, total); result() is the one host synchronisation."""
+
+  def __init__(self, device, crops=10):
+    self.counts = torch.zeros(2, dtype=torch.int64, device=device)
+    self.crops = int(crops)
+
+  def update(self, logits, targets):
+    assert logits.is_cuda and logits.dtype is F32 and logits.dim() == 2
+    rows, k = logits.shape
+    B, left = divmod(rows, self.crops)
+    assert left == 0 and B > 0, "general.py:71-72: whole images only"
+    targets = torch.as_tensor(targets).to(device=logits.device, dtype=torch.int64).contiguous()
+    assert targets.shape == (B,)
+    check(lib().iic_sup_tencrop_acc(ptr(logits.contiguous()), ptr(targets), ptr(self.counts), B, k, self.crops,
+                                    stream_ptr()), "iic_sup_tencrop_acc")
+
+  def result(self):
+    """(correct, total) as Python ints."""
+    c, t = self.counts.tolist()
+    return int(c), int(t)
+
+  def accuracy(self):
+    c, t = self.result()
+    return c / float(t)
+
+
+class TenCropEvaluator(object):
+  """The test loader of the semisup script resident on the GPU: uint8 images [B, H, W, 3], their labels, and the ten
+  crops of size input_sz cut by the augmentation kernel (bit-identical to TenCropAndFinish's PIL crops)."""
+
+  def __init__(self, images_u8, targets, input_sz, include_rgb):
+    self.aug = PairedAugmenter(images_u8, input_sz, input_sz, include_rgb)
+    self.targets = torch.as_tensor(targets).to(device=images_u8.device, dtype=torch.int64).contiguous()
+    assert self.targets.shape == (self.aug.B,)
+    self.include_rgb = bool(include_rgb)
+
+  def crops(self, idx):
+    """float32 [10 len(idx), C, S, S]: what TenCropAndFinish stacks for these images."""
+    return self.aug.apply(*ten_crop_params(idx, self.aug.W, self.aug.H, self.aug.S))
+
+  def accuracy(self, net, images_per_batch=70, penultimate_features=False):
+    """assess_acc_block(net, loader, ...)'s value.  Per batch: crops, Sobel, the network, the count -- one launch
+    chain, nothing copied to the host; one synchronisation at the end."""
+    acc = TenCropAccumulator(self.targets.device)
+    with torch.no_grad():
+      for s in range(0, self.aug.B, images_per_batch):
+        idx = np.arange(s, min(self.aug.B, s + images_per_batch))
+        x = sobel_process(self.crops(idx), self.include_rgb)
+        acc.update(net(x, penultimate_features=penultimate_features), self.targets[idx[0]:idx[-1] + 1])
+    return acc.accuracy()

@@ -765,6 +765,58 @@ int iic_seg_prepare_test(const void* imgs_u8, int B, int H, int W, int Cs, const
                          const int* idx, int N, int S, int no_sobel, int include_rgb, const float* lut,
                          float* imgs, void* targets, void* mask, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Supervised head of the semi-supervised fine-tuning step (csrc/sup_head.hip) -- replaces
+ *   code/archs/semisup/sup_head5.py:12-19, 33-37   (nn.Linear(dlen, 2048) + nn.BatchNorm1d + nn.ReLU on the
+ *                                                   flattened layer-3 tensor of net5g.py:50-56)
+ *   code/scripts/semisup/IID_semisup_STL10.py      (nn.CrossEntropyLoss on the head's logits)
+ *   code/utils/semisup/general.py:46-93            (assess_acc_block: ten-crop sum, arg-max, count)
+ * x_pt, dx_pt: bf16 PT tensors [N][H+2][W+2][C], border 1 (read as it is / never written).  K = C H W.
+ * w: the fp32 parameter [F][K], columns in the reference's (c, h, w) flatten order (net5g.py:56).
+ * Supported: N >= 1, any H, W, C % 64 == 0, F % 64 == 0; anything else returns IIC_ERR_UNSUPPORTED before a launch.
+ * The three products run on the bf16 MFMA pipe with fp32 accumulation; no float atomics, every sum in a fixed order:
+ * two calls give identical bits.
+ * ------------------------------------------------------------------------------- */
+/* wb [F][K] = bf16(w), round to nearest even, columns permuted to the PT interior order (h, w, c): the forward's
+ * operand; wt [K][F]: its transpose, the backward-data operand.  Once per optimiser step. */
+int iic_sup_weight_prep(const float* w, void* wb, void* wt, int F, int C, int H, int W, void* stream);
+/* K slices S of the forward for this shape (0: unsupported shape): S > 1 needs ws, S * N * F floats; the slices'
+ * partial matrices are added in index order, then the bias: S fp32 additions on top of the accumulator's. */
+int iic_sup_fwd_nsplit(int N, int F, int C, int H, int W);
+/* y[n][f] = sum_k x[n][k] wb[f][k] + bias[f] (bias nullable), y fp32 [N][F]; the PT interior is read in place
+ * (sup_head5.py:35 on net5g.py:56's view) */
+int iic_sup_linear_fwd(const void* x_pt, const void* wb, const float* bias, float* y, float* ws, int N, int F, int C,
+                       int H, int W, void* stream);
+/* dyb [N][F] = bf16(dy), dyt [F][Np] = its transpose, Np = N rounded up to a multiple of 64, zero beyond N: the
+ * operands of the two backward products */
+int iic_sup_dy_cast(const float* dy, void* dyb, void* dyt, int N, int F, void* stream);
+/* dx[n][k] = sum_f dyb[n][f] wt[k][f], stored round-to-nearest-even as bf16 into the interior of dx_pt (the backward
+ * of sup_head5.py:35 w.r.t. its input; no ReLU mask: layer 3's last block masks its own output gradient) */
+int iic_sup_linear_bwd_dx(const void* dyb, const void* wt, void* dx_pt, int N, int F, int C, int H, int W, void* stream);
+/* dW[f][c HW + p] = sum_n dyt[f][n] x[n][p][c]: fp32, in the parameter's own column order; db: iic_colsum_f32 */
+int iic_sup_linear_wgrad(const void* dyt, const void* x_pt, float* dW, int N, int F, int C, int H, int W, void* stream);
+/* nn.BatchNorm1d(F) + nn.ReLU over fp32 [N][F] (sup_head5.py:16-17).  training != 0: batch mean and biased variance,
+ * running_mean / running_var (nullable pair) updated with `momentum` and the unbiased variance; N == 1 is
+ * IIC_ERR_ARG, as torch raises.  training == 0: the running statistics.  save_mean / save_invstd [F]: what the
+ * backward needs, in both modes. */
+int iic_sup_bn_relu_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                        float* y, float* save_mean, float* save_invstd, int N, int F, int training, float momentum,
+                        float eps, void* stream);
+/* g = dout where y > 0; dgamma = sum g xhat, dbeta = sum g; dx = gamma invstd (g - dbeta / N - xhat dgamma / N)
+ * on batch statistics, gamma invstd g on running statistics */
+int iic_sup_bn_relu_bwd(const float* dout, const float* x, const float* y, const float* gamma, const float* save_mean,
+                        const float* save_invstd, float* dx, float* dgamma, float* dbeta, int N, int F, int training,
+                        void* stream);
+/* loss[0] = mean_n (logsumexp(logits[n]) - logits[n][targets[n]]), dlogits = (softmax - onehot) / N, from one
+ * launch, max-subtracted fp32.  targets int64 [N], each in [0, k): the caller checks that on the host. */
+int iic_sup_cross_entropy(const float* logits, const long long* targets, float* loss, float* dlogits, int N, int k,
+                          void* stream);
+/* assess_acc_block without the host arrays: per image b the `crops` rows logits[b crops + q] are added per class in
+ * float64 in row order and divided by `crops`, the first maximal class (np.argmax) is compared with targets[b]
+ * (int64 [B]); counts int64 [2] += (correct, B). */
+int iic_sup_tencrop_acc(const float* logits, const long long* targets, long long* counts, int B, int k, int crops,
+                        void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
