@@ -93,6 +93,8 @@ _SIGNATURES = {
   "iic_seg_label_map": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_seg_contingency_acc": (c_int, [_P, _P, _P, c_long, c_int, c_int, _P, _P]),
   "iic_augment": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, c_int, _P, _P]),
+  "iic_augment_affine": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, c_int,
+                                 _P, _P]),
   "iic_seg_augment": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P,
                               _P, _P]),
   "iic_seg_augment_ragged": (c_int, [_P, _P, _P, c_int, c_long, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P,

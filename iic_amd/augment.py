@@ -2,7 +2,7 @@
 
 Host side of csrc/augment.hip.  `PairedAugmenter` mirrors the three transform pipelines the reference builds in
 /root/reference/code/utils/cluster/transforms.py:107-217 (`sobel_make_transforms`: crop_orig; the
-cutout, fluid_warp and demean branches are built and optional, see `PairedAugmenter`; random affine is not):
+cutout, fluid_warp, demean and random_affine branches are built and optional, see `PairedAugmenter`):
 
   tf1  RandomCrop(rand_crop_sz) -> Resize(input_sz) -> custom_greyscale_to_tensor(include_rgb)
   tf2  RandomCrop -> Resize -> RandomHorizontalFlip -> ColorJitter(0.4, 0.4, 0.4, 0.125)
@@ -81,6 +81,22 @@ def rotation_fixed_point(angle, w, h):
   return (fix(m0), fix(m1), fix(m2 + m0 * 0.5 + m1 * 0.5), fix(m3), fix(m4), fix(m5 + m3 * 0.5 + m4 * 0.5))
 
 
+def inverse_affine_matrix(center, angle, translate, scale, shear):
+  """torchvision 0.2.1 F._get_inverse_affine_matrix in Python doubles, operation for operation: the six coefficients
+  F.affine hands to img.transform(size, Image.AFFINE, matrix, resample) -- output pixel -> input coordinates.  angle and
+  shear in degrees; F.affine's center is (w * 0.5 + 0.5, h * 0.5 + 0.5)."""
+  a, s = math.radians(angle), math.radians(shear)
+  k = 1.0 / scale
+  d = math.cos(a + s) * math.cos(a) + math.sin(a + s) * math.sin(a)
+  m = [math.cos(a + s), math.sin(a + s), 0, -math.sin(a), math.cos(a), 0]
+  m = [k / d * v for v in m]
+  m[2] += m[0] * (-center[0] - translate[0]) + m[1] * (-center[1] - translate[1])
+  m[5] += m[3] * (-center[0] - translate[0]) + m[4] * (-center[1] - translate[1])
+  m[2] += center[0]
+  m[5] += center[1]
+  return m
+
+
 def _center_xy(w, h, crop):
   """torchvision 0.2.1 F.center_crop: i = int(round((h - th) / 2.)), j = int(round((w - tw) / 2.))."""
   return int(round((w - crop) / 2.)), int(round((h - crop) / 2.))
@@ -150,7 +166,10 @@ class _AugmenterBase(object):
       sel = rows[ip[rows, 10] == t]
       ip[sel, 1], ip[sel, 2] = _center_xy(self.W, self.H, c)
 
-  def apply(self, iparams, fparams):
+  def apply(self, iparams, fparams, aparams=None):
+    """One launch for the rows of (iparams, fparams): iic_augment, or iic_augment_affine when aparams (float64 [n, 6],
+    the inverse affine matrices `draw` returns with random_affine) is given and a row has the affine switch (bit 1 of
+    iparams[:, 11]) set."""
     iparams = np.ascontiguousarray(iparams, dtype=np.int32)
     fparams = np.ascontiguousarray(fparams, dtype=np.float32)
     n = int(iparams.shape[0])
@@ -161,11 +180,32 @@ class _AugmenterBase(object):
     assert (iparams[:, 1] >= 0).all() and (iparams[:, 1] + crop <= self.W).all()
     assert (iparams[:, 2] >= 0).all() and (iparams[:, 2] + crop <= self.H).all()
     assert (iparams[:, 4] >= 0).all() and (iparams[:, 4] <= 4).all()
+    # bit 1 of iparams[:, 11]: the row is affined.  Its matrix is checked here, on the host: the kernel reads nothing
+    # outside the crop for any values, but a non-finite matrix is a caller's mistake, not an augmentation
+    affine = (iparams[:, 11] & 2) != 0
+    if affine.any():
+      if aparams is None:
+        raise ValueError("rows with the affine switch (bit 1 of iparams[:, 11]) need their matrices")
+      if self.channels != 3:
+        raise ValueError("greyscale_make_transforms has no affine")
+      aparams = np.ascontiguousarray(aparams, dtype=np.float64)
+      if aparams.shape != (n, 6) or not np.isfinite(aparams[affine]).all():
+        raise ValueError("aparams: float64 [n, 6], finite in every affined row")
+      aparams = np.where(affine[:, None], aparams, 0.0)      # the other rows are not read
     dev = self.images.device
     assert self.images.is_cuda, "the dataset must be resident on the GPU (there is no CPU path)"
     ip = torch.from_numpy(iparams).to(dev, non_blocking=True)
     fp = torch.from_numpy(fparams).to(dev, non_blocking=True)
     out = torch.empty(n, self.out_channels, self.S, self.S, device=dev, dtype=torch.float32)
+    if affine.any():
+      ap = torch.from_numpy(aparams).to(dev, non_blocking=True)
+      _lib.check(_lib.lib().iic_augment_affine(
+        self.images.data_ptr(), self.B, self.H, self.W, self.channels, ip.data_ptr(), fp.data_ptr(), ap.data_ptr(), n,
+        self.tables_host.ctypes.data, len(self.crop_szs), self.bounds.data_ptr(), self.kk.data_ptr(),
+        self.S, self.lut.data_ptr(), out.data_ptr(), int(self.include_rgb),
+        None if self.norm is None else self.norm.data_ptr(), _lib.stream_ptr()),
+        "iic_augment_affine")
+      return out
     _lib.check(_lib.lib().iic_augment(
       self.images.data_ptr(), self.B, self.H, self.W, self.channels, ip.data_ptr(), fp.data_ptr(), n,
       self.tables_host.ctypes.data, len(self.crop_szs), self.bounds.data_ptr(), self.kk.data_ptr(),
@@ -211,17 +251,24 @@ class PairedAugmenter(_AugmenterBase):
       whole image (PIL NEAREST) first, then a RandomCrop whose size is chosen uniformly from
       rand_crop_szs_tf;
     demean (--demean, :196-204): Normalize(data_mean, data_std) at the end of tf1 / tf2 / tf3.
+    random_affine (--random_affine --affine_p p of the semi-supervised script, :152-161; the clustering data layer
+      never switches it on): with probability affine_p RandomAffine(affine_degrees, translate, scale, shear,
+      resample=BILINEAR, fillcolor=0) of the crop -- after the crop (and fluid_warp's rotation), before the cutout and the
+      Resize; PIL's bilinear affine bit for bit (csrc/augment_affine.hip).  `draw(idx, "jittered")` then returns a third
+      array, the float64 [n, 6] inverse matrices, which `apply` takes; the raw draws are in `last_affine`.
   per_img_demean (:98-104, :206-212) asserts a 3-channel tensor and therefore cannot run behind
-  custom_greyscale_to_tensor (1 or 4 channels) in the reference either: not built.  random_affine
-  is never switched on by the reference's clustering data layer (data.py calls sobel_make_transforms(config)); the
-  semi-supervised script can switch it on (--random_affine): not built, those crops stay on the host.  Its tf2 without
-  that flag is `PairedAugmenter(..., cutout=True, cutout_p=..., cutout_max_box=...).jittered(idx)`, and its ten-crop
-  test batches are `iic_amd.semisup.ten_crop_params` through `apply` (crop size = input size: no new kernel).
+  custom_greyscale_to_tensor (1 or 4 channels) in the reference either: not built.
+  The semi-supervised script's tf2 (examples/commands.txt section 1.3, model 698) is
+  `PairedAugmenter(..., random_affine=True, affine_p=0.5, cutout=True, cutout_p=0.5, cutout_max_box=0.7).jittered(idx)`,
+  and its ten-crop test batches are `iic_amd.semisup.ten_crop_params` through `apply` (crop size = input size).
+  Draw order within tf2: rotation, crop-size choice, crop, affine, cutout, flip, jitter.  Without random_affine the
+  random stream is consumed, and `apply` launches iic_augment, exactly as before the affine existed.
   """
 
   def __init__(self, images_u8, rand_crop_sz, input_sz, include_rgb, jitter=(0.4, 0.4, 0.4, 0.125),
                seed=0, cutout=False, cutout_p=0.5, cutout_max_box=0.5, fluid_warp=False, rot_val=0.0,
-               rand_crop_szs_tf=(), demean=False, data_mean=(), data_std=()):
+               rand_crop_szs_tf=(), demean=False, data_mean=(), data_std=(), random_affine=False, affine_p=0.5,
+               affine_degrees=18, affine_translate=(0.1, 0.1), affine_scale=(0.9, 1.1), affine_shear=10):
     assert images_u8.dim() == 4, "RGB dataset [B, H, W, 3]"
     assert not (cutout and fluid_warp), "transforms.py:172"
     szs = [int(rand_crop_sz)]
@@ -239,6 +286,34 @@ class PairedAugmenter(_AugmenterBase):
     self.cutout, self.cutout_p = bool(cutout), float(cutout_p)
     self.cut_min, self.cut_max = int(self.crop * 0.2), int(self.crop * float(cutout_max_box))
     self.fluid_warp, self.rot_val = bool(fluid_warp), float(rot_val)
+    self.random_affine, self.affine_p = bool(random_affine), float(affine_p)
+    # RandomAffine(degrees, translate, scale, shear): numbers mean (-v, v) for degrees and shear, as in torchvision
+    self.affine_degrees, self.affine_shear = float(affine_degrees), float(affine_shear)
+    self.affine_translate = tuple(float(v) for v in affine_translate)
+    self.affine_scale = tuple(float(v) for v in affine_scale)
+    assert 0.0 <= self.affine_p <= 1.0 and self.affine_degrees >= 0 and self.affine_shear >= 0
+    assert all(0.0 <= t <= 1.0 for t in self.affine_translate) and all(v > 0 for v in self.affine_scale)
+
+  def _affine_draws(self, ip):
+    """RandomApply(p) + RandomAffine.get_params with img_size = the row's crop: angle, translations (np.round:
+    integer-valued), scale, shear -> float64 [n, 6] inverse matrices (identity where not applied), bit 1 of ip[:, 11]."""
+    r, n = self.rng, ip.shape[0]
+    crop = np.asarray(self.crop_szs, dtype=np.float64)[ip[:, 10]]
+    do = r.random_sample(n) < self.affine_p
+    angle = r.uniform(-self.affine_degrees, self.affine_degrees, size=n)
+    max_dx, max_dy = self.affine_translate[0] * crop, self.affine_translate[1] * crop
+    tx, ty = np.round(r.uniform(-max_dx, max_dx)), np.round(r.uniform(-max_dy, max_dy))
+    scale = r.uniform(self.affine_scale[0], self.affine_scale[1], size=n)
+    shear = r.uniform(-self.affine_shear, self.affine_shear, size=n)
+    self.last_affine = np.full((n, 5), np.nan)         # angle, tx, ty, scale, shear of the rows that are affined
+    mats = np.tile(np.asarray([1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), (n, 1))
+    for i in np.nonzero(do)[0]:
+      c = float(crop[i]) * 0.5 + 0.5                   # F.affine: center = (w * 0.5 + 0.5, h * 0.5 + 0.5)
+      mats[i] = inverse_affine_matrix((c, c), float(angle[i]), (float(tx[i]), float(ty[i])), float(scale[i]),
+                                      float(shear[i]))
+      self.last_affine[i] = (angle[i], tx[i], ty[i], scale[i], shear[i])
+      ip[i, 11] |= 2
+    return mats
 
   def _cutout_draws(self, ip):
     """custom_cutout (transforms.py:28-44) under RandomApply(p): box side, centre."""
@@ -259,7 +334,8 @@ class PairedAugmenter(_AugmenterBase):
 
   def draw(self, idx, mode):
     """mode 'plain' (tf1), 'jittered' (tf2) or 'center' (tf3).  Returns (iparams int32 [n, 20],
-    fparams float32 [n, 4]) as iic_augment reads them."""
+    fparams float32 [n, 4]) as iic_augment reads them; with random_affine, 'jittered' returns (iparams, fparams,
+    aparams float64 [n, 6]) as iic_augment_affine reads them.  Either way `apply(*draw(...))` is the batch."""
     ip, fp = self._new_params(idx)
     n = ip.shape[0]
     if mode == "center":
@@ -280,11 +356,12 @@ class PairedAugmenter(_AugmenterBase):
           self.last_angles[i] = ang[i]
       ip[:, 10] = np.asarray(self.tf2_tables)[self.rng.randint(0, len(self.tf2_tables), size=n)]
     self._random_crops(ip)
+    mats = self._affine_draws(ip) if self.random_affine else None
     if self.cutout:
       self._cutout_draws(ip)
     ip[:, 3] = self.rng.random_sample(n) < 0.5
     self._jitter_draws(ip, fp)
-    return ip, fp
+    return (ip, fp) if mats is None else (ip, fp, mats)
 
 
 class GreyscaleAugmenter(_AugmenterBase):

@@ -14,8 +14,13 @@ With penultimate_features=True the first Linear reads layer 3's bf16 PT tensor i
 NCHW copy of the activation, its bf16 operand refreshed once per optimiser step (the rule ops.PreppedWeights applies
 to the conv weights).  Under ops.fp32_mode() the whole head runs exact fp32 (pt_to_nchw + iic_gemm_f32): the parity tier.
 
-Out of scope here: RandomAffine (with --random_affine the training crops stay on the host), install.PATCHES and the
-strict installer, graph capture of this step, data parallelism / grad_groups for SupHead5.
+  train_loader        the script's shuffled training DataLoader over a resident PairedAugmenter: tf2 of
+                      sobel_make_transforms with the script's --random_affine / --cutout flags (model 698:
+                      PairedAugmenter(..., random_affine=True, affine_p=0.5, cutout=True, cutout_p=0.5,
+                      cutout_max_box=0.7)), one launch per batch (csrc/augment_affine.hip)
+
+Out of scope here: install.PATCHES and the strict installer, graph capture of this step, data parallelism /
+grad_groups for SupHead5.
 """
 import numpy as np
 import torch
@@ -31,7 +36,7 @@ F32, BF16 = torch.float32, torch.bfloat16
 SUP_WS = ops.Scratch()      # partial matrices of the forward's K split
 
 __all__ = ["SupHead5", "cross_entropy", "CrossEntropyLoss", "ten_crop_params", "TenCropAccumulator",
-           "TenCropEvaluator", "permute_columns", "unpermute_columns"]
+           "TenCropEvaluator", "permute_columns", "unpermute_columns", "train_loader"]
 
 
 # ------------------------------------------------------------------------------------
@@ -314,6 +319,39 @@ class SupHead5(nn.Module):
       h = _LinearF32Fn.apply(f, pv(lin1.weight), pv(lin1.bias))
     h = _BNReLUFn.apply(h, pv(bn.weight), pv(bn.bias), bn)
     return _LinearF32Fn.apply(h, pv(lin2.weight), pv(lin2.bias))     # no softmax (sup_head5.py:36)
+
+
+# ------------------------------------------------------------------------------------
+# training batches
+# ------------------------------------------------------------------------------------
+class _TrainLoader(object):
+  """The script's training DataLoader (IID_semisup_STL10.py: shuffle=True, drop_last=False) over images resident on the
+  GPU: iterating yields (augmenter.jittered(idx), targets[idx]) for a fresh permutation of the dataset per epoch, the
+  ragged last batch included.  The permutation comes from numpy, not from torch's sampler: the sample order of a
+  reference run is not replayed."""
+
+  def __init__(self, augmenter, targets, batch_sz, seed=0):
+    self.aug, self.batch_sz = augmenter, int(batch_sz)
+    self.targets = torch.as_tensor(targets)
+    self.n = int(self.targets.shape[0])
+    assert self.batch_sz > 0 and self.n == augmenter.B, "one target per image of the augmenter's dataset"
+    self.rng = np.random.RandomState(seed)
+
+  def __len__(self):
+    return (self.n + self.batch_sz - 1) // self.batch_sz
+
+  def __iter__(self):
+    perm = self.rng.permutation(self.n)
+    for lo in range(0, self.n, self.batch_sz):
+      idx = perm[lo:lo + self.batch_sz]
+      yield self.aug.jittered(idx), self.targets[torch.as_tensor(idx, device=self.targets.device)]
+
+
+def train_loader(augmenter, targets, batch_sz, seed=0):
+  """`for imgs, targets in train_loader(aug, labels, batch_sz)` is the script's training loop head: imgs float32
+  [b, C, input_sz, input_sz] on the GPU (tf2 of the augmenter, affine and cutout included when it was built with
+  them), targets the matching rows of `targets` (kept on whichever device they are)."""
+  return _TrainLoader(augmenter, targets, batch_sz, seed)
 
 
 # ------------------------------------------------------------------------------------

@@ -597,6 +597,29 @@ int iic_augment(const void* imgs_u8, int B, int H, int W, int channels, const in
                 int include_rgb, const float* norm, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * iic_augment with the RandomAffine of sobel_make_transforms (code/utils/cluster/transforms.py:152-161; the
+ * semi-supervised script switches it on, examples/commands.txt section 1.3 model 698):
+ *   RandomApply([RandomAffine(18, scale=(0.9, 1.1), translate=(0.1, 0.1), shear=10, resample=BILINEAR, fillcolor=0)], p)
+ * after the RandomCrop (and after fluid_warp's rotation of the whole image) and before the cutout and the Resize.  It
+ * acts on the crop as an image of its own: img.transform(img.size, AFFINE, m, BILINEAR) of Pillow (Geometry.c:
+ * affine_transform + bilinear_filter32RGB) in IEEE double, bit for bit -- coordinates (m0 (x + .5) + m1 (y + .5)) + m2,
+ * zero where they leave [0, crop) BEFORE the half-pixel shift, floor, neighbours clamped to the crop, the row below
+ * taken only when it exists, truncation to uint8.
+ * Every argument as for iic_augment (channels = 3 only: greyscale_make_transforms has no affine), and
+ * iparams[11] bit 0: rotate the whole image before the crop (iic_augment's rotate flag); bit 1: this row is affined.  A
+ *          row without bit 1 gives exactly iic_augment's output.
+ * aparams  double [N][6], required: the INVERSE matrix torchvision's _get_inverse_affine_matrix computes, as
+ *          Image.transform receives it (output pixel -> crop coordinates); read for rows with bit 1 only.  The kernel
+ *          reads nothing outside the crop for any values; a NaN coordinate reads as outside (zero).
+ * IIC_ERR_UNSUPPORTED, before any launch, when the crop planes do not fit the workgroup's LDS:
+ *          align16(3 crop max(crop, S)) + 3 max(crop, S)^2 bytes > 150 KB (84 -> 96: 51 KB, as iic_augment).
+ * ------------------------------------------------------------------------------- */
+int iic_augment_affine(const void* imgs_u8, int B, int H, int W, int channels, const int* iparams,
+                       const float* fparams, const double* aparams, int N, const int* tables_host, int n_tables,
+                       const int* bounds, const int* kk, int S, const float* lut, float* out,
+                       int include_rgb, const float* norm, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Paired augmentation of the segmentation datasets on the GPU -- replaces the per-sample host
  * pipeline of the training __getitem__:
  *   code/datasets/segmentation/potsdam.py:95-216    (_Potsdam._prepare_train)
