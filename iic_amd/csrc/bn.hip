@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(
   }
   if (relu) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
+    for (int i = 0; i < 8; ++i) v[i] = iic_relu(v[i]);
   }
   *reinterpret_cast<uint4*>(out + off) = pack8(v);
 }

@@ -214,6 +214,22 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float bf16lo(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
+// The forward ReLU and the fold of a max-pool window as torch has them: a NaN comes out as NaN.  fmaxf alone is one
+// v_max_f32, IEEE maxNum: it returns the operand that is NOT NaN, so relu(NaN) was 0 and a window dropped its NaN -- a
+// channel whose BatchNorm coefficients a poisoned statistic had turned to NaN went on as zeros under a finite loss
+// ("Non-finite values").  On ordered operands both give fmaxf's bits (v_max_f32 orders -0 below +0:
+// relu(-0) is +0 either way).  iic_relu is one compare and one select (v_cmp_nle_f32: "not <=" is true for v > 0 and for
+// NaN); iic_max_nan keeps a NaN that is already in m as well as one that arrives in v.
+__device__ __forceinline__ float iic_relu(float v) { return !(v <= 0.f) ? v : 0.f; }
+__device__ __forceinline__ float iic_max_nan(float m, float v) { return v != v ? v : (m != m ? m : fmaxf(m, v)); }
+// The same fold for two packed bf16 values that are post-ReLU (+0, positive, +inf or NaN of either sign; never -0 or
+// negative): on those the unsigned 16-bit order is the float order with every NaN above +inf, so one v_pk_max_u16
+// is the NaN-propagating maximum of both halves, and its result is already the packed store.
+typedef __attribute__((ext_vector_type(2))) unsigned short iic_u16x2;
+__device__ __forceinline__ uint32_t iic_max_nan_relu_bf16x2(uint32_t m, uint32_t v) {
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(iic_u16x2, m), __builtin_bit_cast(iic_u16x2, v)));
+}
+
 // Accumulator row of register r for the 32x32 MFMA C/D map (col = lane & 31).
 __device__ __forceinline__ int mfma32_row(int r, int lane) {
   return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);

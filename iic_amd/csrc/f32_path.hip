@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void f32_bn_apply_kernel(const float* __restri
   float v = y[o] * coef[c] + coef[C + c];
   if (res) v += res[o];
   if (y2) v += y2[o] * coef2[c] + coef2[C + c];
-  out[o] = relu ? fmaxf(v, 0.f) : v;
+  out[o] = relu ? iic_relu(v) : v;
 }
 
 // g = dout [* (act > 0)] [* (scale*y + shift > 0)]
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void f32_maxpool_fwd_kernel(const float* __res
     for (int dx = 0; dx < 2; ++dx) {
       const int y = 2 * ho - 1 + dy, x = 2 * wo - 1 + dx;
       if (y < 0 || y >= H || x < 0 || x >= W) continue;
-      m = fmaxf(m, in[((n * (H + 2) + y + 1) * (W + 2) + x + 1) * C + c]);
+      m = iic_max_nan(m, in[((n * (H + 2) + y + 1) * (W + 2) + x + 1) * C + c]);
     }
   out[((n * (Ho + 2) + ho + 1) * (Wo + 2) + wo + 1) * C + c] = m;
 }
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void f32_maxpool2_fwd_kernel(const float* __re
   const long n = px / Ho;
   float m = -INFINITY;
   for (int q = 0; q < 4; ++q)
-    m = fmaxf(m, in[((n * (H + 2 * Pi) + 2 * yo + (q >> 1) + Pi) * (W + 2 * Pi) + 2 * xo + (q & 1) + Pi) * C + c]);
+    m = iic_max_nan(m, in[((n * (H + 2 * Pi) + 2 * yo + (q >> 1) + Pi) * (W + 2 * Pi) + 2 * xo + (q & 1) + Pi) * C + c]);
   out[((n * (Ho + 2 * Po) + yo + Po) * (Wo + 2 * Po) + xo + Po) * C + c] = m;
 }
 

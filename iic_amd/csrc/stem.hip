@@ -150,8 +150,8 @@ __global__ __launch_bounds__(512) void stem_apply_pool_kernel(const float* __res
       const int px = wave * 32 + mfma32_row(r, lane);
       if (px < W) {
         bf16_t* d = sP + ((long)rs * W + px) * STEM_CO;
-        d[ch0] = f32_to_bf16(fmaxf(acc[0][r] * sc0 + sh0, 0.f));
-        d[ch0 + 32] = f32_to_bf16(fmaxf(acc[1][r] * sc1 + sh1, 0.f));
+        d[ch0] = f32_to_bf16(iic_relu(acc[0][r] * sc0 + sh0));
+        d[ch0 + 32] = f32_to_bf16(iic_relu(acc[1][r] * sc1 + sh1));
       }
     }
   }
@@ -159,9 +159,7 @@ __global__ __launch_bounds__(512) void stem_apply_pool_kernel(const float* __res
   const bool v0 = (2 * ho - 1) >= 0, v1 = (2 * ho) < H;
   for (int item = threadIdx.x; item < Wo * 8; item += blockDim.x) {
     const int wo = item >> 3, c8 = item & 7;
-    float m[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) m[i] = 0.f;   // post-ReLU values are >= 0: 0 == -inf padding
+    uint32_t m[4] = {0u, 0u, 0u, 0u};   // packed bf16 pairs; post-ReLU values are >= 0: 0 == -inf padding
 #pragma unroll
     for (int rs = 0; rs < 2; ++rs) {
       if (!(rs == 0 ? v0 : v1)) continue;
@@ -172,16 +170,11 @@ __global__ __launch_bounds__(512) void stem_apply_pool_kernel(const float* __res
         const uint4 v = *reinterpret_cast<const uint4*>(sP + ((long)rs * W + cx) * STEM_CO + c8 * 8);
         const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          m[2 * i] = fmaxf(m[2 * i], bf16lo(vv[i]));
-          m[2 * i + 1] = fmaxf(m[2 * i + 1], bf16hi(vv[i]));
-        }
+        for (int i = 0; i < 4; ++i) m[i] = iic_max_nan_relu_bf16x2(m[i], vv[i]);   // a NaN in the window wins
       }
     }
     const long o = (((long)n * (Ho + 2) + ho + 1) * (Wo + 2) + wo + 1) * STEM_CO + c8 * 8;
-    *reinterpret_cast<uint4*>(out + o) =
-        make_uint4(pack_bf16x2(m[0], m[1]), pack_bf16x2(m[2], m[3]), pack_bf16x2(m[4], m[5]),
-                   pack_bf16x2(m[6], m[7]));
+    *reinterpret_cast<uint4*>(out + o) = make_uint4(m[0], m[1], m[2], m[3]);
   }
 }
 

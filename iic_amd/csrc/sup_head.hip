@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void sup_bn_relu_fwd_kernel(const float* __res
   const float ga = gamma[c], be = beta[c];
   for (int r = g; r < N; r += 8) {
     const float xh = (x[(long)r * F + c] - mean) * inv;
-    y[(long)r * F + c] = fmaxf(xh * ga + be, 0.f);
+    y[(long)r * F + c] = iic_relu(xh * ga + be);
   }
 }
 

@@ -249,7 +249,7 @@ __device__ __forceinline__ void unpack8v(const uint4 v, float* f) {
 // backward's arg-max sees the same bits).  sc / sh: this thread's 8 channels of coef[0][C], coef[1][C].
 __device__ __forceinline__ void bn_relu_bf16_8(float* v, const float* sc, const float* sh) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i] * sc[i] + sh[i], 0.f);
+  for (int i = 0; i < 8; ++i) v[i] = iic_relu(v[i] * sc[i] + sh[i]);
   const uint4 r = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
                              pack_bf16x2(v[6], v[7]));
   unpack8v(r, v);
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const bf16_t* __restr
     unpack8v(*reinterpret_cast<const uint4*>(in + off), v);
     if (BN) bn_relu_bf16_8(v, sc, sh);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) m[i] = fmaxf(m[i], v[i]);
+    for (int i = 0; i < 8; ++i) m[i] = iic_max_nan(m[i], v[i]);
   }
   const long o = (((long)n * Hpo + yo + Po) * Wpo + xo + Po) * C + c8 * 8;
   *reinterpret_cast<uint4*>(out + o) = make_uint4(pack_bf16x2(m[0], m[1]), pack_bf16x2(m[2], m[3]),

@@ -34,6 +34,7 @@ import torch
 from tests import conv_f64_cases as cc
 from tests.conftest import hook
 from tests.lattice import record
+from tests.nonfinite_cases import cls as nonfinite_cls
 from tests.parity import (BF16_MAX, U32, WORST, assert_in_bracket, assert_within, bf16_bracket, conv_acc_bound)
 from tests.test_gpu_kernels import CONV_CASES
 
@@ -401,10 +402,7 @@ SMALL128 = cc.Case(128, 128, 3, 1, 1, 4, 7)
 NONFINITE = [(SMALL64, "rows"), (SMALL64, "frag"), (SMALL128, "frag")]      # first generation, persistent 64 -> 64, weights-direct
 
 
-def _classes(v):
-  """0 finite, 1 +inf, 2 -inf, 3 NaN."""
-  v = v.double()
-  return torch.isposinf(v).long() + 2 * torch.isneginf(v).long() + 3 * torch.isnan(v).long()
+_classes = nonfinite_cls      # 0 finite, 1 +inf, 2 -inf, 3 NaN
 
 
 @pytest.mark.parametrize("zero_weight", [False, True], ids=["dense-weights", "zero-weight-under-inf"])

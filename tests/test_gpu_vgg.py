@@ -118,6 +118,34 @@ def test_fused_bn_relu_maxpool_is_bit_identical_to_the_two_pass_path(C, H, W):
   assert (border == 7.0).all()
 
 
+def test_fused_bn_relu_maxpool_agrees_with_the_two_pass_path_on_non_finite_data():
+  """The sibling of the test above on tests/nonfinite_cases.py bn_pool2_case(7, 9) -- a NaN at every window position, a
+  +inf beside a NaN, an all -inf window, a NaN in the uncovered trailing row, a channel with NaN coefficients: the fused
+  forward and iic_bn_apply followed by the plain pool agree in class (finite / +inf / -inf / NaN) everywhere and bit for
+  bit where finite, and both hold the NaNs the float64 reference has.  (Forward only: the backward under a non-finite
+  forward is unspecified)"""
+  from iic_amd import ops
+  from tests import nonfinite_cases as nf
+  from tests.parity import pt_of
+  H, W, P, C, N = 7, 9, 2, nf.POOL_C, nf.POOL_N
+  c = nf.bn_pool2_case(H, W)
+  d = dev()
+  y, coef = pt_of(c["y"], P, torch.bfloat16), c["coef"].to(d)
+  a = torch.zeros_like(y)
+  ops.bn_apply(y, coef, a, N, H, W, P, C, relu=True)
+  o_ref = torch.full((N, H // 2 + 2 * P, W // 2 + 2 * P, C), 7.0, dtype=torch.bfloat16, device=d)
+  o_fus = o_ref.clone()
+  ops.maxpool2_fwd(a, o_ref, N, H, W, P, P, C)
+  ops.bn_relu_maxpool2_fwd(y, coef, o_fus, N, H, W, P, P, C)
+  torch.cuda.synchronize()
+  o_ref, o_fus = o_ref.float().cpu(), o_fus.float().cpu()
+  assert torch.equal(nf.cls(o_ref), nf.cls(o_fus))
+  fin = nf.cls(o_ref) == nf.FIN
+  assert torch.equal(o_ref[fin], o_fus[fin])
+  nf.assert_classes(o_fus[:, P:-P, P:-P], c["ref"], "fused pool")
+  assert int((nf.cls(c["ref"]) == nf.ISNAN).sum()) >= 8
+
+
 def test_net6c_step_with_and_without_the_fused_pool_is_bit_identical():
   """Whole ClusterNet6c train step (three pooled stages): IIC_FUSE_POOL on / off -- outputs, loss and every gradient."""
   from iic_amd import archs
