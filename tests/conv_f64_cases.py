@@ -29,6 +29,15 @@ DRAWS = ("mixed", "pos")
 # boundaries are one spacing >= 2^-8 |ref| apart, so the expected share of such elements is at most
 # 2 b / spacing <= 2 * 4608 * 2^-24 / 2^-8 = 0.14 at the longest K range used here: 0.85 holds with room at every case.
 POS_DECISIVE_FLOOR = 0.85
+
+
+def pos_decisive_floor(terms):
+  """0.85 up to the 4608 terms it was derived for; beyond (the 5 x 5 layers of ClusterNet6c: 6400 terms in the forward
+  of 256 -> 512 and the backward-data of 128 -> 256, 12800 in the backward-data of 256 -> 512) the same expression,
+  1 - 2 terms 2^-24 / 2^-8, less the same margin of 0.01: 0.795 and 0.599."""
+  return POS_DECISIVE_FLOOR if terms <= 4608 else 1.0 - 2.0 * terms * 2.0 ** -24 / 2.0 ** -8 - 0.01
+
+
 # mixed, cases of <= 576 terms only: the float64 references of CONV_CASES give 0.960 / 0.975 at 64 / 128 terms and
 # 0.544-0.559 at 576 (forward and backward-data alike); the floors are the smallest of those figures less a margin of
 # 0.1 for another shape's draw.  Beyond 576 terms the share falls to 0.23 (1152) and 0 (4608): no floor, `pos` decides.
@@ -91,6 +100,15 @@ class Case(object):
 def of(case_tuple, **kw):
   cin, cout, K, s, p, N, H = case_tuple
   return Case(cin, cout, K, s, p, N, H, **kw)
+
+
+# Layer geometries of tests/conv_layer_cases.py that tests/test_gpu_kernels.py's CONV_CASES lack, for the brackets (the
+# lattice of tests/test_gpu_conv_layers_exact.py is blind to rounding): the three 25-tap 5 x 5 layers of ClusterNet6c
+# (PT border 2) at batches that leave a tail after whole tiles (M = 432, 180, 261), 512 -> 512 on a 3 x 3 plane where
+# every pixel is a border pixel (M = 261), 64 -> 64 on 33 x 33 (the persistent kernel, M = 1089) and the stride-2
+# 128 -> 256 on 17 x 17 (four parity classes of 81 / 72 / 72 / 64 rows per image).
+LAYER_CASES = [Case(64, 128, 5, 1, 2, 3, 12, P=2), Case(128, 256, 5, 1, 2, 5, 6, P=2), Case(256, 512, 5, 1, 2, 29, 3, P=2),
+               Case(512, 512, 3, 1, 1, 29, 3), Case(64, 64, 3, 1, 1, 1, 33), Case(128, 256, 3, 2, 1, 3, 17)]
 
 
 def bf16(t):

@@ -87,17 +87,30 @@ def test_assert_in_bracket_reports_and_records():
 
 
 # ---- 1. the condition ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", [cc.of(t) for t in CONV_CASES], ids=repr)
+@pytest.mark.parametrize("case", [cc.of(t) for t in CONV_CASES] + cc.LAYER_CASES, ids=repr)
 def test_decisive_share_holds_from_the_reference_alone(case):
+  """(cc.LAYER_CASES: the layer geometries of tests/conv_layer_cases.py.  The 5 x 5 layers reach 6400 and 12800 terms,
+  where cc.pos_decisive_floor continues the expression 0.85 was derived from: 0.795 and 0.599.)"""
   for kind, bracket, terms in (("forward", cc.forward_bracket, case.terms_fwd),
                                ("backward-data", cc.backward_data_bracket, case.terms_bd)):
     for draw in cc.DRAWS:
       _, _, lo, hi = bracket(case, draw)
       share = cc.decisive_share(lo, hi)
-      _report(case=repr(case), kind=kind, draw=draw, terms=terms, decisive=share)
-      floor = cc.POS_DECISIVE_FLOOR if draw == "pos" else cc.mixed_decisive_floor(terms)
+      floor = cc.pos_decisive_floor(terms) if draw == "pos" else cc.mixed_decisive_floor(terms)
+      _report(case=repr(case), kind=kind, draw=draw, terms=terms, decisive=share, floor=floor)
       if floor is not None:
         assert share >= floor, (kind, draw, terms, share, floor)
+
+
+def test_floors_beyond_4608_terms_and_the_layer_cases_are_layers_of_the_table():
+  assert cc.pos_decisive_floor(64) == cc.pos_decisive_floor(4608) == cc.POS_DECISIVE_FLOOR == 0.85
+  assert abs(cc.pos_decisive_floor(6400) - (1 - 2 * 6400 / 65536.0 - 0.01)) < 1e-12 and 0.79 < cc.pos_decisive_floor(6400) < 0.80
+  assert abs(cc.pos_decisive_floor(12800) - (1 - 2 * 12800 / 65536.0 - 0.01)) < 1e-12 and 0.59 < cc.pos_decisive_floor(12800) < 0.60
+  assert sorted({t for c in cc.LAYER_CASES for t in (c.terms_fwd, c.terms_bd) if t > 4608}) == [6400, 12800]
+  from tests import conv_layer_cases as lc
+  table = {lc.geometry(e) for e in lc.ENTRIES}
+  for c in cc.LAYER_CASES:
+    assert (c.cin, c.cout, c.K, c.s, c.p, c.d, c.H, c.W, c.P) in table, c
 
 
 # ---- 2. correct emulations stay inside ---------------------------------------------------------------------------------

@@ -112,10 +112,14 @@ def _borders_zero(pt, P, what):
 
 def _operand(sh, w_dev, operand, bwd, geoms):
   """rows = the row-major bf16 operand of ops.weight_prep (first-generation kernel); frag = ops.PreppedWeights (the
-  weights-direct kernels wherever ops.frag_supported); f32 = the parameter itself (exact-fp32 path)."""
+  weights-direct kernels wherever ops.frag_supported, else skipped); product = the same handle without the skip (a
+  stride-2 layer whose one-tap parity class only the first-generation kernel serves: tests/test_gpu_conv_layers_exact.py
+  asserts which geometries are refused); f32 = the parameter itself (exact-fp32 path)."""
   from iic_amd import ops
   if operand == "rows":
     return ops.weight_prep(w_dev)[1 if bwd else 0]
+  if operand == "product":      # the handle the architectures pass: ops.conv_igemm takes each geometry to the kernel that serves it
+    return ops.PreppedWeights(w_dev)[1 if bwd else 0]
   if operand == "frag" and not all(ops.frag_supported(g) for g in geoms):
     assert not (sh.cin == 64 and sh.cout == 64 and sh.K == 3 and sh.s == 1), "64->64 3x3 must run on the persistent kernel"
     pytest.skip("geometry not served by the weights-direct kernels (library: iic_conv_igemm_frag_supported = 0)")
@@ -387,11 +391,12 @@ RED = [(Shape(128, 128, 3, 1, 1, 40, 13), False, True), (Shape(256, 128, 3, 1, 1
        (Shape(512, 512, 3, 1, 1, 16, 7, dens=(QUARTER, HALF), seed=1), True, True)]
 
 
-@pytest.mark.parametrize("sh,has2,masked", RED, ids=["%r-y2%d-mask%d" % (s, h, m) for s, h, m in RED])
-def test_fused_bn_backward_reduction_exact(sh, has2, masked):
+def _fused_reduction(sh, has2, masked, require=True):
   """iic_conv_igemm_frag_red: red_stats += (sum g, sum g*y) [and (sum g, sum g*y2)] over the stored gradient g, masked
   with (scale*y + shift > 0) when the BatchNorm's coefficients are given.  g is an integer, y and y2 are on the lattice,
-  scale and shift are powers of two (so the mask expression is exact): the four sums are exact integers."""
+  scale and shift are powers of two (so the mask expression is exact): the four sums are exact integers.  Of a layer
+  with several parity classes, every class ops.red_supported serves carries the reduction and the sums are expected over
+  the pixels of those classes; the other classes are launched without one.  require=False: skip where no class is served."""
   from iic_amd import geom, ops
   dy, w = sh.dy(), sh.w()
   r = sh.ref_backward_data(dy, w)
@@ -401,26 +406,44 @@ def test_fused_bn_backward_reduction_exact(sh, has2, masked):
   rng = sh.rng(16)
   scale = torch.from_numpy(rng.choice([1.0, -1.0, 2.0, 0.5, -0.25], sh.cin)).double()
   shift = torch.from_numpy(rng.choice([0.5, -0.5, 0.25, 0.0, -2.0, 1.0], sh.cin)).double()
+  geoms = geom.bwd_data_geoms(sh.spec, sh.N, sh.H, sh.W, sh.P, sh.P)
+  pw = ops.PreppedWeights(w.to(dev()))
+  served = [ops.red_supported(g, pw[1]) for g in geoms]
+  if not any(served):
+    assert not require, "no parity class of %r carries a fused reduction" % sh
+    pytest.skip("library: iic_conv_igemm_red_supported = 0 for this geometry")
+  inred = torch.zeros(sh.H, sh.W, dtype=torch.bool)      # pixels whose launch carries the reduction
+  for g, ok in zip(geoms, served):
+    if ok:
+      inred |= _covered(sh, [g])
   gm = gexp * ((y * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)) > 0).double() if masked else gexp
+  gm = gm * inred.double()
   want = [torch.stack([gm.sum((0, 2, 3)), (gm * y).sum((0, 2, 3))]), torch.stack([gm.sum((0, 2, 3)), (gm * y2).sum((0, 2, 3))])]
   assert float(gm.abs().sum((0, 2, 3)).max()) < F32_EXACT_BOUND      # any float partial of these sums is exact
-  (gb,) = geom.bwd_data_geoms(sh.spec, sh.N, sh.H, sh.W, sh.P, sh.P)
-  pw = ops.PreppedWeights(w.to(dev()))
-  if not ops.red_supported(gb, pw[1]):
-    pytest.skip("library: iic_conv_igemm_red_supported = 0 for this geometry")
-  sh.figures(kind="fused reduction", has2=has2, masked=masked, max_ref=top, max_abs_sum=float(gm.abs().sum((0, 2, 3)).max()))
+  sh.figures(kind="fused reduction", has2=has2, masked=masked, max_ref=top, max_abs_sum=float(gm.abs().sum((0, 2, 3)).max()),
+             classes=len(geoms), classes_reduced=sum(served))
   P = sh.P
   coef = torch.stack([scale.float(), shift.float(), torch.zeros(sh.cin), torch.ones(sh.cin), torch.zeros(sh.cin)]).to(dev())
   pt = lambda t: ops.pt_from_nchw(t.float().to(dev()), P)
   dx = torch.zeros((sh.N, sh.H + 2 * P, sh.W + 2 * P, sh.cin), dtype=torch.bfloat16, device=dev())
   s1, s2 = ops.new_stats(sh.cin, dev()), ops.new_stats(sh.cin, dev())
-  ops.conv_igemm(gb, pt(dy), pw[1], dx, res_grad=pt(rg), res_act=pt(ra), premask=True,
-                 red=(pt(y), coef if masked else None, s1, pt(y2) if has2 else None, s2 if has2 else None))
+  dyp, rgp, rap, yp, y2p = pt(dy), pt(rg), pt(ra), pt(y), pt(y2)
+  for g, ok in zip(geoms, served):
+    red = (yp, coef if masked else None, s1, y2p if has2 else None, s2 if has2 else None) if ok else None
+    ops.conv_igemm(g, dyp, pw[1], dx, res_grad=rgp, res_act=rap, premask=True, red=red)
   torch.cuda.synchronize()
-  assert_exact(ops.pt_to_nchw(dx, P), gexp, "gradient stored by the fused launch")
+  cov = _covered(sh, geoms)
+  assert_exact(ops.pt_to_nchw(dx, P), gexp * cov.double(), "gradient stored by the fused launch")
   assert_exact(ops.stats_decode(s1, sh.cin).cpu(), want[0], "fused sums (sum g, sum g*y)")
   if has2:
     assert_exact(ops.stats_decode(s2, sh.cin).cpu(), want[1], "fused sums (sum g, sum g*y2)")
+
+
+@pytest.mark.parametrize("sh,has2,masked", RED, ids=["%r-y2%d-mask%d" % (s, h, m) for s, h, m in RED])
+def test_fused_bn_backward_reduction_exact(sh, has2, masked):
+  from iic_amd import geom
+  (gb,) = geom.bwd_data_geoms(sh.spec, sh.N, sh.H, sh.W, sh.P, sh.P)      # stride 1: one launch, as the trunk fuses it
+  _fused_reduction(sh, has2, masked, require=False)
 
 
 # --------------------------------------------------------------------------------------

@@ -286,6 +286,36 @@ def test_f32_weight_gradient_within_float64_bound(case, draw):
   _backward_weight(case, draw, operand="f32")
 
 
+# --------------------------------------------------------------------------------------
+# layer geometries of tests/conv_layer_cases.py that CONV_CASES lack (cc.LAYER_CASES): the 25-tap 5 x 5 layers, a 3 x 3
+# plane, 64 -> 64 on 33 x 33, stride 2 on 17 x 17.  Bounds and brackets unchanged; families of their own ("layers-...")
+# so that their worst ratios are listed beside the others'.  The references of a (case, draw) are shared by its runs.
+# --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("draw", cc.DRAWS)
+@pytest.mark.parametrize("case", cc.LAYER_CASES, ids=repr)
+def test_layer_geometries_forward_and_statistics_in_float64_brackets(case, draw):
+  from iic_amd import geom, ops
+  assert ops.frag_supported(geom.fwd_geom(case.spec, case.N, case.H, case.W, case.P, case.P))
+  for operand in ("rows", "frag"):
+    _forward(case, draw, operand, tag="layers-" + operand)
+
+
+@pytest.mark.parametrize("draw", cc.DRAWS)
+@pytest.mark.parametrize("case", cc.LAYER_CASES, ids=repr)
+def test_layer_geometries_backward_data_and_epilogues_in_float64_brackets(case, draw):
+  from iic_amd import geom, ops
+  assert all(ops.frag_supported(g) for g in geom.bwd_data_geoms(case.spec, case.N, case.H, case.W, case.P, case.P))
+  for operand in ("rows", "frag"):
+    _backward_data(case, draw, operand, tag="layers-" + operand)
+
+
+@pytest.mark.parametrize("draw", cc.DRAWS)
+@pytest.mark.parametrize("case", cc.LAYER_CASES, ids=repr)
+def test_layer_geometries_weight_gradient_within_float64_bound(case, draw):
+  for use_tr in (False, True):
+    _backward_weight(case, draw, use_tr, splits=(1, 2, 3, None), tag="layers")
+
+
 DILATED = cc.Case(128, 128, 3, 1, 2, 4, 20, d=2, P=2)
 # padded row numbering (g.MP > plane), two images so that the padding rows sit inside the row range: H = 62 is the
 # smallest for which geom pads a 64 -> 128 layer with PT border 3
