@@ -59,6 +59,8 @@ _SIGNATURES = {
   "iic_seg_tiled_grad": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
   "iic_affine_warp_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_affine_warp_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_affine_warp_gather_supported": (c_int, [_P, c_int]),
+  "iic_affine_warp_bwd_gather": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
   "iic_conv_lds_bytes": (c_long, [POINTER(ConvGeom), c_int]),
   "iic_conv_igemm": (c_int, [POINTER(ConvGeom), _P, _P, _P, _P, _P, _P, c_int, _P]),
   "iic_conv_wgrad_nsplit": (c_int, [POINTER(ConvGeom)]),

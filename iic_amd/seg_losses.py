@@ -8,7 +8,9 @@ signature, same asserts (inputs require grad; affine / mask do not), returns
 potsdam.py:189-202 / cocostuff.py produce unless --use_random_affine, which no published run
 sets) are folded into the kernels' index arithmetic; general matrices (perform_affine_tf,
 transforms.py:131-143) and the sparse random translation (IID_losses.py:101-104,
-transforms.py:145-165) go through an explicit warp of the second view (csrc/warp.hip).
+transforms.py:145-165) go through an explicit warp of the second view (csrc/warp.hip), whose
+backward is a fixed-order gather (bit-reproducible like the rest) wherever the library serves
+the matrices -- WARP_BWD_GATHER below.
 
 Data-parallel: the raw per-shift joints are all-reduced (SUM) like the clustering loss.
 """
@@ -68,30 +70,49 @@ def _pixel_matrices(aff, H, W):
   return M.float()
 
 
+# Backward of the warp.  True = the gather kernel (iic_affine_warp_bwd_gather: fixed summation order, bit-reproducible)
+# wherever the library serves the batch's matrices; False = the float-atomic scatter (iic_affine_warp_bwd) always, for
+# A/B runs.  The scatter remains the backward of matrices the gather kernel refuses -- shrinking by more than
+# IIC_WARP_GATHER_CAP allows (to less than about 0.3 of the size), the one corner whose gradient bits depend on the run.
+WARP_BWD_GATHER = [True]
+
+
 class _AffineWarpFn(torch.autograd.Function):
-  """perform_affine_tf + random_translation_multiple of the second view (csrc/warp.hip)."""
+  """perform_affine_tf + random_translation_multiple of the second view (csrc/warp.hip).  host_mats: the host tensor
+  `mats` was uploaded from (float32 [n, 6], contiguous) -- the backward chooses its kernel from it without a copy from
+  the device; None = not known, the scatter kernel."""
 
   @staticmethod
-  def forward(ctx, x, mats, sx, sy):
+  def forward(ctx, x, mats, sx, sy, host_mats=None):
     assert x.is_cuda and x.dtype == F32 and x.dim() == 4
     x = x.contiguous()
     n, k, h, w = x.shape
     out = torch.empty_like(x)
     check(lib().iic_affine_warp_fwd(ptr(x), ptr(mats), ptr(out), n, k, h, w, int(sx), int(sy),
                                     stream_ptr()), "iic_affine_warp_fwd")
+    if host_mats is not None:
+      assert not host_mats.is_cuda and host_mats.dtype == F32 and host_mats.is_contiguous() and \
+        tuple(host_mats.shape) == (n, 6)
     ctx.save_for_backward(mats)
+    ctx.host_mats = host_mats
     ctx.meta = (n, k, h, w, int(sx), int(sy))
     return out
 
   @staticmethod
   def backward(ctx, dout):
     mats, = ctx.saved_tensors
+    host = ctx.host_mats
     n, k, h, w, sx, sy = ctx.meta
     dout = dout.contiguous()
     dx = torch.empty_like(dout)
-    check(lib().iic_affine_warp_bwd(ptr(dout), ptr(mats), ptr(dx), n, k, h, w, sx, sy, stream_ptr()),
-          "iic_affine_warp_bwd")
-    return dx, None, None, None
+    L = lib()
+    if WARP_BWD_GATHER[0] and host is not None and L.iic_affine_warp_gather_supported(ptr(host), n):
+      check(L.iic_affine_warp_bwd_gather(ptr(dout), ptr(mats), ptr(host), ptr(dx), n, k, h, w, sx, sy, stream_ptr()),
+            "iic_affine_warp_bwd_gather")
+    else:
+      check(L.iic_affine_warp_bwd(ptr(dout), ptr(mats), ptr(dx), n, k, h, w, sx, sy, stream_ptr()),
+            "iic_affine_warp_bwd")
+    return dx, None, None, None, None
 
 
 def _draw_sparse_shift(half_side_min, half_side_max):
@@ -197,8 +218,8 @@ def _seg_loss(x1_outs, x2_outs, all_affine2_to_1, all_mask_img1, lamb, half_T_si
     # (IID_losses.py:101-104): warp the second view explicitly, then the flip-free loss kernels
     bn, _, h, w = x2_outs.shape
     sx, sy = _draw_sparse_shift(half_T_side_sparse_min, half_T_side_sparse_max) if sparse else (0, 0)
-    mats = _pixel_matrices(all_affine2_to_1, h, w).to(x2_outs.device)
-    x2_outs = _AffineWarpFn.apply(x2_outs, mats, sx, sy)
+    host_mats = _pixel_matrices(all_affine2_to_1, h, w).contiguous()
+    x2_outs = _AffineWarpFn.apply(x2_outs, host_mats.to(x2_outs.device), sx, sy, host_mats)
     flips = torch.zeros((bn, 2), dtype=torch.int32)
   flips = flips.to(x1_outs.device)
   T = int(half_T_side_dense)

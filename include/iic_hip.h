@@ -146,6 +146,30 @@ int iic_affine_warp_fwd(const float* x, const float* pixel_mats, float* out, int
                         int shift_x, int shift_y, void* stream);
 int iic_affine_warp_bwd(const float* dout, const float* pixel_mats, float* dx, int N, int K, int H, int W,
                         int shift_x, int shift_y, void* stream);
+/* The same backward (the adjoint of perform_affine_tf, transforms.py:131-143, and of the shift) in gather form: no
+ * float atomics and no zero-fill, every element of dx written once -- bit-reproducible launch to launch and between
+ * eager launches and graph replay.  One thread owns one source pixel (u, v) and sums, for every k, the output pixels
+ * whose sampling point M_n (qx, qy, 1) falls in [u-1, u+1) x [v-1, v+1): it searches the bounding box of that
+ * square's preimage (centre and half-extents from the inverse of M_n's 2x2 part, in double, 1/64 pixel of slack a side,
+ * clamped to the image) and recomputes the forward's taps at every position of the box -- membership is decided by
+ * the forward's own arithmetic, the box only bounds the search.
+ *   Summation order: contributors in ascending (oy, ox); acc = +0.0f; acc = fl32(acc + fl32(w * dout)) with w the
+ *   forward's float32 tap weight; no FMA contraction.  With one contributor, or with exactly representable
+ *   contributions, these are iic_affine_warp_bwd's bits.  A NaN / inf of dout reaches exactly the source pixels its
+ *   output pixel taps (0 x inf = NaN, as in iic_affine_warp_bwd and grid_sample).
+ *   Range: matrices whose box is at most IIC_WARP_GATHER_CAP positions in each direction, i.e. with
+ *   det = m0 m4 - m1 m3:  2 ((|m4| + |m1|) / |det| + 1/64) + 1 < IIC_WARP_GATHER_CAP  and the same for
+ *   (|m3| + |m0|) / |det| -- every matrix the reference's random_affine draws (rotation +-30 deg, shear +-10 deg, scale
+ *   0.8-1.2, flips) up to an aspect ratio of 20:9 needs at most 7, shrinking to one half needs 6.
+ * iic_affine_warp_gather_supported(host_mats, N): 1 when the launch serves all N matrices, 0 when one of them is
+ *   singular, non-finite or beyond the cap (or the arguments are void).  host_mats is a HOST pointer to [N][6] floats.
+ * iic_affine_warp_bwd_gather: pixel_mats is the device copy of host_mats, a HOST pointer to the same [N][6] values; the
+ *   launch asks the query first and answers IIC_ERR_UNSUPPORTED, with nothing enqueued, where it says 0 (no device-to-host
+ *   copy anywhere).  Overwrites dx.                                                                              */
+#define IIC_WARP_GATHER_CAP 8
+int iic_affine_warp_gather_supported(const float* host_mats, int N);
+int iic_affine_warp_bwd_gather(const float* dout, const float* pixel_mats, const float* host_mats, float* dx, int N,
+                               int K, int H, int W, int shift_x, int shift_y, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Convolution as an im2col-free implicit GEMM on bf16 MFMA (fp32 accumulate).
