@@ -166,6 +166,11 @@ _SIGNATURES = {
   "iic_sup_bn_relu_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
   "iic_sup_cross_entropy": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
   "iic_sup_tencrop_acc": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+  "iic_kmeans_supported": (c_int, [c_long, c_int, c_int]),
+  "iic_kmeans_workspace_bytes": (c_long, [c_long, c_int, c_int]),
+  "iic_kmeans_assign": (c_int, [_P, c_long, _P, c_long, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+  "iic_kmeans_update": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_int, _P, _P, _P]),
+  "iic_kmeans_seed_potential": (c_int, [_P, c_long, c_long, c_int, _P, c_int, _P, c_int, _P, _P, _P]),
   "iic_probe_tr16": (c_int, [_P, _P]),
 }
 

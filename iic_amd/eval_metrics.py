@@ -56,3 +56,54 @@ def _acc(preds, targets, num_k, verbose=0):
   cnt = torch.empty((), dtype=torch.long, device=p.device)
   check(lib().iic_count_equal(ptr(p), ptr(t), p.numel(), ptr(cnt), stream_ptr()), "iic_count_equal")
   return int(cnt) / float(preds.shape[0])
+
+
+def nmi_ari_from_counts(counts):
+  """(NMI, ARI) of a contingency matrix, float64 on the host, with scikit-learn's definitions: mutual information over
+  the arithmetic mean of the two entropies (1.0 when both partitions are a single cluster), and the adjusted Rand index
+  in its pair-count form (1.0 for the trivial partitions scikit-learn special-cases)."""
+  c = np.asarray(counts, dtype=np.float64)
+  assert c.ndim == 2 and (c >= 0).all()
+  n = c.sum()
+  assert n > 0
+  a, b = c.sum(axis=1), c.sum(axis=0)
+
+  def entropy(m):
+    p = m[m > 0] / n
+    return float(-(p * np.log(p)).sum())
+  ha, hb = entropy(a), entropy(b)
+  if (a > 0).sum() == 1 and (b > 0).sum() == 1:
+    nmi = 1.0
+  else:
+    i, j = np.nonzero(c)
+    v = c[i, j]
+    mi = max(float(((v / n) * (np.log(v) + np.log(n) - np.log(a[i]) - np.log(b[j]))).sum()), 0.0)
+    nmi = mi / (0.5 * (ha + hb)) if mi > 0.0 else 0.0
+  # pair confusion: tn, fp, fn, tp over ordered pairs, as sklearn.metrics.pair_confusion_matrix
+  sum_sq = (c ** 2).sum()
+  tp = sum_sq - n
+  fp = (c.dot(b)).sum() - sum_sq
+  fn = (c.T.dot(a)).sum() - sum_sq
+  tn = n ** 2 - fp - fn - sum_sq
+  if fn == 0 and fp == 0:
+    ari = 1.0
+  else:
+    ari = 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+  return float(nmi), float(ari)
+
+
+def _nmi_ari(preds, targets):
+  assert (isinstance(preds, torch.Tensor) and isinstance(targets, torch.Tensor) and preds.is_cuda and targets.is_cuda)
+  assert (preds.shape == targets.shape)
+  kp, kt = int(preds.max()) + 1, int(targets.max()) + 1
+  return nmi_ari_from_counts(_counts(preds, targets, kp, kt))
+
+
+def _nmi(preds, targets):
+  """Reference signature (eval_metrics.py:73-75): normalised mutual information of two flat label tensors."""
+  return _nmi_ari(preds, targets)[0]
+
+
+def _ari(preds, targets):
+  """Reference signature (eval_metrics.py:77-78): adjusted Rand index of two flat label tensors."""
+  return _nmi_ari(preds, targets)[1]

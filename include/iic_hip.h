@@ -864,6 +864,44 @@ int iic_sup_cross_entropy(const float* logits, const long long* targets, float* 
 int iic_sup_tencrop_acc(const float* logits, const long long* targets, long long* counts, int B, int k, int crops,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * k-means on the nets' pre-head features (csrc/kmeans.hip) -- replaces
+ *   code/utils/cluster/baselines/triplets.py:134-173  (features copied to the host batch by batch, then
+ *                                                      sklearn.cluster.KMeans(n_clusters=gt_k).fit on the host)
+ *   code/utils/cluster/baselines/triplets.py:176-228  (triplets_eval's k-means branch consumes the labels)
+ * for the features of kmeans_use_features=True (code/archs/cluster/net5g.py:73-78, net6c.py:52-57).
+ * X: fp32 [n][d] with row stride ldx >= d (floats); C: fp32 [k][d], contiguous.
+ * Served: 1 <= k <= 256, 1 <= d <= 32768, 1 <= n < 2^31; anything else is IIC_ERR_UNSUPPORTED, ldx < d or a null
+ * pointer IIC_ERR_ARG, before a launch.  Dot products and one-hot sums run on the exact-fp32 MFMA pipe; no float
+ * atomics: per-workgroup partial sums in a tile order that depends on (n, d, k) only, added in ascending order --
+ * two runs give the same bits.
+ * state: 64 bytes on the device {int32 iter, converged, pause, changed; double shift, inertia, tol, pad}.  The host
+ * zeroes it and writes tol (the scaled tolerance) before the first iteration.  Once `converged` (1: no label changed,
+ * 2: shift <= tol) or `pause` (a cluster came out empty: the host relocates, clears pause and calls the update with
+ * force = 1) is set, every launch that is given the state returns at once without writing: a host may enqueue several
+ * iterations and read the state once.
+ * ------------------------------------------------------------------------------- */
+/* 1 when (n, d, k) is served, else 0.  Host only. */
+int iic_kmeans_supported(long n, int d, int k);
+/* bytes of the workspace `ws` of the three calls below for (n, d, k); 0 when unsupported.  Host only. */
+long iic_kmeans_workspace_bytes(long n, int d, int k);
+/* labels[i] = arg-min_j ||c_j||^2 - 2 x_i.c_j (ties to the lowest j, always in [0, k)), mind[i] = max(0, ||x_i||^2 +
+ * that score); sums [k][d] fp32 / counts [k] int64 of the rows per label (both null: assignment only); inertia
+ * (nullable) = sum_i mind[i] in float64.  state nullable: with it the latch is honoured and labels that differ from
+ * the incoming ones are counted into state.changed (fill labels with -1 before the first iteration). */
+int iic_kmeans_assign(const float* X, long ldx, const float* C, long n, int d, int k, int* labels, float* mind,
+                      float* sums, long long* counts, double* inertia, void* ws, void* state, void* stream);
+/* c_j <- sums_j / counts_j (a cluster with count 0 keeps its row); state.shift = sum ||c_new - c_old||^2,
+ * state.inertia = the sum of mind of the preceding iic_kmeans_assign on the same ws, both float64 in a fixed order;
+ * iter += 1; the latch as above.  A count of 0 with force == 0 changes nothing but state.pause = 1. */
+int iic_kmeans_update(float* C, const float* sums, const long long* counts, long n, int d, int k, int force, void* ws,
+                      void* state, void* stream);
+/* k-means++ support.  cand: int64 [ncand] row indices on the device, 1 <= ncand <= 8 (clamped to [0, n)).
+ * pot[c] = sum_i min(mind[i], ||x_i - x_cand[c]||^2), float64, fixed order.  write != 0 (ncand == 1):
+ * mind[i] <- min(mind[i], distance to the candidate) as well.  ws: iic_kmeans_workspace_bytes(n, d, 1) bytes. */
+int iic_kmeans_seed_potential(const float* X, long ldx, long n, int d, const long long* cand, int ncand, float* mind,
+                              int write, double* pot, void* ws, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
