@@ -185,6 +185,17 @@ def _bn_training(bn):
   return bn.training or not bn.track_running_stats
 
 
+def _bn_coef(bn, stats, gamma, beta, C, count):
+  """ops.bn_finalize for one forward of `bn`: from the batch statistics in `stats` (the running statistics are updated
+  only when the module itself is in training mode), or from the running statistics."""
+  rm, rv, nbt = _bn_buffers(bn)
+  if _bn_training(bn):
+    upd = bn.training
+    return ops.bn_finalize(stats, gamma.detach(), beta.detach(), rm if upd else None,
+                           rv if upd else None, nbt if upd else None, C, count, True)
+  return ops.bn_finalize(None, gamma.detach(), beta.detach(), rm, rv, None, C, count, False)
+
+
 def _frozen_runs_eagerly(ctx):
   """A forward that will be differentiated through a BatchNorm on running statistics (eval(), a frozen layer) is not
   captured into a HIP graph: iic_amd.graphed leaves such a module to eager launches (graphed.eligible), and a capture
@@ -208,19 +219,15 @@ class _StemFn(torch.autograd.Function):
     x = x.contiguous().float()
     N, C, H, W = x.shape
     bn = mod.bn1
-    rm, rv, nbt = _bn_buffers(bn)
     training = _bn_training(bn)
     if not training:
       _frozen_runs_eagerly(ctx)
     wd = w.detach()
+    st = None
     if training:
       st = mod._h_conv1.stats(x.device)
       ops.stem_stats(x, wd, st)
-      coef = ops.bn_finalize(st, gamma.detach(), beta.detach(), rm if bn.training else None,
-                             rv if bn.training else None, nbt if bn.training else None, 64,
-                             N * H * W, True)
-    else:
-      coef = ops.bn_finalize(None, gamma.detach(), beta.detach(), rm, rv, None, 64, N * H * W, False)
+    coef = _bn_coef(bn, st, gamma, beta, 64, N * H * W)
     Ho, Wo = H // 2 + 1, W // 2 + 1
     out = ops.pt_alloc(N, Ho, Wo, 64, 1, x.device)
     ops.stem_apply_pool(x, wd, coef, out)
@@ -266,7 +273,6 @@ class _StemF32Fn(torch.autograd.Function):
     x = x.contiguous().float()
     N, C, H, W = x.shape
     bn, h = mod.bn1, mod._h_conv1
-    rm, rv, nbt = _bn_buffers(bn)
     training = _bn_training(bn)
     if not training:
       _frozen_runs_eagerly(ctx)
@@ -276,11 +282,7 @@ class _StemF32Fn(torch.autograd.Function):
     st = h.stats(dev) if training else None
     y = ops.pt_alloc(N, H, W, 64, 1, dev)
     ops.conv_igemm(gf, xp, h.weights()[0], y, stats=st)
-    if training:
-      coef = ops.bn_finalize(st, gamma.detach(), beta.detach(), rm if bn.training else None,
-                             rv if bn.training else None, nbt if bn.training else None, 64, N * H * W, True)
-    else:
-      coef = ops.bn_finalize(None, gamma.detach(), beta.detach(), rm, rv, None, 64, N * H * W, False)
+    coef = _bn_coef(bn, st, gamma, beta, 64, N * H * W)
     a = ops.bn_apply(y, coef, ops.pt_alloc(N, H, W, 64, 1, dev), N, H, W, 1, 64, relu=True)
     Ho, Wo = H // 2 + 1, W // 2 + 1
     out = ops.f32_maxpool_s2p1_fwd(a, ops.pt_alloc(N, Ho, Wo, 64, 1, dev), N, H, W, 64)
@@ -322,20 +324,12 @@ class _BlockFn(torch.autograd.Function):
     cnt = N * Ho * Wo
     need_grad = any(ctx.needs_input_grad)   # (grad mode is off inside Function.forward)
 
-    def bn_coef(bn, holder, gamma, beta, y_stats):
-      rm, rv, nbt = _bn_buffers(bn)
-      if _bn_training(bn):
-        upd = bn.training
-        return ops.bn_finalize(y_stats, gamma.detach(), beta.detach(), rm if upd else None,
-                               rv if upd else None, nbt if upd else None, planes, cnt, True)
-      return ops.bn_finalize(None, gamma.detach(), beta.detach(), rm, rv, None, planes, cnt, False)
-
     gf1, _ = h1.geoms(N, H, W)
     gf2, _ = h2.geoms(N, Ho, Wo)
     st1 = h1.stats(dev) if _bn_training(blk.bn1) else None
     y1 = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
     ops.conv_igemm(gf1, x, h1.weights()[0], y1, stats=st1)
-    coef1 = bn_coef(blk.bn1, h1, g1, b1, st1)
+    coef1 = _bn_coef(blk.bn1, st1, g1, b1, planes, cnt)
     # conv2 reads a1 = relu(bn1(y1)), made by a separate HBM pass.  (Round 4 built the fusion of that pass into conv2's
     # patch loader -- in LDS after the DMA -- bit-identical and 0.6-0.9 ms per step SLOWER; removed in round 5,
     # LAB.md section R5.3 has the arithmetic of why the register variant cannot pay either.)
@@ -344,7 +338,7 @@ class _BlockFn(torch.autograd.Function):
     a1 = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
     ops.bn_apply(y1, coef1, a1, N, Ho, Wo, 1, planes, relu=True)
     ops.conv_igemm(gf2, a1, h2.weights()[0], y2, stats=st2)
-    coef2 = bn_coef(blk.bn2, h2, g2, b2, st2)
+    coef2 = _bn_coef(blk.bn2, st2, g2, b2, planes, cnt)
     out = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
     yd = coefd = None
     if hd is not None:
@@ -353,7 +347,7 @@ class _BlockFn(torch.autograd.Function):
       std = hd.stats(dev) if _bn_training(bnd) else None
       yd = ops.pt_alloc(N, Ho, Wo, planes, 1, dev)
       ops.conv_igemm(gfd, x, hd.weights()[0], yd, stats=std)
-      coefd = bn_coef(bnd, hd, gd, bd, std)
+      coefd = _bn_coef(bnd, std, gd, bd, planes, cnt)
       ops.bn_apply(y2, coef2, out, N, Ho, Wo, 1, planes, y2=yd, coef2=coefd, relu=True)
     else:
       ops.bn_apply(y2, coef2, out, N, Ho, Wo, 1, planes, res=x, relu=True)

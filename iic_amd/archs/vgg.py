@@ -16,7 +16,7 @@ import torch.nn as nn
 from .. import geom as G
 from .. import ops
 from ..dist import shard_batch
-from .cluster import (FUSE_RED, _ApplyCounter, _ConvHolder, _HeadsFn, _bn_buffers, _bn_training,
+from .cluster import (FUSE_RED, _ApplyCounter, _ConvHolder, _HeadsFn, _bn_coef, _bn_training,
                       _frozen_runs_eagerly)
 
 import os
@@ -40,7 +40,6 @@ class _StageFn(torch.autograd.Function):
     training = _bn_training(bn)
     if not training:
       _frozen_runs_eagerly(ctx)
-    rm, rv, nbt = _bn_buffers(bn)
     C = st.cout
     if st.first:
       assert x.is_cuda, "HIP path needs a device tensor -- no CPU fallback"
@@ -64,12 +63,7 @@ class _StageFn(torch.autograd.Function):
       stt = st.holder.stats(dev) if training else None
       ops.conv_igemm(gf, x, st.holder.weights()[0], y, stats=stt)
     cnt = N * Ho * Wo
-    if training:
-      upd = bn.training
-      coef = ops.bn_finalize(stt, gamma.detach(), beta.detach(), rm if upd else None,
-                             rv if upd else None, nbt if upd else None, C, cnt, True)
-    else:
-      coef = ops.bn_finalize(None, gamma.detach(), beta.detach(), rm, rv, None, C, cnt, False)
+    coef = _bn_coef(bn, stt, gamma, beta, C, cnt)
     # pooled stages (bf16 path): the activation a = relu(bn(y)) is never stored -- the pool recomputes it from (y, coef)
     # bit for bit, forward and backward (csrc/vgg.hip maxpool2_*_kernel<true>): one full-tensor write + read less
     fused_pool = st.pool and FUSE_POOL[0] and ops.PT_DTYPE[0] is not torch.float32

@@ -9,7 +9,16 @@
 // Forward statistics (sum, sum of squares per channel) are produced by the conv kernel's
 // epilogue into IIC_STAT_STRIPES stripes; bn_finalize folds them into per-channel
 // scale/shift.  Backward: bn_bwd_reduce (sum g, sum g*y) -> bn_bwd_finalize (c1,c2,c3,
-// dgamma, dbeta) -> bn_bwd_apply (dy = c1*g + c2*y + c3), with g = dout * (act > 0).
+// dgamma, dbeta) -> bn_bwd_apply (dy = c1*g + c2*y + c3), with g = dout * (act > 0); on running
+// statistics the one pass bn_bwd_frozen (dy = scale*g, the same two sums) -> bn_bwd_finalize_frozen.
+//
+// The streaming backward kernels (bn_bwd_reduce2, bn_bwd_apply2, bn_bwd_frozen) are a coefficient preload and a
+// per-pixel body around four pieces that exist once: the lane layout (bn_lanes), the gradient mask (bn_mask_coef,
+// bn_mask), the pixel walk (bn_px_walk) and the end of a reduction (BN_BLOCK_SUMS); one host ladder (bn_dispatch)
+// picks the instantiation.  The product library instantiates only what its compiled-in switches can launch; the
+// first-generation reduction and the plain-load variants exist in the instrumented library alone.
+#include <type_traits>
+
 #include "common.h"
 #include "../../include/iic_hip.h"
 
@@ -142,87 +151,116 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(
   *reinterpret_cast<uint4*>(out + off) = pack8(v);
 }
 
-// sums[stripe][0][C] += sum g ; sums[stripe][1][C] += sum g*y   (g = dout * (act > 0))
-// block = 256 threads: channel chunk = tid % (C/8), pixel lane = tid / (C/8); grid-stride over rows.
-// MASK: 0 = g = dout, 1 = g = dout * (act > 0), 2 = g = dout * (scale*y + shift > 0) with the
-// forward coefficients mcoef: act = relu(scale*y + shift) was produced by bn_apply with exactly
-// this expression, so the mask is identical and the activation tensor is not read (one tensor
-// less).  HAS2: second BatchNorm (downsample branch) sharing g.
+// ---------------------------------------------------------------------------------------------
+// Pieces that every backward kernel with per-channel registers is made of (each exists once).
+//
+// Lane layout of a 256-thread block: a thread owns the 8-channel chunk c8 = tid % (C/8) and the pixel lane
+// pl = tid / (C/8); the PL = 256 / (C/8) pixel lanes of a block take pixels PL apart.
+struct BnLanes {
+  int c8n, PL, c8, pl;
+};
+__device__ __forceinline__ BnLanes bn_lanes(int C) {
+  BnLanes l;
+  l.c8n = C >> 3;
+  l.PL = 256 / l.c8n;
+  l.c8 = threadIdx.x % l.c8n;
+  l.pl = threadIdx.x / l.c8n;
+  return l;
+}
+
+// The gradient mask.  MASK: 0 = g = dout, 1 = g = dout * (act > 0), 2 = g = dout * (scale*y + shift > 0) with the
+// forward coefficients mcoef: act = relu(scale*y + shift) was produced by bn_apply with exactly this expression, so
+// the mask is identical and the activation tensor is not read (one tensor less).
+template <int MASK>
+__device__ __forceinline__ void bn_mask_coef(const float* __restrict__ mcoef, int C, int c8, float* msc, float* msh) {
+  if constexpr (MASK == 2) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      msc[i] = mcoef[c8 * 8 + i];
+      msh[i] = mcoef[C + c8 * 8 + i];
+    }
+  }
+}
+// g: dout of one pixel, masked in place; ra: the raw 16 bytes of act (read for MASK 1 only); v: y of that pixel
+template <int MASK>
+__device__ __forceinline__ void bn_mask(float* g, const uint4 ra, const float* v, const float* msc, const float* msh) {
+  if constexpr (MASK == 1) {
+    float a[8];
+    unpack8(ra, a);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) g[i] = a[i] > 0.f ? g[i] : 0.f;
+  } else if constexpr (MASK == 2) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) g[i] = (v[i] * msc[i] + msh[i]) > 0.f ? g[i] : 0.f;
+  }
+}
+
+// End of a reducing kernel: the per-thread sums (sum g, sum g*y and, with HAS2 -- a second BatchNorm, the downsample
+// branch, sharing g -- sum g*y2) are added over the block's pixel lanes through LDS, one round per sum, and go to the
+// exact accumulators:  sums[stripe][0][C] += sum g ; sums[stripe][1][C] += sum g*y ; sums2 likewise with y2.
+// A macro, not a function: the choice among the three arrays is then compiled in the frame that owns them.  Behind a
+// call, inlined or not, the compiler pairs the HAS2 kernels' accumulations differently in their pixel loops:
+// bn_bwd_reduce2_kernel<0,true,true> 64 -> 72 VGPRs (8 -> 7 waves), the HAS2 reductions 1-2 % slower at 13x13x256 and
+// 7x7x512 (profiles/bn_refactor_ab.txt).  l: the BnLanes of the kernel.
+#define BN_BLOCK_SUMS(HAS2, sg, sgy, sgy2, sums, sums2, C, l)                                  \
+  do {                                                                                         \
+    __shared__ float s_acc[256 * 8];                                                           \
+    const int stripe = blockIdx.x % IIC_STAT_STRIPES;                                          \
+    for (int which = 0; which < (HAS2 ? 3 : 2); ++which) {                                     \
+      const float* src = which == 0 ? sg : (which == 1 || !HAS2 ? sgy : sgy2);                 \
+      __syncthreads();                                                                         \
+      _Pragma("unroll") for (int i = 0; i < 8; ++i)                                            \
+        s_acc[(l.pl * l.c8n + l.c8) * 8 + i] = src[i];                                         \
+      __syncthreads();                                                                         \
+      for (int c = threadIdx.x; c < C; c += 256) {                                             \
+        float t = 0.f;                                                                         \
+        for (int p = 0; p < l.PL; ++p) t += s_acc[(p * l.c8n + (c >> 3)) * 8 + (c & 7)];       \
+        if (which == 0) {                                                                      \
+          iic_stat_add(sums, stripe, C, c, 0, t);                                              \
+          if (HAS2) iic_stat_add(sums2, stripe, C, c, 0, t);                                   \
+        } else if (which == 1) {                                                               \
+          iic_stat_add(sums, stripe, C, c, 1, t);                                              \
+        } else {                                                                               \
+          iic_stat_add(sums2, stripe, C, c, 1, t);                                             \
+        }                                                                                      \
+      }                                                                                        \
+    }                                                                                          \
+  } while (0)
+
+#ifdef IIC_DEBUG_HOOKS
+// First generation of the reduction (g_bn_v2 = 0; instrumented library only: the reference of the kernel-generation
+// test and the v1 column of tools/bn_perf.py): grid-stride over rows, a row's pixels PL apart.
 template <int MASK, bool HAS2>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     const bf16_t* __restrict__ dout, const bf16_t* __restrict__ act, const bf16_t* __restrict__ y,
     const bf16_t* __restrict__ y2, float* __restrict__ sums, float* __restrict__ sums2,
     const float* __restrict__ mcoef, int N, int H, int W, int P, int C) {
-  __shared__ float s_acc[256 * 8];
-  const int c8n = C >> 3;
-  const int PL = 256 / c8n;
-  const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
+  const BnLanes l = bn_lanes(C);
   const int Hp = H + 2 * P, Wp = W + 2 * P;
-  float sg[8], sgy[8], sgy2[HAS2 ? 8 : 1], msc[MASK == 2 ? 8 : 1], msh[MASK == 2 ? 8 : 1];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) sg[i] = sgy[i] = 0.f;
-  if (HAS2) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sgy2[HAS2 ? i : 0] = 0.f;
-  }
-  if (MASK == 2) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      msc[MASK == 2 ? i : 0] = mcoef[c8 * 8 + i];
-      msh[MASK == 2 ? i : 0] = mcoef[C + c8 * 8 + i];
-    }
-  }
+  float sg[8] = {}, sgy[8] = {}, sgy2[8] = {}, msc[8], msh[8];
+  bn_mask_coef<MASK>(mcoef, C, l.c8, msc, msh);
   const long rows = (long)N * H;
   for (long row = blockIdx.x; row < rows; row += gridDim.x) {
     const int n = (int)(row / H), yy = (int)(row - (long)n * H);
-    const long rbase = (((long)n * Hp + yy + P) * Wp + P) * C + c8 * 8;
-    for (int xq = pl; xq < W; xq += PL) {
+    const long rbase = (((long)n * Hp + yy + P) * Wp + P) * C + l.c8 * 8;
+    for (int xq = l.pl; xq < W; xq += l.PL) {
       const long off = rbase + (long)xq * C;
       float g[8], v[8];
       unpack8(*reinterpret_cast<const uint4*>(dout + off), g);
-      if (MASK == 1) {
-        float a[8];
-        unpack8(*reinterpret_cast<const uint4*>(act + off), a);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) g[i] = a[i] > 0.f ? g[i] : 0.f;
-      }
       unpack8(*reinterpret_cast<const uint4*>(y + off), v);
-      if (MASK == 2) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          g[i] = (v[i] * msc[MASK == 2 ? i : 0] + msh[MASK == 2 ? i : 0]) > 0.f ? g[i] : 0.f;
-      }
+      bn_mask<MASK>(g, MASK == 1 ? *reinterpret_cast<const uint4*>(act + off) : make_uint4(0, 0, 0, 0), v, msc, msh);
 #pragma unroll
       for (int i = 0; i < 8; ++i) { sg[i] += g[i]; sgy[i] += g[i] * v[i]; }
       if (HAS2) {
         unpack8(*reinterpret_cast<const uint4*>(y2 + off), v);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) sgy2[HAS2 ? i : 0] += g[i] * v[i];
+        for (int i = 0; i < 8; ++i) sgy2[i] += g[i] * v[i];
       }
     }
   }
-  const int stripe = blockIdx.x % IIC_STAT_STRIPES;
-  // three LDS reductions over the pixel lanes (sum g, sum g*y, sum g*y2)
-  for (int which = 0; which < (HAS2 ? 3 : 2); ++which) {
-    const float* src = which == 0 ? sg : (which == 1 || !HAS2 ? sgy : sgy2);
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s_acc[(pl * c8n + c8) * 8 + i] = src[i];
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-      float t = 0.f;
-      for (int p = 0; p < PL; ++p) t += s_acc[(p * c8n + (c >> 3)) * 8 + (c & 7)];
-      if (which == 0) {
-        iic_stat_add(sums, stripe, C, c, 0, t);
-        if (HAS2) iic_stat_add(sums2, stripe, C, c, 0, t);
-      } else if (which == 1) {
-        iic_stat_add(sums, stripe, C, c, 1, t);
-      } else {
-        iic_stat_add(sums2, stripe, C, c, 1, t);
-      }
-    }
-  }
+  BN_BLOCK_SUMS(HAS2, sg, sgy, sgy2, sums, sums2, C, l);
 }
+#endif
 
 // bcoef: [0]=c1 [1]=c2 [2]=c3 ; dy = c1*g + c2*y + c3
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
@@ -269,7 +307,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     unpack8(*reinterpret_cast<const uint4*>(act + off), a);
 #pragma unroll
     for (int i = 0; i < 8; ++i) g[i] = a[i] > 0.f ? g[i] : 0.f;
-  } else if (mcoef) {      // mask from y (see bn_bwd_reduce_kernel)
+  } else if (mcoef) {      // mask from y (see bn_mask)
     ld8(mcoef + c8 * 8, k1);
     ld8(mcoef + C + c8 * 8, k2);
 #pragma unroll
@@ -330,164 +368,34 @@ __device__ __forceinline__ void px_advance(PxWalk& w, int step, int H, int W, in
   }
 }
 
-template <int MASK, bool HAS2, bool NTL>
-__global__ __launch_bounds__(256) void bn_bwd_reduce2_kernel(
-    const bf16_t* __restrict__ dout, const bf16_t* __restrict__ act, const bf16_t* __restrict__ y,
-    const bf16_t* __restrict__ y2, float* __restrict__ sums, float* __restrict__ sums2,
-    const float* __restrict__ mcoef, long npx, long per, int H, int W, int P, int C) {
-  __shared__ float s_acc[256 * 8];
-  const int c8n = C >> 3;
-  const int PL = 256 / c8n;
-  const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
-  float sg[8], sgy[8], sgy2[HAS2 ? 8 : 1], msc[MASK == 2 ? 8 : 1], msh[MASK == 2 ? 8 : 1];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) sg[i] = sgy[i] = 0.f;
-  if (HAS2) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sgy2[HAS2 ? i : 0] = 0.f;
-  }
-  if (MASK == 2) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      msc[MASK == 2 ? i : 0] = mcoef[c8 * 8 + i];
-      msh[MASK == 2 ? i : 0] = mcoef[C + c8 * 8 + i];
-    }
-  }
+// The walk of one thread through its block's chunk [blockIdx.x * per, + per) of the npx interior pixels: the pixels
+// PL apart from pixel lane pl on, two per iteration with every load issued before the first use, then the odd pixel
+// (per is a multiple of 2*PL, bn_v2_grid, so only a ragged last chunk has one).  Calls
+//   body(off, g, v, ry2): element offset of the pixel's chunk, g = masked dout and v = y as 8 floats, ry2 = the raw
+//   16 bytes of y2 (zeros unless HAS2).
+template <int MASK, bool HAS2, bool NTL, class Body>
+__device__ __forceinline__ void bn_px_walk(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ act,
+                                           const bf16_t* __restrict__ y, const bf16_t* __restrict__ y2,
+                                           const float* __restrict__ mcoef, long npx, long per, int H, int W, int P,
+                                           int C, const BnLanes l, Body body) {
+  float msc[8], msh[8];
+  bn_mask_coef<MASK>(mcoef, C, l.c8, msc, msh);
   const long q0 = (long)blockIdx.x * per;
   const long q1 = q0 + per < npx ? q0 + per : npx;
-  auto accumulate = [&](const uint4 rg, const uint4 ra, const uint4 ry, const uint4 ry2) {
+  auto pixel = [&](long off, const uint4 rg, const uint4 ra, const uint4 ry, const uint4 ry2) {
     float g[8], v[8];
     unpack8(rg, g);
-    if (MASK == 1) {
-      float a[8];
-      unpack8(ra, a);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) g[i] = a[i] > 0.f ? g[i] : 0.f;
-    }
     unpack8(ry, v);
-    if (MASK == 2) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        g[i] = (v[i] * msc[MASK == 2 ? i : 0] + msh[MASK == 2 ? i : 0]) > 0.f ? g[i] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { sg[i] += g[i]; sgy[i] += g[i] * v[i]; }
-    if (HAS2) {
-      unpack8(ry2, v);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) sgy2[HAS2 ? i : 0] += g[i] * v[i];
-    }
+    bn_mask<MASK>(g, ra, v, msc, msh);
+    body(off, g, v, ry2);
   };
-  if (q0 + pl < q1) {
-    PxWalk wa = px_start(q0 + pl, H, W, P, C, c8);
-    long q = q0 + pl;
-    for (; q + PL < q1; q += 2 * PL) {          // two pixels per iteration
-      PxWalk wb = wa;
-      px_advance(wb, PL, H, W, P, C);
-      const uint4 z = make_uint4(0, 0, 0, 0);
-      const uint4 g0 = ld16<NTL>(dout + wa.off);
-      const uint4 g1 = ld16<NTL>(dout + wb.off);
-      const uint4 y0 = ld16<NTL>(y + wa.off);
-      const uint4 y1 = ld16<NTL>(y + wb.off);
-      const uint4 a0 = MASK == 1 ? ld16<NTL>(act + wa.off) : z;
-      const uint4 a1 = MASK == 1 ? ld16<NTL>(act + wb.off) : z;
-      const uint4 t0 = HAS2 ? ld16<NTL>(y2 + wa.off) : z;
-      const uint4 t1 = HAS2 ? ld16<NTL>(y2 + wb.off) : z;
-      accumulate(g0, a0, y0, t0);
-      accumulate(g1, a1, y1, t1);
-      wa = wb;
-      px_advance(wa, PL, H, W, P, C);
-    }
-    if (q < q1) {
-      const uint4 z = make_uint4(0, 0, 0, 0);
-      accumulate(ld16<NTL>(dout + wa.off),
-                 MASK == 1 ? ld16<NTL>(act + wa.off) : z,
-                 ld16<NTL>(y + wa.off),
-                 HAS2 ? ld16<NTL>(y2 + wa.off) : z);
-    }
-  }
-  const int stripe = blockIdx.x % IIC_STAT_STRIPES;
-  for (int which = 0; which < (HAS2 ? 3 : 2); ++which) {
-    const float* src = which == 0 ? sg : (which == 1 || !HAS2 ? sgy : sgy2);
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s_acc[(pl * c8n + c8) * 8 + i] = src[i];
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-      float t = 0.f;
-      for (int p = 0; p < PL; ++p) t += s_acc[(p * c8n + (c >> 3)) * 8 + (c & 7)];
-      if (which == 0) {
-        iic_stat_add(sums, stripe, C, c, 0, t);
-        if (HAS2) iic_stat_add(sums2, stripe, C, c, 0, t);
-      } else if (which == 1) {
-        iic_stat_add(sums, stripe, C, c, 1, t);
-      } else {
-        iic_stat_add(sums2, stripe, C, c, 1, t);
-      }
-    }
-  }
-}
-
-template <int MASK, bool HAS2, bool NTL>
-__global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(
-    const bf16_t* __restrict__ dout, const bf16_t* __restrict__ act, const bf16_t* __restrict__ y,
-    const float* __restrict__ bcoef, bf16_t* __restrict__ dy, const bf16_t* __restrict__ y2,
-    const float* __restrict__ bcoef2, bf16_t* __restrict__ dy2, const float* __restrict__ mcoef,
-    long npx, long per, int H, int W, int P, int C) {
-  const int c8n = C >> 3;
-  const int PL = 256 / c8n;
-  const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
-  float k1[8], k2[8], k3[8], m1[MASK == 2 ? 8 : 1], m2[MASK == 2 ? 8 : 1];
-  float j1[HAS2 ? 8 : 1], j2[HAS2 ? 8 : 1], j3[HAS2 ? 8 : 1];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    k1[i] = bcoef[c8 * 8 + i];
-    k2[i] = bcoef[C + c8 * 8 + i];
-    k3[i] = bcoef[2 * C + c8 * 8 + i];
-    if (MASK == 2) {
-      m1[MASK == 2 ? i : 0] = mcoef[c8 * 8 + i];
-      m2[MASK == 2 ? i : 0] = mcoef[C + c8 * 8 + i];
-    }
-    if (HAS2) {
-      j1[HAS2 ? i : 0] = bcoef2[c8 * 8 + i];
-      j2[HAS2 ? i : 0] = bcoef2[C + c8 * 8 + i];
-      j3[HAS2 ? i : 0] = bcoef2[2 * C + c8 * 8 + i];
-    }
-  }
-  const long q0 = (long)blockIdx.x * per;
-  const long q1 = q0 + per < npx ? q0 + per : npx;
-  auto emit = [&](long off, const uint4 rg, const uint4 ra, const uint4 ry, const uint4 ry2) {
-    float g[8], v[8], o[8];
-    unpack8(rg, g);
-    unpack8(ry, v);
-    if (MASK == 1) {
-      float a[8];
-      unpack8(ra, a);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) g[i] = a[i] > 0.f ? g[i] : 0.f;
-    } else if (MASK == 2) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        g[i] = (v[i] * m1[MASK == 2 ? i : 0] + m2[MASK == 2 ? i : 0]) > 0.f ? g[i] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = k1[i] * g[i] + k2[i] * v[i] + k3[i];
-    *reinterpret_cast<uint4*>(dy + off) = pack8(o);
-    if (HAS2) {
-      unpack8(ry2, v);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        o[i] = j1[HAS2 ? i : 0] * g[i] + j2[HAS2 ? i : 0] * v[i] + j3[HAS2 ? i : 0];
-      *reinterpret_cast<uint4*>(dy2 + off) = pack8(o);
-    }
-  };
-  if (q0 + pl >= q1) return;
-  PxWalk wa = px_start(q0 + pl, H, W, P, C, c8);
-  long q = q0 + pl;
+  if (q0 + l.pl >= q1) return;
+  PxWalk wa = px_start(q0 + l.pl, H, W, P, C, l.c8);
+  long q = q0 + l.pl;
   const uint4 z = make_uint4(0, 0, 0, 0);
-  for (; q + PL < q1; q += 2 * PL) {
+  for (; q + l.PL < q1; q += 2 * l.PL) {
     PxWalk wb = wa;
-    px_advance(wb, PL, H, W, P, C);
+    px_advance(wb, l.PL, H, W, P, C);
     const uint4 g0 = ld16<NTL>(dout + wa.off);
     const uint4 g1 = ld16<NTL>(dout + wb.off);
     const uint4 y0 = ld16<NTL>(y + wa.off);
@@ -496,16 +404,73 @@ __global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(
     const uint4 a1 = MASK == 1 ? ld16<NTL>(act + wb.off) : z;
     const uint4 t0 = HAS2 ? ld16<NTL>(y2 + wa.off) : z;
     const uint4 t1 = HAS2 ? ld16<NTL>(y2 + wb.off) : z;
-    emit(wa.off, g0, a0, y0, t0);
-    emit(wb.off, g1, a1, y1, t1);
+    pixel(wa.off, g0, a0, y0, t0);
+    pixel(wb.off, g1, a1, y1, t1);
     wa = wb;
-    px_advance(wa, PL, H, W, P, C);
+    px_advance(wa, l.PL, H, W, P, C);
   }
   if (q < q1)
-    emit(wa.off, ld16<NTL>(dout + wa.off),
-         MASK == 1 ? ld16<NTL>(act + wa.off) : z,
-         ld16<NTL>(y + wa.off),
-         HAS2 ? ld16<NTL>(y2 + wa.off) : z);
+    pixel(wa.off, ld16<NTL>(dout + wa.off),
+          MASK == 1 ? ld16<NTL>(act + wa.off) : z,
+          ld16<NTL>(y + wa.off),
+          HAS2 ? ld16<NTL>(y2 + wa.off) : z);
+}
+
+template <int MASK, bool HAS2, bool NTL>
+__global__ __launch_bounds__(256) void bn_bwd_reduce2_kernel(
+    const bf16_t* __restrict__ dout, const bf16_t* __restrict__ act, const bf16_t* __restrict__ y,
+    const bf16_t* __restrict__ y2, float* __restrict__ sums, float* __restrict__ sums2,
+    const float* __restrict__ mcoef, long npx, long per, int H, int W, int P, int C) {
+  const BnLanes l = bn_lanes(C);
+  float sg[8] = {}, sgy[8] = {}, sgy2[8] = {};
+  bn_px_walk<MASK, HAS2, NTL>(dout, act, y, y2, mcoef, npx, per, H, W, P, C, l,
+                              [&](long, const float* g, const float* v, const uint4 ry2) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { sg[i] += g[i]; sgy[i] += g[i] * v[i]; }
+    if (HAS2) {
+      float v2[8];
+      unpack8(ry2, v2);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sgy2[i] += g[i] * v2[i];
+    }
+  });
+  BN_BLOCK_SUMS(HAS2, sg, sgy, sgy2, sums, sums2, C, l);
+}
+
+template <int MASK, bool HAS2, bool NTL>
+__global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(
+    const bf16_t* __restrict__ dout, const bf16_t* __restrict__ act, const bf16_t* __restrict__ y,
+    const float* __restrict__ bcoef, bf16_t* __restrict__ dy, const bf16_t* __restrict__ y2,
+    const float* __restrict__ bcoef2, bf16_t* __restrict__ dy2, const float* __restrict__ mcoef,
+    long npx, long per, int H, int W, int P, int C) {
+  const BnLanes l = bn_lanes(C);
+  float k1[8], k2[8], k3[8], j1[8], j2[8], j3[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    k1[i] = bcoef[l.c8 * 8 + i];
+    k2[i] = bcoef[C + l.c8 * 8 + i];
+    k3[i] = bcoef[2 * C + l.c8 * 8 + i];
+    if (HAS2) {
+      j1[i] = bcoef2[l.c8 * 8 + i];
+      j2[i] = bcoef2[C + l.c8 * 8 + i];
+      j3[i] = bcoef2[2 * C + l.c8 * 8 + i];
+    }
+  }
+  bn_px_walk<MASK, HAS2, NTL>(dout, act, y, y2, mcoef, npx, per, H, W, P, C, l,
+                              [&](long off, const float* g, const float* v, const uint4 ry2) {
+    // fmaf spelled out: with two products the compiler may fuse either one, and which it takes decides the last bit
+    float o[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = fmaf(k1[i], g[i], k2[i] * v[i]) + k3[i];
+    *reinterpret_cast<uint4*>(dy + off) = pack8(o);
+    if (HAS2) {
+      float v2[8];
+      unpack8(ry2, v2);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = fmaf(j1[i], g[i], j2[i] * v2[i]) + j3[i];
+      *reinterpret_cast<uint4*>(dy2 + off) = pack8(o);
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -521,40 +486,16 @@ __global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(
     const float* __restrict__ coef2, bf16_t* __restrict__ dy2, float* __restrict__ sums,
     float* __restrict__ sums2, const float* __restrict__ mcoef, long npx, long per, int H, int W, int P,
     int C) {
-  __shared__ float s_acc[256 * 8];
-  const int c8n = C >> 3;
-  const int PL = 256 / c8n;
-  const int c8 = threadIdx.x % c8n, pl = threadIdx.x / c8n;
-  float sg[8], sgy[8], sgy2[HAS2 ? 8 : 1], k1[8], j1[HAS2 ? 8 : 1], msc[MASK == 2 ? 8 : 1], msh[MASK == 2 ? 8 : 1];
+  const BnLanes l = bn_lanes(C);
+  float sg[8] = {}, sgy[8] = {}, sgy2[8] = {}, k1[8], j1[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    sg[i] = sgy[i] = 0.f;
-    k1[i] = coef[c8 * 8 + i];
-    if (HAS2) {
-      sgy2[HAS2 ? i : 0] = 0.f;
-      j1[HAS2 ? i : 0] = coef2[c8 * 8 + i];
-    }
-    if (MASK == 2) {
-      msc[MASK == 2 ? i : 0] = mcoef[c8 * 8 + i];
-      msh[MASK == 2 ? i : 0] = mcoef[C + c8 * 8 + i];
-    }
+    k1[i] = coef[l.c8 * 8 + i];
+    if (HAS2) j1[i] = coef2[l.c8 * 8 + i];
   }
-  const long q0 = (long)blockIdx.x * per;
-  const long q1 = q0 + per < npx ? q0 + per : npx;
-  auto emit = [&](long off, const uint4 rg, const uint4 ra, const uint4 ry, const uint4 ry2) {
-    float g[8], v[8], o[8];
-    unpack8(rg, g);
-    unpack8(ry, v);
-    if (MASK == 1) {
-      float a[8];
-      unpack8(ra, a);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) g[i] = a[i] > 0.f ? g[i] : 0.f;
-    } else if (MASK == 2) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        g[i] = (v[i] * msc[MASK == 2 ? i : 0] + msh[MASK == 2 ? i : 0]) > 0.f ? g[i] : 0.f;
-    }
+  bn_px_walk<MASK, HAS2, NTL>(dout, act, y, y2, mcoef, npx, per, H, W, P, C, l,
+                              [&](long off, const float* g, const float* v, const uint4 ry2) {
+    float o[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       o[i] = k1[i] * g[i];
@@ -563,61 +504,17 @@ __global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(
     }
     *reinterpret_cast<uint4*>(dy + off) = pack8(o);
     if (HAS2) {
-      unpack8(ry2, v);
+      float v2[8];
+      unpack8(ry2, v2);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        o[i] = j1[HAS2 ? i : 0] * g[i];
-        sgy2[HAS2 ? i : 0] += g[i] * v[i];
+        o[i] = j1[i] * g[i];
+        sgy2[i] += g[i] * v2[i];
       }
       *reinterpret_cast<uint4*>(dy2 + off) = pack8(o);
     }
-  };
-  if (q0 + pl < q1) {
-    PxWalk wa = px_start(q0 + pl, H, W, P, C, c8);
-    long q = q0 + pl;
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    for (; q + PL < q1; q += 2 * PL) {          // two pixels per iteration
-      PxWalk wb = wa;
-      px_advance(wb, PL, H, W, P, C);
-      const uint4 g0 = ld16<NTL>(dout + wa.off);
-      const uint4 g1 = ld16<NTL>(dout + wb.off);
-      const uint4 y0 = ld16<NTL>(y + wa.off);
-      const uint4 y1 = ld16<NTL>(y + wb.off);
-      const uint4 a0 = MASK == 1 ? ld16<NTL>(act + wa.off) : z;
-      const uint4 a1 = MASK == 1 ? ld16<NTL>(act + wb.off) : z;
-      const uint4 t0 = HAS2 ? ld16<NTL>(y2 + wa.off) : z;
-      const uint4 t1 = HAS2 ? ld16<NTL>(y2 + wb.off) : z;
-      emit(wa.off, g0, a0, y0, t0);
-      emit(wb.off, g1, a1, y1, t1);
-      wa = wb;
-      px_advance(wa, PL, H, W, P, C);
-    }
-    if (q < q1)
-      emit(wa.off, ld16<NTL>(dout + wa.off),
-           MASK == 1 ? ld16<NTL>(act + wa.off) : z,
-           ld16<NTL>(y + wa.off),
-           HAS2 ? ld16<NTL>(y2 + wa.off) : z);
-  }
-  const int stripe = blockIdx.x % IIC_STAT_STRIPES;
-  for (int which = 0; which < (HAS2 ? 3 : 2); ++which) {
-    const float* src = which == 0 ? sg : (which == 1 || !HAS2 ? sgy : sgy2);
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s_acc[(pl * c8n + c8) * 8 + i] = src[i];
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-      float t = 0.f;
-      for (int p = 0; p < PL; ++p) t += s_acc[(p * c8n + (c >> 3)) * 8 + (c & 7)];
-      if (which == 0) {
-        iic_stat_add(sums, stripe, C, c, 0, t);
-        if (HAS2) iic_stat_add(sums2, stripe, C, c, 0, t);
-      } else if (which == 1) {
-        iic_stat_add(sums, stripe, C, c, 1, t);
-      } else {
-        iic_stat_add(sums2, stripe, C, c, 1, t);
-      }
-    }
-  }
+  });
+  BN_BLOCK_SUMS(HAS2, sg, sgy, sgy2, sums, sums2, C, l);
 }
 
 // dgamma = (sum g*y - running_mean * sum g) * invstd, dbeta = sum g; bcoef (nullable) = (scale, 0, 0): the
@@ -644,15 +541,44 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_frozen_kernel(
 // (tools/bn_perf.py: every reduce, and the apply unless it reads the activation tensor for its mask
 // -- with 3 reads + 1 write per element the deeper prefetch costs occupancy: 161 vs 158 us at
 // layer1, against 122 vs 145 us for the mask-from-y apply); 2: second generation everywhere (tests).
+// BN_MAY(cond): can `cond` on the switches hold in this build?  In the instrumented library they are variables, so
+// always; in the product they are constants, and a kernel they rule out is not instantiated.
 #ifdef IIC_DEBUG_HOOKS
 static int g_bn_v2 = 1;
 static int g_bn_v2_blocks = 1024;
+#define BN_MAY(cond) true
 #else
 static constexpr int g_bn_v2 = 1;
 static constexpr int g_bn_v2_blocks = 1024;
+#define BN_MAY(cond) (cond)
 #endif
 // 1 (default): the passes' streaming loads carry the non-temporal hint (see ld16); 0: plain loads (A/B runs)
 IIC_SWITCH(g_bn_nt, 1, iic_debug_bn_nt)
+
+// launch(nt) with g_bn_nt as a std::bool_constant
+template <class Launch>
+static void bn_dispatch_nt(Launch launch) {
+  if constexpr (BN_MAY(g_bn_nt != 0)) {
+    if (g_bn_nt) return launch(std::true_type{});
+  }
+  if constexpr (BN_MAY(g_bn_nt == 0)) {
+    if (!g_bn_nt) return launch(std::false_type{});
+  }
+}
+// The one ladder from (mask mode, second BatchNorm, non-temporal loads) to a kernel instantiation:
+// launch(m, h2, nt) gets them as std::integral_constant / std::bool_constant.  WITH_ACT = false: mode 1 cannot come.
+template <bool WITH_ACT, class Launch>
+static void bn_dispatch(int mode, bool has2, Launch launch) {
+  auto with_has2 = [&](auto m) {
+    bn_dispatch_nt([&](auto nt) {
+      if (has2) launch(m, std::true_type{}, nt); else launch(m, std::false_type{}, nt);
+    });
+  };
+  if constexpr (WITH_ACT) {
+    if (mode == 1) return with_has2(std::integral_constant<int, 1>{});
+  }
+  if (mode == 2) with_has2(std::integral_constant<int, 2>{}); else with_has2(std::integral_constant<int, 0>{});
+}
 
 // chunk of pixels per block: a multiple of 2*PL so that every thread's pair loop stays aligned
 // reduce != 0: the reduction kernels end with 2C (3C) integer atomics per block into the exact
@@ -728,10 +654,10 @@ int iic_bn_apply(const void* y, const float* coef, const void* res, const void* 
   if (C % 8 != 0) return IIC_ERR_UNSUPPORTED;
   if ((y2 == nullptr) != (coef2 == nullptr)) return IIC_ERR_ARG;
   dim3 grid(N * H, (W * (C / 8) + 255) / 256);
-#define BN_APPLY_LAUNCH(L_)                                                                                 \
-  hipLaunchKernelGGL((bn_apply_kernel<L_>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y, coef, \
-                     (const bf16_t*)res, (const bf16_t*)y2, coef2, (bf16_t*)out, H, W, P, C, relu)
-  if (g_bn_nt) BN_APPLY_LAUNCH(true); else BN_APPLY_LAUNCH(false);
+  bn_dispatch_nt([&](auto nt) {
+    hipLaunchKernelGGL((bn_apply_kernel<decltype(nt)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y,
+                       coef, (const bf16_t*)res, (const bf16_t*)y2, coef2, (bf16_t*)out, H, W, P, C, relu);
+  });
   return iic_launch_status();
 }
 
@@ -742,38 +668,29 @@ int iic_bn_bwd_reduce(const void* dout, const void* act, const void* y, const vo
   if (check_c(C)) return IIC_ERR_UNSUPPORTED;
   if ((y2 == nullptr) != (sums2 == nullptr)) return IIC_ERR_ARG;
   const int mode = act ? 1 : (mask_coef ? 2 : 0);
-  if (g_bn_v2) {
-    long per;
-    int grid2;
-    bn_v2_grid((long)N * H * W, C, per, grid2, 1);
-#define BN_RED2_LAUNCH_(M_, H2_, L_)                                                            \
-  hipLaunchKernelGGL((bn_bwd_reduce2_kernel<M_, H2_, L_>), dim3(grid2), dim3(256), 0,           \
-                     (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act,              \
-                     (const bf16_t*)y, (const bf16_t*)y2, sums, sums2, mask_coef,               \
-                     (long)N * H * W, per, H, W, P, C)
-#define BN_RED2_LAUNCH(M_, H2_)                                  \
-  do {                                                           \
-    if (g_bn_nt) BN_RED2_LAUNCH_(M_, H2_, true);                 \
-    else BN_RED2_LAUNCH_(M_, H2_, false);                        \
-  } while (0)
-    if (y2) {
-      if (mode == 1) BN_RED2_LAUNCH(1, true); else if (mode == 2) BN_RED2_LAUNCH(2, true); else BN_RED2_LAUNCH(0, true);
-    } else {
-      if (mode == 1) BN_RED2_LAUNCH(1, false); else if (mode == 2) BN_RED2_LAUNCH(2, false); else BN_RED2_LAUNCH(0, false);
-    }
+  const bool has2 = y2 != nullptr;
+#ifdef IIC_DEBUG_HOOKS
+  if (!g_bn_v2) {
+    long rows = (long)N * H;
+    int grid = (int)(rows < 2048 ? rows : 2048);
+    bn_dispatch<true>(mode, has2, [&](auto m, auto h2, auto) {
+      hipLaunchKernelGGL((bn_bwd_reduce_kernel<decltype(m)::value, decltype(h2)::value>), dim3(grid), dim3(256), 0,
+                         (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act, (const bf16_t*)y,
+                         (const bf16_t*)y2, sums, sums2, mask_coef, N, H, W, P, C);
+    });
     return iic_launch_status();
   }
-  long rows = (long)N * H;
-  int grid = (int)(rows < 2048 ? rows : 2048);
-#define BN_RED_LAUNCH(M_, H2_)                                                                  \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<M_, H2_>), dim3(grid), dim3(256), 0,                 \
-                     (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act,              \
-                     (const bf16_t*)y, (const bf16_t*)y2, sums, sums2, mask_coef, N, H, W, P, C)
-  if (y2) {
-    if (mode == 1) BN_RED_LAUNCH(1, true); else if (mode == 2) BN_RED_LAUNCH(2, true); else BN_RED_LAUNCH(0, true);
-  } else {
-    if (mode == 1) BN_RED_LAUNCH(1, false); else if (mode == 2) BN_RED_LAUNCH(2, false); else BN_RED_LAUNCH(0, false);
-  }
+#else
+  static_assert(g_bn_v2 != 0, "bn_bwd_reduce_kernel (first generation) exists in the instrumented library only");
+#endif
+  long per;
+  int grid2;
+  bn_v2_grid((long)N * H * W, C, per, grid2, 1);
+  bn_dispatch<true>(mode, has2, [&](auto m, auto h2, auto nt) {
+    hipLaunchKernelGGL((bn_bwd_reduce2_kernel<decltype(m)::value, decltype(h2)::value, decltype(nt)::value>),
+                       dim3(grid2), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act,
+                       (const bf16_t*)y, (const bf16_t*)y2, sums, sums2, mask_coef, (long)N * H * W, per, H, W, P, C);
+  });
   return iic_launch_status();
 }
 
@@ -797,21 +714,13 @@ int iic_bn_bwd_apply(const void* dout, const void* act, const void* y, const flo
     long per;
     int grid2;
     bn_v2_grid((long)N * H * W, C, per, grid2);
-#define BN_APP2_LAUNCH_(M_, H2_, L_)                                                             \
-  hipLaunchKernelGGL((bn_bwd_apply2_kernel<M_, H2_, L_>), dim3(grid2), dim3(256), 0,            \
-                     (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act,              \
-                     (const bf16_t*)y, bcoef, (bf16_t*)dy, (const bf16_t*)y2, bcoef2,           \
-                     (bf16_t*)dy2, mask_coef, (long)N * H * W, per, H, W, P, C)
-#define BN_APP2_LAUNCH(M_, H2_)                                  \
-  do {                                                           \
-    if (g_bn_nt) BN_APP2_LAUNCH_(M_, H2_, true);                 \
-    else BN_APP2_LAUNCH_(M_, H2_, false);                        \
-  } while (0)
-    if (y2) {
-      if (mode == 1) BN_APP2_LAUNCH(1, true); else if (mode == 2) BN_APP2_LAUNCH(2, true); else BN_APP2_LAUNCH(0, true);
-    } else {
-      if (mode == 1) BN_APP2_LAUNCH(1, false); else if (mode == 2) BN_APP2_LAUNCH(2, false); else BN_APP2_LAUNCH(0, false);
-    }
+    // (the act mode comes here under g_bn_v2 == 2 only)
+    bn_dispatch<BN_MAY(g_bn_v2 == 2)>(mode, y2 != nullptr, [&](auto m, auto h2, auto nt) {
+      hipLaunchKernelGGL((bn_bwd_apply2_kernel<decltype(m)::value, decltype(h2)::value, decltype(nt)::value>),
+                         dim3(grid2), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act,
+                         (const bf16_t*)y, bcoef, (bf16_t*)dy, (const bf16_t*)y2, bcoef2, (bf16_t*)dy2, mask_coef,
+                         (long)N * H * W, per, H, W, P, C);
+    });
     return iic_launch_status();
   }
   dim3 grid(N * H, (W * (C / 8) + 255) / 256);
@@ -834,21 +743,12 @@ int iic_bn_bwd_frozen(const void* dout, const void* act, const void* y, const fl
   long per;
   int grid2;
   bn_v2_grid((long)N * H * W, C, per, grid2, 1);
-#define BN_FRZ_LAUNCH_(M_, H2_, L_)                                                              \
-  hipLaunchKernelGGL((bn_bwd_frozen_kernel<M_, H2_, L_>), dim3(grid2), dim3(256), 0,            \
-                     (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act,              \
-                     (const bf16_t*)y, coef, (bf16_t*)dy, (const bf16_t*)y2, coef2,             \
-                     (bf16_t*)dy2, sums, sums2, mask_coef, (long)N * H * W, per, H, W, P, C)
-#define BN_FRZ_LAUNCH(M_, H2_)                                   \
-  do {                                                           \
-    if (g_bn_nt) BN_FRZ_LAUNCH_(M_, H2_, true);                  \
-    else BN_FRZ_LAUNCH_(M_, H2_, false);                         \
-  } while (0)
-  if (y2) {
-    if (mode == 1) BN_FRZ_LAUNCH(1, true); else if (mode == 2) BN_FRZ_LAUNCH(2, true); else BN_FRZ_LAUNCH(0, true);
-  } else {
-    if (mode == 1) BN_FRZ_LAUNCH(1, false); else if (mode == 2) BN_FRZ_LAUNCH(2, false); else BN_FRZ_LAUNCH(0, false);
-  }
+  bn_dispatch<true>(mode, y2 != nullptr, [&](auto m, auto h2, auto nt) {
+    hipLaunchKernelGGL((bn_bwd_frozen_kernel<decltype(m)::value, decltype(h2)::value, decltype(nt)::value>),
+                       dim3(grid2), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)act,
+                       (const bf16_t*)y, coef, (bf16_t*)dy, (const bf16_t*)y2, coef2, (bf16_t*)dy2, sums, sums2,
+                       mask_coef, (long)N * H * W, per, H, W, P, C);
+  });
   return iic_launch_status();
 }
 

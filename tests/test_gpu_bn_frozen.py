@@ -91,6 +91,39 @@ def test_bn_bwd_frozen_vs_float64(shape):
   fcases.check_frozen(GPU, shape)
 
 
+@pytest.mark.parametrize("shape", [(5, 49, 49, 1, 64),       # pair loop plus a ragged tail
+                                   (3, 3, 5, 2, 64),         # one advance crosses two image borders
+                                   (11, 7, 7, 1, 512)],      # 4 pixel lanes, a last chunk shorter than that
+                         ids=str)
+def test_bn_bwd_frozen_leaves_the_statistic_cells_of_bn_bwd_reduce(shape):
+  """iic_bn_bwd_frozen and iic_bn_bwd_reduce walk the pixels in the same order, mask and accumulate alike and end in the
+  same block sums (one walk, one mask, one block-sum routine in csrc/bn.hip): on the same inputs the raw accumulator
+  cells of sums and sums2 are equal bit for bit, in every mask mode, with and without the second BatchNorm."""
+  from iic_amd import ops
+  N, H, W, P, C = shape
+  i = cases.inputs(*shape)
+  dout, act, y, y2 = (_pt(i[k], P) for k in ("dout", "act", "y", "y2"))
+  coef, coef2, mcoef = _d(i["coef"]), _d(i["coef2"]), _d(i["mcoef"])
+  dy, dy2 = _sentinel(shape), _sentinel(shape)
+  for mode in cases.MASK_MODES:
+    a, m = (act if mode == "act" else None), (mcoef if mode == "mask_coef" else None)
+    for two in (False, True):
+      cells = {}
+      for entry in ("reduce", "frozen"):
+        s1, s2 = ops.new_stats(C, dev()), (ops.new_stats(C, dev()) if two else None)
+        if entry == "reduce":
+          ok("iic_bn_bwd_reduce", dout, a, y, y2 if two else None, s1, s2, m, N, H, W, P, C)
+        else:
+          ok("iic_bn_bwd_frozen", dout, a, y, coef, dy, y2 if two else None, coef2 if two else None, dy2 if two else None,
+             s1, s2, m, N, H, W, P, C)
+        assert int(s1.abs().max()) > 0
+        cells[entry] = (s1, s2)
+      what = "%s mask=%s y2=%d" % (shape, mode, two)
+      assert torch.equal(cells["frozen"][0], cells["reduce"][0]), what + ": sums"
+      if two:
+        assert torch.equal(cells["frozen"][1], cells["reduce"][1]), what + ": sums2"
+
+
 def test_bn_bwd_finalize_frozen_vs_float64():
   """iic_bn_bwd_finalize_frozen: dgamma, dbeta within (U32 + 8 EPS64) |ref| (sums with sy within a few ulps of
   mean * s), bcoef = (scale, 0, 0), sums re-zeroed -- a second finalise returns zeros."""
