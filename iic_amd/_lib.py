@@ -171,6 +171,9 @@ _SIGNATURES = {
   "iic_kmeans_assign": (c_int, [_P, c_long, _P, c_long, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
   "iic_kmeans_update": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_int, _P, _P, _P]),
   "iic_kmeans_seed_potential": (c_int, [_P, c_long, c_long, c_int, _P, c_int, _P, c_int, _P, _P, _P]),
+  "iic_triplets_supported": (c_int, [c_long, c_int]),
+  "iic_triplets_workspace_bytes": (c_long, [c_long, c_int]),
+  "iic_triplets_loss": (c_int, [_P, _P, _P, c_long, c_long, c_int, _P, _P, _P, _P, _P, _P]),
   "iic_probe_tr16": (c_int, [_P, _P]),
 }
 

@@ -902,6 +902,35 @@ int iic_kmeans_update(float* C, const float* sums, const long long* counts, long
 int iic_kmeans_seed_potential(const float* X, long ldx, long n, int d, const long long* cand, int ncand, float* mind,
                               int write, double* pot, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Triplets baseline loss and its gradients (csrc/triplets.hip) -- replaces
+ *   code/utils/cluster/baselines/triplets.py:231-238  (triplets_loss: log_softmax, two softmax, two kl_div with
+ *                                                      reduction "elementwise_mean", and their backward nodes)
+ * a (orig), b (pos), c (neg): fp32 logits [N][k], rows at stride ld >= k floats (one ld for all three).  With
+ * lo = a - lse(a), lp = b - lse(b), lq = c - lse(c), p = exp(lp), q = exp(lq), tp_n = sum_j p (lp - lo),
+ * tq_n = sum_j q (lq - lo):
+ *   loss = sum_n (tp_n - tq_n) / (N k)       d_a = (q - p) / (N k)
+ *   d_b  = p ((lp - lo) - tp_n) / (N k)      d_c = -q ((lq - lo) - tq_n) / (N k)
+ * Row arithmetic is float64, every output is rounded to fp32 once.  The log-space form is the specification: log p is
+ * b - lse(b), never log(exp(..)).  torch's own gradient of the target is 0 * (-inf) = NaN once a softmax entry
+ * underflows; this kernel keeps the finite limit (such an entry contributes 0), so its d_b and d_c stay finite at
+ * logit spreads where torch's are NaN.  Both KL terms are computed by one routine: with b and c bit-identical,
+ * loss == 0, d_a == 0 and d_b == -d_c exactly.  No float atomics: one float64 partial per workgroup, added in index
+ * order by a second launch -- two calls give the same bits.
+ * Non-finite logits: the loss is non-finite exactly when torch's is (b_j = -inf alone contributes 0, as xlogy(0, 0)
+ * does); every gradient of a row with a non-finite logit in any of the three inputs is NaN, other rows are untouched.
+ * Served: 1 <= k <= 1024, N >= 1, N k < 2^31.
+ * ------------------------------------------------------------------------------- */
+/* 1 when (N, k) is served, else 0.  Host only. */
+int iic_triplets_supported(long N, int k);
+/* bytes of the workspace `ws` of iic_triplets_loss for (N, k); 0 when unsupported.  Host only. */
+long iic_triplets_workspace_bytes(long N, int k);
+/* loss: fp32 [1].  d_a, d_b, d_c: fp32 [N][k] contiguous.  d_b and d_c may both be NULL (the targets are constants:
+ * skipped), d_a may be NULL together with them (loss only); any other combination, a null input, loss or ws, or
+ * ld < k: IIC_ERR_ARG.  A shape outside the served range: IIC_ERR_UNSUPPORTED.  Either way before any launch. */
+int iic_triplets_loss(const float* a, const float* b, const float* c, long ld, long N, int k, float* loss, float* d_a,
+                      float* d_b, float* d_c, void* ws, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
