@@ -171,6 +171,10 @@ _SIGNATURES = {
   "iic_kmeans_assign": (c_int, [_P, c_long, _P, c_long, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
   "iic_kmeans_update": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_int, _P, _P, _P]),
   "iic_kmeans_seed_potential": (c_int, [_P, c_long, c_long, c_int, _P, c_int, _P, c_int, _P, _P, _P]),
+  "iic_seg_kmeans_label_acc": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+  "iic_seg_kmeans_label_lds_floats": (c_long, [c_int, c_int, c_int, c_int]),
+  "iic_seg_feat_sample": (c_int, [_P, c_int, _P, c_long, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_kmeans_minibatch_update": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, _P, _P, _P]),
   "iic_triplets_supported": (c_int, [c_long, c_int]),
   "iic_triplets_workspace_bytes": (c_long, [c_long, c_int]),
   "iic_triplets_loss": (c_int, [_P, _P, _P, c_long, c_long, c_int, _P, _P, _P, _P, _P, _P]),

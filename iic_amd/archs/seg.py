@@ -214,3 +214,86 @@ class SegmentationNet10aTwoHead(_ApplyCounter, nn.Module):
   @ops.auto_branch
   def _label_maps(self, x, head="B"):
     return (self.head_A if head == "A" else self.head_B).label_maps(self.trunk(x))
+
+
+# ---- the baselines' feature net (code/archs/segmentation/baselines/net10a_isola.py:73-101, net10a_doersch.py:66-96) -----------
+__all__ += ["SegmentationNet10aFeatures", "load_trunk_state_dict", "trunk_pt", "upsampled_features"]
+
+
+def upsampled_features(pt, S):
+  """fp32 [N, C, S, S]: F.interpolate(trunk output, size=S, mode="bilinear") (net10a_isola.py:92) from the PT feature
+  tensor -- interior gather, then iic_bilinear_fwd over all C channels.  For small inputs and tests: the evaluation
+  twins (iic_amd/seg_kmeans.py) never build this tensor."""
+  P = SegmentationNet10aTrunk.P
+  N, Hp, Wp, C = pt.shape
+  Hl, Wl = Hp - 2 * P, Wp - 2 * P
+  L, s = lib(), stream_ptr()
+  Fm = torch.empty((N * Hl * Wl, C), dtype=F32, device=pt.device)
+  if pt.dtype == F32:
+    check(L.iic_f32_window_gather(ptr(pt), ptr(Fm), N, Hl, Wl, Hp, Wp, P, C, s), "iic_f32_window_gather")
+  else:
+    check(L.iic_seg_window_gather(ptr(pt), ptr(Fm), N, Hl, Wl, Hp, Wp, P, C, s), "iic_seg_window_gather")
+  out = torch.empty((N, C, S, S), dtype=F32, device=pt.device)
+  check(L.iic_bilinear_fwd(ptr(Fm), ptr(out), N, Hl, Wl, C, S, s), "iic_bilinear_fwd")
+  return out
+
+
+@ops.auto_branch
+def _trunk_pt(core, x):
+  return (core.features if isinstance(core, SegmentationNet10aFeatures) else core.trunk)(x)
+
+
+def trunk_pt(net, x):
+  """The PT feature tensor [N, Hf + 2P, Wf + 2P, 512] of a SegmentationNet10aFeatures, SegmentationNet10a or
+  SegmentationNet10aTwoHead (DataParallel wrappers are unwrapped).  Inference only."""
+  assert not torch.is_grad_enabled(), "trunk_pt is inference only: call it under torch.no_grad()"
+  core = getattr(net, "module", net)
+  if not isinstance(core, (SegmentationNet10aFeatures, SegmentationNet10a, SegmentationNet10aTwoHead)):
+    raise ValueError("seg k-means (HIP): net must be a SegmentationNet10aFeatures, SegmentationNet10a or "
+                     "SegmentationNet10aTwoHead, got %s" % type(core).__name__)
+  return _trunk_pt(core, x)
+
+
+class SegmentationNet10aFeatures(_ApplyCounter, nn.Module):
+  """The part of SegmentationNet10aIsola / SegmentationNet10aDoersch the k-means evaluation uses: ``features`` (the
+  10a trunk, under the reference's attribute name) and ``forward(x, penultimate=True)``.  The baselines' training heads
+  (isola_head, doersch_head) are not built."""
+  cfg = SegmentationNet10a.cfg
+
+  def __init__(self, config):
+    super(SegmentationNet10aFeatures, self).__init__()
+    self.batchnorm_track = config.batchnorm_track
+    self.input_sz = config.input_sz
+    self.features_sz = SegmentationNet10a.cfg[-1][0]
+    self.features = SegmentationNet10aTrunk(config, cfg=SegmentationNet10a.cfg)
+    _initialize_weights_vgg(self)
+
+  def forward(self, x, centre=None, other=None, penultimate=False):
+    if not penultimate:
+      raise NotImplementedError("SegmentationNet10aFeatures (HIP): the Isola / Doersch baseline heads are not built -- "
+                                "only forward(x, penultimate=True) is served")
+    assert not torch.is_grad_enabled(), "penultimate features are inference only: call under torch.no_grad()"
+    return upsampled_features(_trunk_pt(self, x), self.input_sz)
+
+
+def load_trunk_state_dict(net, state_dict):
+  """Load the trunk weights of an Isola, Doersch or IIC checkpoint into a SegmentationNet10aFeatures: ``features.*`` or
+  ``trunk.*`` keys are read (a DataParallel ``module.`` prefix is dropped), ``isola_head.*``, ``doersch_head.*`` and
+  ``head*`` keys are ignored, anything else raises ValueError.  The trunk must come out complete (strict)."""
+  core = getattr(net, "module", net)
+  if not isinstance(core, SegmentationNet10aFeatures):
+    raise ValueError("load_trunk_state_dict: net must be a SegmentationNet10aFeatures, got %s" % type(core).__name__)
+  trunk = {}
+  for key, val in state_dict.items():
+    name = key[len("module."):] if key.startswith("module.") else key
+    if name.startswith("features."):
+      trunk[name[len("features."):]] = val
+    elif name.startswith("trunk."):
+      trunk[name[len("trunk."):]] = val
+    elif name.startswith(("isola_head.", "doersch_head.", "head")):
+      continue
+    else:
+      raise ValueError("load_trunk_state_dict: unexpected key %r (expected features.*, trunk.*, isola_head.*, "
+                       "doersch_head.* or head*)" % key)
+  core.features.load_state_dict(trunk, strict=True)
+  return core

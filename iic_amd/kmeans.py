@@ -11,7 +11,11 @@ label changes, a final assignment so that ``labels_`` match ``cluster_centers_``
 empty clusters relocated to the points farthest from their centre.  Distances are fp32 in the score form
 ||c||^2 - 2 x.c (exact-fp32 MFMA dot products); every sum has a fixed order, so two fits give the same bits.
 
-``install()`` does not rebind anything to this module; a script opts in -- INTEGRATION.md section 5g.
+``MiniBatchKMeans`` is scikit-learn's mini-batch algorithm on the same assignment kernel, with the centre update, the
+reassignment schedule and the early-stopping bookkeeping of csrc/seg_kmeans.hip; the reference fits it on sampled pixel
+features (code/utils/segmentation/baselines/kmeans_segmentation_eval.py:104; iic_amd/seg_kmeans.py).
+
+``install()`` does not rebind anything to this module; a script opts in -- INTEGRATION.md sections 5g and 5i.
 """
 import math
 
@@ -21,11 +25,12 @@ import torch
 from . import eval_metrics
 from ._lib import check, lib, ptr, stream_ptr
 
-__all__ = ["KMeans", "lloyd_step", "seed_potentials", "supported", "workspace_bytes", "get_data_kmeans_on_features",
-           "kmeans_eval"]
+__all__ = ["KMeans", "MiniBatchKMeans", "lloyd_step", "seed_potentials", "supported", "workspace_bytes",
+           "get_data_kmeans_on_features", "kmeans_eval"]
 F32 = torch.float32
 MAX_K, MAX_D = 256, 32768
 STATE_BYTES = 64
+MB_STATE_BYTES = 128      # csrc/seg_kmeans.hip mb_state: 10 int32, then 8 float64 from byte 40
 
 
 def supported(n, d, k):
@@ -272,6 +277,241 @@ class KMeans(object):
 
   def fit_predict(self, X):
     return self.fit(X).labels_
+
+
+class MiniBatchKMeans(object):
+  """scikit-learn's ``MiniBatchKMeans`` for fp32 features resident on the device.  The defaults are those of the
+  scikit-learn era the reference's bare ``MiniBatchKMeans(n_clusters=gt_k)`` implies (batch_size=100, n_init=3,
+  max_iter=100, max_no_improvement=10, reassignment_ratio=0.01, tol=0.0) -- the choice ``KMeans`` made with n_init=10.
+
+  The algorithm is sklearn/cluster/_kmeans.py's, step for step: a validation subset of ``init_size`` random rows,
+  ``n_init`` initialisations (k-means++ on a fresh random subset each) of which the one with the lowest validation
+  inertia is kept, ``n_steps = max_iter * n // batch_size`` steps on ``randint(0, n, batch_size)`` mini-batches drawn
+  from a host ``RandomState``, the reassignment schedule of ``_random_reassign``, the early stopping of
+  ``_mini_batch_convergence``, a final full assignment for ``labels_`` and ``inertia_``.  A step is a gather of the
+  batch rows into a reused [batch, d] buffer, iic_kmeans_assign and iic_kmeans_minibatch_update; ``check_every`` steps
+  are enqueued between two reads of the 128-byte state block, and the latch on the device makes the result identical to
+  checking after every step (the host rewinds its RandomState to the paused step before it draws the reassignment).  The
+  rare reassignment itself is a few torch ops on the host's side, as ``KMeans`` relocates empty clusters.
+
+  The same caveat as ``KMeans``: the random stream of scikit-learn cannot be replayed -- its k-means++ distances are
+  float64 (see ``kmeans_plusplus``).  ``batches``: an optional sequence of index arrays that replaces the random
+  mini-batches (one step each).  After ``fit``: ``cluster_centers_``, ``labels_``, ``inertia_``, ``n_steps_``,
+  ``n_iter_``, ``counts_`` (float64 [k] on the device), ``n_pauses_`` (steps that waited for a reassignment)."""
+
+  def __init__(self, n_clusters, batch_size=100, max_iter=100, n_init=3, init_size=None, max_no_improvement=10,
+               reassignment_ratio=0.01, tol=0.0, init="k-means++", seed=0, check_every=8):
+    if isinstance(init, str):
+      if init != "k-means++":
+        raise ValueError("kmeans (HIP): init must be 'k-means++' or a [k, d] array, got %r" % init)
+    else:
+      n_init = 1
+    if n_clusters < 1 or batch_size < 1 or n_init < 1 or max_iter < 1 or check_every < 1 or tol < 0:
+      raise ValueError("kmeans (HIP): n_clusters, batch_size, n_init, max_iter, check_every >= 1 and tol >= 0 required")
+    if reassignment_ratio < 0:
+      raise ValueError("reassignment_ratio should be >= 0, got %r instead." % reassignment_ratio)
+    self.n_clusters, self.batch_size, self.max_iter, self.n_init = int(n_clusters), int(batch_size), int(max_iter), int(n_init)
+    self.init_size, self.max_no_improvement = init_size, max_no_improvement
+    self.reassignment_ratio, self.tol = float(reassignment_ratio), float(tol)
+    self.init, self.seed, self.check_every = init, seed, int(check_every)
+    self._choice = None      # tests inject the reassignment picks: callable(n_rows, size) -> indices
+    self._bufs = {}
+
+  # ---- pieces -----------------------------------------------------------------------------------------------------------
+  def _init_size_for(self, n, batch):
+    k = self.n_clusters
+    size = self.init_size
+    if size is None:
+      size = 3 * batch
+      if size < k:
+        size = 3 * k
+    elif size < k:
+      size = 3 * k
+    return min(int(size), n)
+
+  def _init_centroids(self, X, rng, init_size):
+    """_BaseKMeans._init_centroids: a random subset of init_size rows (drawn even for an array init), then k-means++."""
+    n, k = X.shape[0], self.n_clusters
+    Xi = X
+    if init_size is not None and init_size < n:
+      Xi = X[torch.from_numpy(rng.randint(0, n, init_size)).to(X.device)]
+    if isinstance(self.init, str):
+      return Xi[kmeans_plusplus(Xi, k, rng)].contiguous()
+    return torch.as_tensor(self.init).to(device=X.device, dtype=F32).contiguous().clone()
+
+  def _buf(self, Xb):
+    key = (Xb.shape[0], Xb.shape[1], Xb.device)
+    if key not in self._bufs:
+      self._bufs[key] = _Buffers(Xb, self.n_clusters)
+    return self._bufs[key]
+
+  def _new_state(self, dev, norm, alpha, tol, max_no_improvement):
+    host = torch.zeros((MB_STATE_BYTES,), dtype=torch.uint8)
+    ints, dbl = host[:40].view(torch.int32), host[40:104].view(torch.float64)
+    ints[8] = 10 * self.n_clusters
+    ints[9] = -1 if max_no_improvement is None else int(max_no_improvement)
+    dbl[4], dbl[5], dbl[6], dbl[7] = tol, alpha, self.reassignment_ratio, norm
+    return host.to(dev)
+
+  @staticmethod
+  def _read(state):
+    host = state.cpu()      # the one transfer of a chunk
+    ints, dbl = host[:40].view(torch.int32), host[40:104].view(torch.float64)
+    return dict(step=int(ints[0]), converged=int(ints[1]), pause=int(ints[2]), n_since=int(ints[4]),
+                no_improvement=int(ints[5]), inertia=float(dbl[0]), ewa=float(dbl[1]) if int(ints[6]) else None,
+                ewa_min=float(dbl[2]) if int(ints[7]) else None, shift=float(dbl[3]))
+
+  def _step(self, Xb, C, Cold, w, buf, state, resume=0):
+    if not resume:
+      _assign(Xb, C, buf, state=state)
+    check(lib().iic_kmeans_minibatch_update(ptr(C), ptr(Cold), ptr(buf.sums), ptr(buf.counts), ptr(w), buf.n, buf.d,
+                                            buf.k, int(resume), ptr(buf.ws), ptr(state), stream_ptr()),
+          "iic_kmeans_minibatch_update")
+
+  def _reassign(self, Xs, C, w, rng):
+    """The tail of _mini_batch_step (sklearn/cluster/_kmeans.py) on the weights the step left: centres below
+    reassignment_ratio * max w (at most half a batch of them, the lightest) move to random rows of the batch, and take
+    the smallest remaining weight."""
+    wh = w.cpu().numpy().copy()
+    nb = Xs.shape[0]
+    to = wh < self.reassignment_ratio * wh.max()
+    if to.sum() > 0.5 * nb:
+      to[np.argsort(wh)[int(0.5 * nb):]] = False
+    nre = int(to.sum())
+    if nre:
+      picks = self._choice(nb, nre) if self._choice is not None else rng.choice(nb, replace=False, size=nre)
+      dev = C.device
+      C[torch.from_numpy(np.nonzero(to)[0]).to(dev)] = Xs[torch.as_tensor(np.asarray(picks, dtype=np.int64)).to(dev)]
+    wh[to] = np.min(wh[~to])
+    w.copy_(torch.from_numpy(wh))
+
+  def _resume(self, Xs, C, Cold, w, buf, state, rng):
+    self._reassign(Xs, C, w, rng)
+    state[8:12].view(torch.int32).zero_()      # pause
+    self._step(None, C, Cold, w, buf, state, resume=1)
+    return self._read(state)
+
+  # ---- public -----------------------------------------------------------------------------------------------------------
+  def fit(self, X, batches=None):
+    n, d, _ = _check_X(X, need_device=False)
+    k = self.n_clusters
+    if n < k:
+      raise ValueError("n_samples=%d should be >= n_clusters=%d." % (n, k))
+    batch = min(self.batch_size, n)
+    if batches is not None:
+      batches = [np.asarray(b, dtype=np.int64) for b in batches]
+      if not batches or any(b.ndim != 1 or b.shape != batches[0].shape or b.size < 1 for b in batches) or \
+         any(b.min() < 0 or b.max() >= n for b in batches):
+        raise ValueError("kmeans (HIP): batches must be equally long 1-d index arrays into X")
+      batch = int(batches[0].size)
+    _check_shape(n, d, k)
+    _check_shape(batch, d, k)
+    if not isinstance(self.init, str) and tuple(torch.as_tensor(self.init).shape) != (k, d):
+      raise ValueError("kmeans (HIP): init has shape %s, expected %s" % (tuple(torch.as_tensor(self.init).shape), (k, d)))
+    _check_X(X)
+    dev = X.device
+    rng = np.random.RandomState(self.seed)
+    init_size = self._init_size_for(n, batch)
+    tol = 0.0
+    if self.tol > 0 and n > 1:
+      tol = float(X.var(dim=0, unbiased=False).double().mean()) * self.tol
+    # validation set, then the best of n_init initialisations on it
+    Xv = X[torch.from_numpy(rng.randint(0, n, init_size)).to(dev)]
+    vbuf = _Buffers(Xv, k, with_sums=False)
+    cands, inertias = [], []
+    for _ in range(self.n_init):
+      Ci = self._init_centroids(X, rng, init_size)
+      _assign(Xv, Ci, vbuf, with_sums=False, inertia=True)
+      cands.append(Ci)
+      inertias.append(vbuf.inertia.clone())
+    best, best_inertia = 0, None
+    for i, v in enumerate(torch.cat(inertias).cpu().tolist()):
+      if not math.isfinite(v):
+        raise ValueError("non-finite features")
+      if best_inertia is None or v < best_inertia:
+        best, best_inertia = i, v
+    C = cands[best]
+    Cold = torch.empty_like(C)
+    w = torch.zeros((k,), dtype=torch.float64, device=dev)
+    n_steps = (self.max_iter * n) // batch if batches is None else len(batches)
+    state = self._new_state(dev, float(batch), min(batch * 2.0 / (n + 1), 1.0), tol, self.max_no_improvement)
+    Xb = torch.empty((batch, d), dtype=F32, device=dev)
+    buf = self._buf(Xb)
+    buf.labels.fill_(-1)
+    st = dict(step=0, converged=0, pause=0, ewa=None)
+    self.n_pauses_ = 0
+    while st["step"] < n_steps and not st["converged"]:
+      i0 = st["step"]
+      ce = min(self.check_every, n_steps - i0)
+      idxs, rstates = [], []
+      for j in range(ce):
+        if batches is None:
+          idxs.append(rng.randint(0, n, batch))
+          rstates.append(rng.get_state())
+        else:
+          idxs.append(batches[i0 + j])
+      idx_dev = torch.from_numpy(np.stack(idxs).astype(np.int64)).to(dev)
+      for j in range(ce):
+        torch.index_select(X, 0, idx_dev[j], out=Xb)
+        self._step(Xb, C, Cold, w, buf, state)
+      st = self._read(state)
+      if st["pause"]:
+        j = st["step"] - i0      # the steps behind it were latched out: their draws are taken back
+        if batches is None:
+          rng.set_state(rstates[j])
+        self.n_pauses_ += 1
+        st = self._resume(X[idx_dev[j]], C, Cold, w, buf, state, rng)
+    self.cluster_centers_, self.counts_ = C, w
+    self.n_steps_ = st["step"]
+    self.n_iter_ = int(np.ceil((st["step"] * batch) / float(n)))
+    self.ewa_inertia_ = st["ewa"]
+    fbuf = _Buffers(X, k, with_sums=False)
+    _assign(X, C, fbuf, with_sums=False, inertia=True)
+    self.labels_ = fbuf.labels
+    self.inertia_ = float(fbuf.inertia.cpu()[0])
+    if not math.isfinite(self.inertia_):
+      raise ValueError("non-finite features")
+    self._w, self._rng = w, rng
+    return self
+
+  def partial_fit(self, X):
+    """One mini-batch step on the rows of X (the first call initialises the centres on them).  Reads the state block
+    once: a reassignment, when the step asks for one, is completed before the call returns."""
+    n, d, _ = _check_X(X)
+    k = self.n_clusters
+    _check_shape(n, d, k)
+    dev = X.device
+    if not hasattr(self, "_rng"):
+      self._rng = np.random.RandomState(self.seed)
+    if not hasattr(self, "cluster_centers_"):
+      if n < k:
+        raise ValueError("n_samples=%d should be >= n_clusters=%d." % (n, k))
+      if not isinstance(self.init, str) and tuple(torch.as_tensor(self.init).shape) != (k, d):
+        raise ValueError("kmeans (HIP): init has shape %s, expected %s" % (tuple(torch.as_tensor(self.init).shape), (k, d)))
+      self.cluster_centers_ = self._init_centroids(X, self._rng, self._init_size_for(n, min(self.batch_size, n)))
+      self._w = self.counts_ = torch.zeros((k,), dtype=torch.float64, device=dev)
+      self.n_steps_ = 0
+    if not hasattr(self, "_pstate"):
+      # never latches on convergence: tol 0 and no max_no_improvement; n_since carries the reassignment schedule
+      self._pstate = self._new_state(dev, float(n), 1.0, 0.0, None)
+      self._pstate[0:4].view(torch.int32).fill_(int(self.n_steps_))
+      self._pold = torch.empty_like(self.cluster_centers_)
+    C = self.cluster_centers_
+    if d != C.shape[1]:
+      raise ValueError("kmeans (HIP): X has %d features, the centres %d" % (d, C.shape[1]))
+    Xc = X if X.is_contiguous() else X.contiguous()
+    buf = self._buf(Xc)
+    buf.labels.fill_(-1)
+    self._step(Xc, C, self._pold, self._w, buf, self._pstate)
+    st = self._read(self._pstate)
+    if st["pause"]:
+      st = self._resume(Xc, C, self._pold, self._w, buf, self._pstate, self._rng)
+    self.n_steps_ = st["step"]
+    self.batch_inertia_ = st["inertia"]
+    return self
+
+  predict = KMeans.predict
+  fit_predict = KMeans.fit_predict
 
 
 def _features(config, net, dataloader, sobel):

@@ -903,6 +903,55 @@ int iic_kmeans_seed_potential(const float* X, long ldx, long n, int d, const lon
                               int write, double* pot, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Segmentation k-means evaluation (csrc/seg_kmeans.hip) -- replaces, in
+ * code/utils/segmentation/baselines/kmeans_segmentation_eval.py:
+ *   :56, :141    net(imgs, penultimate=True).cpu().numpy(): the fp32 [N][512][S][S] up-sampled trunk features
+ *   :64-66, :143-144  transpose and boolean mask on the host
+ *   :78-91       the sampled feature rows
+ *   :104         MiniBatchKMeans(n_clusters=gt_k).fit on the host
+ *   :148-186     kmeans.predict per batch, flat int32 arrays of the test set, the reorder loop, _acc
+ * ------------------------------------------------------------------------------- */
+/* kmeans_segmentation_eval.py:141-152 and what :162-186 derive from the flat arrays.  dots_nhwc fp32 [N][Hl][Wl][k]: the
+ * products x.c_j at the trunk's resolution; cnorm fp32 [k].  Per output pixel of [N][S][S]: every channel is up-sampled
+ * with the operations and order of iic_bilinear_fwd, score_j = cnorm_j - 2 up_j in fp32, label = arg-min (lowest index
+ * on a tie; a NaN score never beats a number; all NaN: label 0 -- the rule of iic_kmeans_assign).  The label is folded
+ * with targets_u8 / mask_u8 ([N][S][S]; mask nullable) into counts int64 [k k_gt + 1] exactly as
+ * iic_seg_contingency_acc does: accumulated, integer atomics, counts[label k_gt + target] += 1 for selected pixels with
+ * target < k_gt, the number of selected pixels in the last cell.  labels_u8 (nullable, any alignment): the label map.
+ * Served: 1 <= k <= 255, k k_gt <= 16384, any Hl, Wl, S; otherwise IIC_ERR_UNSUPPORTED before a launch.  Source rows
+ * that do not fit the LDS budget are read from global memory: the same bits. */
+int iic_seg_kmeans_label_acc(const float* dots_nhwc, const float* cnorm, const unsigned char* targets_u8,
+                             const unsigned char* mask_u8, int N, int Hl, int Wl, int k, int S, int k_gt,
+                             long long* counts, unsigned char* labels_u8, void* stream);
+/* LDS floats iic_seg_kmeans_label_acc stages its sources in for this geometry; 0: the global-read form; -1: bad
+ * arguments.  Host only. */
+long iic_seg_kmeans_label_lds_floats(int Hl, int Wl, int k, int S);
+/* kmeans_segmentation_eval.py:56-91 for the sampled pixels only.  pt: the PT feature tensor [N][Hp][Wp][C], bf16
+ * (pt_is_f32 == 0) or fp32, interior Hl x Wl at `off`; coords int32 [m][3] = (n, y, x) at resolution S on the device
+ * (clamped into range).  rows fp32 [m][C]: rows[i][c] is the number iic_bilinear_fwd would store at (n, c, y, x) for
+ * the fp32-converted interior.  Any C >= 1; m == 0 is a no-op. */
+int iic_seg_feat_sample(const void* pt, int pt_is_f32, const int* coords, long m, float* rows, int N, int Hl, int Wl,
+                        int Hp, int Wp, int off, int C, int S, void* stream);
+/* The centre update of scikit-learn's dense mini-batch step (sklearn/cluster/_k_means_minibatch.pyx
+ * update_center_dense; _kmeans.py _mini_batch_step, MiniBatchKMeans._mini_batch_convergence, _random_reassign), which
+ * kmeans_segmentation_eval.py:104 runs on the host.  sums / counts / ws: what iic_kmeans_assign produced for the batch
+ * of n rows.  counts_j > 0: c_j <- (c_j w_j + sums_j) / (w_j + counts_j) in float64, w_j += counts_j; otherwise the row
+ * stays.  C_old [k][d] receives the centres before the step; w: float64 [k].
+ * state: 128 bytes on the device {int32 step, converged, pause, changed, n_since, no_improvement, have_ewa, have_min,
+ * reassign_every, max_no_improvement; double inertia, ewa, ewa_min, shift, tol, alpha, ratio, norm; 24 bytes pad}.  The
+ * host zeroes it and writes reassign_every (10 k), max_no_improvement (< 0: none), tol, alpha = min(1, 2 batch /
+ * (n_samples + 1)), ratio and norm (the batch size).  The same block is given to iic_kmeans_assign for its latch.
+ * A step is a reassignment step when a w_j was 0 before it or n_since + n >= reassign_every (n_since then restarts); on
+ * such a step, after the update, any w_j < ratio max w sets `pause` and leaves the bookkeeping undone: the host
+ * reassigns, clears pause and calls again with resume = 1, which updates nothing and completes the step (shift from
+ * C_old, inertia from ws).  Bookkeeping: step += 1; from the second step on the exponentially weighted average of
+ * inertia / norm, its minimum and the no-improvement counter; converged = 2 when tol > 0 and shift <= tol, 1 when the
+ * counter reaches max_no_improvement.  Once converged or pause is set every launch given the state returns at once.
+ * Fixed-order sums, no float atomics. */
+int iic_kmeans_minibatch_update(float* C, float* C_old, const float* sums, const long long* counts, double* w, long n,
+                                int d, int k, int resume, void* ws, void* state, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Triplets baseline loss and its gradients (csrc/triplets.hip) -- replaces
  *   code/utils/cluster/baselines/triplets.py:231-238  (triplets_loss: log_softmax, two softmax, two kl_div with
  *                                                      reduction "elementwise_mean", and their backward nodes)
