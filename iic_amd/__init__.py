@@ -6,7 +6,7 @@ implemented on hand-written HIP kernels behind the C ABI of ``libiic_hip.so``
 (include/iic_hip.h).  ``iic_amd.install.install()`` registers them under the reference's
 module names so its training scripts import them unchanged.
 
-Submodules: losses, seg_losses, transforms, archs, optim, dist, install, geom, ops, branches, pool, augment, seg_augment, seg_ragged, seg_prescale, semisup, _lib.
+Submodules: losses, seg_losses, transforms, archs, optim, dist, install, geom, ops, branches, pool, augment, seg_augment, seg_ragged, seg_prescale, semisup, seg_baselines, _lib.
 """
 import importlib
 

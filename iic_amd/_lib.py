@@ -178,6 +178,16 @@ _SIGNATURES = {
   "iic_triplets_supported": (c_int, [c_long, c_int]),
   "iic_triplets_workspace_bytes": (c_long, [c_long, c_int]),
   "iic_triplets_loss": (c_int, [_P, _P, _P, c_long, c_long, c_int, _P, _P, _P, _P, _P, _P]),
+  "iic_seg_patch_sample_fwd": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+  "iic_seg_patch_sample_bwd": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       _P]),
+  "iic_pair_weight_prep": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+  "iic_pair_linear_fwd_nsplit": (c_int, [c_int, c_int, c_int, c_int]),
+  "iic_pair_linear_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+  "iic_pair_linear_bwd_dx": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+  "iic_pair_linear_wgrad": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+  "iic_isola_loss": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
+  "iic_doersch_loss": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
   "iic_probe_tr16": (c_int, [_P, _P]),
 }
 

@@ -257,7 +257,8 @@ def trunk_pt(net, x):
 class SegmentationNet10aFeatures(_ApplyCounter, nn.Module):
   """The part of SegmentationNet10aIsola / SegmentationNet10aDoersch the k-means evaluation uses: ``features`` (the
   10a trunk, under the reference's attribute name) and ``forward(x, penultimate=True)``.  The baselines' training heads
-  (isola_head, doersch_head) are not built."""
+  (isola_head, doersch_head) are its subclasses in iic_amd/archs/seg_baselines.py; this class keeps raising without
+  ``penultimate=True``."""
   cfg = SegmentationNet10a.cfg
 
   def __init__(self, config):

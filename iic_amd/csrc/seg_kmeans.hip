@@ -26,29 +26,11 @@
 #include "common.h"
 #include "../../include/iic_hip.h"
 #include "kmeans_ws.h"
+#include "seg_bilinear.h"
 
 #define SK_MAXBINS 16384            // as seg_contingency_acc_kernel
 #define SK_LDS_BUDGET (40 * 1024)   // staged sources per workgroup, as seg_label_map_kernel
 #define SK_PX 4
-
-// The interpolated numbers must be the very ones bilinear_fwd_kernel stores: pinned operation by operation as
-// seg_eval.hip pins them (see the note there), not left to -ffp-contract.
-__device__ __forceinline__ void sk_src(int d, float scale, int in, int& i0, int& i1, float& lam) {
-#pragma clang fp contract(off)
-  float s = __builtin_fmaf((float)d + 0.5f, scale, -0.5f);
-  if (s < 0.f) s = 0.f;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  lam = s - (float)i0;
-}
-
-__device__ __forceinline__ float sk_blend(float v00, float v01, float v10, float v11, float lx, float ly) {
-#pragma clang fp contract(off)
-  const float top = __builtin_fmaf(v01, lx, v00 * (1.f - lx));
-  const float bot = __builtin_fmaf(v10, 1.f - lx, v11 * lx);
-  return (1.f - ly) * top + ly * bot;
-}
 
 // p0 / p1: channel 0 of source rows y0 / y1; channel c of column j is at [c * cs + o0[j]] (left) and [c * cs + o1[j]]
 // (right).  score = cnorm - 2 up: the doubling is exact, one rounding in the subtraction.  `s < best` from +inf: a NaN
@@ -202,13 +184,6 @@ static sk_plan sk_plan_make(int Hl, int Wl, int k, int S) {
   if (p.lds_floats > budget) p.lds_floats = 0;
   return p;
 }
-
-template <typename T>
-__device__ __forceinline__ float sk_ld(const T* p);
-template <>
-__device__ __forceinline__ float sk_ld<bf16_t>(const bf16_t* p) { return bf16_to_f32(*p); }
-template <>
-__device__ __forceinline__ float sk_ld<float>(const float* p) { return *p; }
 
 // a wave per sampled pixel (grid-stride), lanes over the channels.  Coordinates are device data: clamped into range.
 template <typename T>

@@ -16,6 +16,9 @@
 // parameter's (c, h, w) order.  One block = 4 waves = a 128 x 128 output tile (2 x 2 MFMA tiles of 32 x 32 per wave), K-tiles
 // of 64 through double-buffered LDS at a 144-byte row pitch.  No float atomics anywhere: the forward's K split writes
 // partial matrices that sup_fold_kernel adds in index order, so two runs give equal bits.
+// The joint Linear of the Isola / Doersch baselines' heads (iic_pair_*, at the end of the file) runs on the same kernels:
+// its K axis covers two PT activations, one after the other, and each column half of its weight is a matrix whose rows
+// are 2 K apart.
 #include "common.h"
 #include "../../include/iic_hip.h"
 
@@ -90,11 +93,14 @@ __device__ __forceinline__ void sup_zero(f32x16 (&acc)[2][2]) {
 }
 
 // out[m][n] = sum_k A[m][k] B[n][k]  (both operands k-contiguous).  blockIdx = (row tile, column tile, K slice).
+// A is two matrices side by side along k: K-tiles 0 .. ka - 1 come from A, tiles ka .. K / 64 - 1 from A2 (its columns
+// from 0) -- the two patch activations of the baselines' joint Linear; ka = K / 64 for a single operand.
 // OUT_BF16 = false: fp32 out + z * M * ldc (+ bias[n] when given) at [m * ldc + n];
 // OUT_BF16 = true:  bf16 RNE into the sup_mat `o` (row m, column n) -- the interior of a PT tensor, border untouched.
 template <bool OUT_BF16>
-__global__ __launch_bounds__(256) void sup_gemm_kernel(sup_mat A, sup_mat B, int K, const float* __restrict__ bias,
-                                                        float* __restrict__ out, long ldc, sup_mat o) {
+__global__ __launch_bounds__(256) void sup_gemm_kernel(sup_mat A, sup_mat A2, int ka, sup_mat B, int K,
+                                                        const float* __restrict__ bias, float* __restrict__ out, long ldc,
+                                                        sup_mat o) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sup_smem[];
   bf16_t* const sA = reinterpret_cast<bf16_t*>(sup_smem);     // [2][TILE_ELEMS]
   bf16_t* const sB = sA + 2 * TILE_ELEMS;                     // [2][TILE_ELEMS]
@@ -106,13 +112,17 @@ __global__ __launch_bounds__(256) void sup_gemm_kernel(sup_mat A, sup_mat B, int
   f32x16 acc[2][2];
   sup_zero(acc);
   u32x4 ra[4], rb[4];
+  auto load_a = [&](int t) {
+    if (t < ka) sup_gload(A, m0, t * BK, ra);
+    else sup_gload(A2, m0, (t - ka) * BK, ra);
+  };
   if (t0 < t1) {
-    sup_gload(A, m0, t0 * BK, ra);
+    load_a(t0);
     sup_gload(B, n0, t0 * BK, rb);
     sup_lstore(sA, ra);
     sup_lstore(sB, rb);
     if (t0 + 1 < t1) {
-      sup_gload(A, m0, (t0 + 1) * BK, ra);
+      load_a(t0 + 1);
       sup_gload(B, n0, (t0 + 1) * BK, rb);
     }
   }
@@ -124,7 +134,7 @@ __global__ __launch_bounds__(256) void sup_gemm_kernel(sup_mat A, sup_mat B, int
       sup_lstore(sB + (cur ^ 1) * TILE_ELEMS, rb);
     }
     if (t + 2 < t1) {
-      sup_gload(A, m0, (t + 2) * BK, ra);
+      load_a(t + 2);
       sup_gload(B, n0, (t + 2) * BK, rb);
     }
     sup_compute(sA + cur * TILE_ELEMS, sB + cur * TILE_ELEMS, wm, wn, acc);
@@ -171,6 +181,7 @@ __global__ __launch_bounds__(256) void sup_fold_kernel(const float* __restrict__
 // parameter's (c, h, w) row and a loader thread reads the 8 channels of one pixel in one 16-byte load.
 // A = dyt [F][Np] (Np = N rounded up to 64, zero padded), K = Np.  B[j][n] = x[n][pixel][channel]: the loader takes two
 // images n, n + 1 per item and writes 8 packed pairs into the [j][n] LDS image (conflict-free: banks 36 pp + np).
+// dW rows are ldw floats apart (ldw = K, or 2 K for one column half of the baselines' joint Linear).
 __device__ __forceinline__ void sup_wg_bload(const bf16_t* __restrict__ x, long ldn, long poff, int N, int k0,
                                              u32x4 (&r)[2][2]) {
 #pragma unroll
@@ -200,7 +211,7 @@ __device__ __forceinline__ void sup_wg_bstore(bf16_t* s, const u32x4 (&r)[2][2])
 }
 
 __global__ __launch_bounds__(256) void sup_wgrad_kernel(sup_mat A, const bf16_t* __restrict__ x, long ldn, int N, int H,
-                                                         int W, int C, float* __restrict__ dW) {
+                                                         int W, int C, float* __restrict__ dW, long ldw) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sup_smem[];
   bf16_t* const sA = reinterpret_cast<bf16_t*>(sup_smem);
   bf16_t* const sB = sA + 2 * TILE_ELEMS;
@@ -239,7 +250,6 @@ __global__ __launch_bounds__(256) void sup_wgrad_kernel(sup_mat A, const bf16_t*
     sup_compute(sA + cur * TILE_ELEMS, sB + cur * TILE_ELEMS, wm, wn, acc);
   }
   const int F = A.rows;
-  const long K = (long)HW * C;
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -250,21 +260,20 @@ __global__ __launch_bounds__(256) void sup_wgrad_kernel(sup_mat A, const bf16_t*
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = f0 + wm * 64 + a * 32 + mfma32_row(r, lane);
-        if (row < F) dW[(long)row * K + (long)c * HW + p] = acc[a][b][r];
+        if (row < F) dW[(long)row * ldw + (long)c * HW + p] = acc[a][b][r];
       }
     }
 }
 
 // wb[f][p C + c] = bf16(w[f][c HW + p]): per row f the [C][HW] slab transposed to [HW][C], 64 channels x 64 pixels
 // through LDS -- reads run along p, writes are 128-byte runs of packed channel pairs.  blockIdx = (pixel tile, channel
-// tile, f).
+// tile, f).  Rows of w and wb are ld floats / bf16 apart (ld = K, or 2 K for one column half of the joint Linear).
 __global__ __launch_bounds__(256) void sup_weight_prep_fwd_kernel(const float* __restrict__ w, bf16_t* __restrict__ wb,
-                                                                   int C, int HW) {
+                                                                   int C, int HW, long ld) {
   __shared__ float tile[64][65];
-  const long K = (long)C * HW;
   const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-  const float* src = w + (long)blockIdx.z * K;
-  uint32_t* dst = reinterpret_cast<uint32_t*>(wb + (long)blockIdx.z * K);
+  const float* src = w + (long)blockIdx.z * ld;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(wb + (long)blockIdx.z * ld);
   for (int e = threadIdx.x; e < 64 * 64; e += 256) {
     const int cl = e >> 6, pl = e & 63;
     tile[cl][pl] = (p0 + pl < HW) ? src[(long)(c0 + cl) * HW + p0 + pl] : 0.f;
@@ -275,16 +284,17 @@ __global__ __launch_bounds__(256) void sup_weight_prep_fwd_kernel(const float* _
     if (p0 + pl < HW) dst[((long)(p0 + pl) * C + c0) / 2 + c2] = pack_bf16x2(tile[2 * c2][pl], tile[2 * c2 + 1][pl]);
   }
 }
-// wt[p C + c][f] = bf16(w[f][c HW + p]): 64 f x 64 source columns through LDS, 128-byte runs on both sides
+// wt[p C + c][f] = bf16(w[f][c HW + p]): 64 f x 64 source columns through LDS, 128-byte runs on both sides; rows of
+// w are ld floats apart
 __global__ __launch_bounds__(256) void sup_weight_prep_bwd_kernel(const float* __restrict__ w, bf16_t* __restrict__ wt,
-                                                                   int F, int C, int HW) {
+                                                                   int F, int C, int HW, long ld) {
   __shared__ float tile[64][65];
   const long K = (long)C * HW;
   const int f0 = blockIdx.y * 64;
   const long s0 = (long)blockIdx.x * 64;
   for (int e = threadIdx.x; e < 64 * 64; e += 256) {
     const int fl = e >> 6, sl = e & 63;
-    tile[fl][sl] = (f0 + fl < F && s0 + sl < K) ? w[(long)(f0 + fl) * K + s0 + sl] : 0.f;
+    tile[fl][sl] = (f0 + fl < F && s0 + sl < K) ? w[(long)(f0 + fl) * ld + s0 + sl] : 0.f;
   }
   __syncthreads();
   for (int e = threadIdx.x; e < 64 * 64; e += 256) {
@@ -515,10 +525,10 @@ int iic_sup_weight_prep(const float* w, void* wb, void* wt, int F, int C, int H,
   const long K = (long)C * HW;
   if (F > 65535 || C / 64 > 65535) return IIC_ERR_UNSUPPORTED;
   int rc = iic_launch_lds<sup_weight_prep_fwd_kernel>(dim3((HW + 63) / 64, C / 64, F), dim3(256), 0, (hipStream_t)stream, w,
-                                                      (bf16_t*)wb, C, HW);
+                                                      (bf16_t*)wb, C, HW, K);
   if (rc) return rc;
   rc = iic_launch_lds<sup_weight_prep_bwd_kernel>(dim3((unsigned)((K + 63) / 64), (F + 63) / 64), dim3(256), 0,
-                                                  (hipStream_t)stream, w, (bf16_t*)wt, F, C, HW);
+                                                  (hipStream_t)stream, w, (bf16_t*)wt, F, C, HW, K);
   if (rc) return rc;
   return iic_launch_status();
 }
@@ -537,7 +547,7 @@ int iic_sup_linear_fwd(const void* x_pt, const void* wb, const float* bias, floa
   if (S > 1 && !ws) return IIC_ERR_ARG;
   const sup_mat A = sup_pt(x_pt, N, H, W, C), B = sup_flat(wb, F, K), none = sup_flat(nullptr, 0, 1);
   dim3 grid((N + TM - 1) / TM, (F + TN - 1) / TN, S);
-  int rc = iic_launch_lds<sup_gemm_kernel<false>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, B, K,
+  int rc = iic_launch_lds<sup_gemm_kernel<false>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, A, K / BK, B, K,
                                                   S > 1 ? (const float*)nullptr : bias, S > 1 ? ws : y, (long)F, none);
   if (rc) return rc;
   if (S > 1) {
@@ -564,7 +574,7 @@ int iic_sup_linear_bwd_dx(const void* dyb, const void* wt, void* dx_pt, int N, i
   const int K = H * W * C;
   const sup_mat A = sup_flat(dyb, N, F), B = sup_flat(wt, K, F), o = sup_pt(dx_pt, N, H, W, C);
   dim3 grid((N + TM - 1) / TM, (K + TN - 1) / TN, 1);
-  int rc = iic_launch_lds<sup_gemm_kernel<true>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, B, F,
+  int rc = iic_launch_lds<sup_gemm_kernel<true>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, A, F / BK, B, F,
                                                  (const float*)nullptr, (float*)nullptr, 0L, o);
   if (rc) return rc;
   return iic_launch_status();
@@ -578,7 +588,7 @@ int iic_sup_linear_wgrad(const void* dyt, const void* x_pt, float* dW, int N, in
   const sup_mat A = sup_flat(dyt, F, Np);
   dim3 grid((F + TM - 1) / TM, C / 8, (HW + 15) / 16);
   int rc = iic_launch_lds<sup_wgrad_kernel>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, (const bf16_t*)x_pt,
-                                            (long)(H + 2) * (W + 2) * C, N, H, W, C, dW);
+                                            (long)(H + 2) * (W + 2) * C, N, H, W, C, dW, (long)HW * C);
   if (rc) return rc;
   return iic_launch_status();
 }
@@ -623,6 +633,107 @@ int iic_sup_tencrop_acc(const float* logits, const long long* targets, long long
   int rc = iic_launch_lds<sup_tencrop_acc_kernel>(dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, logits, targets,
                                                   (unsigned long long*)counts, B, k, crops);
   if (rc) return rc;
+  return iic_launch_status();
+}
+
+// ---- joint Linear of the Isola / Doersch heads over the two patch activations (iic_hip.h: iic_pair_*) ----------------
+// y[n][f] = sum_q sum_k a_q[n][k] w[f][q K + k] + b[f], K = C p p: the same three products with the K axis of the
+// forward running over both activations (sup_gemm_kernel's A, A2) and the two column halves of w handled one after the
+// other everywhere else.  The same kernels as iic_sup_*: a half of w is a matrix with row stride 2 K.
+
+static bool pair_shape_ok(int N, int F, int C, int p) {
+  return p >= 1 && (p & 1) == 1 && sup_shape_ok(N, F, C, p, p) && 2L * p * p * C < (1L << 30);
+}
+// K slices of the pair forward.  N is a fraction of one 128-row tile and every weight element is read once, so the
+// product is bound by streaming w: the slices are what fills the chip.  Two workgroups per CU (their LDS: 72 KB each)
+// over the row x column tiles, at least 8 K-tiles per slice, at most 64 slices -- at the Potsdam shape (N = 75,
+// F = 1024, C = 1024, p = 11: 8 column tiles, 3872 K-tiles) 64 slices of 60 or 61 K-tiles, whose partial matrices
+// (64 x 75 x 1024 fp32, 20 MB) are 4 % of the 507 MB of weights read.
+static int pair_nsplit(int N, int F, int K2) {
+  const long tiles = (long)((N + TM - 1) / TM) * ((F + TN - 1) / TN);
+  const int ktiles = K2 / BK;
+  long s = (2L * iic_num_cus() + tiles - 1) / tiles;
+  if (s > ktiles / 8) s = ktiles / 8;
+  if (s > 64) s = 64;
+  return s < 1 ? 1 : (int)s;
+}
+
+int iic_pair_weight_prep(const float* w, void* wb, void* wt, int F, int C, int p, void* stream) {
+  if (!w || !wb || !wt) return IIC_ERR_ARG;
+  if (!pair_shape_ok(1, F, C, p)) return IIC_ERR_UNSUPPORTED;
+  const int HW = p * p;
+  const long K = (long)C * HW;
+  if (F > 65535 || C / 64 > 65535) return IIC_ERR_UNSUPPORTED;
+  for (int q = 0; q < 2; ++q) {
+    int rc = iic_launch_lds<sup_weight_prep_fwd_kernel>(dim3((HW + 63) / 64, C / 64, F), dim3(256), 0, (hipStream_t)stream,
+                                                        w + q * K, (bf16_t*)wb + q * K, C, HW, 2 * K);
+    if (rc) return rc;
+    rc = iic_launch_lds<sup_weight_prep_bwd_kernel>(dim3((unsigned)((K + 63) / 64), (F + 63) / 64), dim3(256), 0,
+                                                    (hipStream_t)stream, w + q * K, (bf16_t*)wt + q * K * F, F, C, HW,
+                                                    2 * K);
+    if (rc) return rc;
+  }
+  return iic_launch_status();
+}
+
+int iic_pair_linear_fwd_nsplit(int N, int F, int C, int p) {
+  if (!pair_shape_ok(N, F, C, p)) return 0;
+  return pair_nsplit(N, F, 2 * p * p * C);
+}
+
+int iic_pair_linear_fwd(const void* a0_pt, const void* a1_pt, const void* wb, const float* bias, float* y, float* ws, int N,
+                        int F, int C, int p, void* stream) {
+  if (!a0_pt || !a1_pt || !wb || !y) return IIC_ERR_ARG;
+  if (!pair_shape_ok(N, F, C, p)) return IIC_ERR_UNSUPPORTED;
+  const int K = p * p * C;
+  const int S = pair_nsplit(N, F, 2 * K);
+  if (S > 1 && !ws) return IIC_ERR_ARG;
+  const sup_mat A0 = sup_pt(a0_pt, N, p, p, C), A1 = sup_pt(a1_pt, N, p, p, C), B = sup_flat(wb, F, 2 * K),
+                none = sup_flat(nullptr, 0, 1);
+  dim3 grid((N + TM - 1) / TM, (F + TN - 1) / TN, S);
+  int rc = iic_launch_lds<sup_gemm_kernel<false>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A0, A1, K / BK, B, 2 * K,
+                                                  S > 1 ? (const float*)nullptr : bias, S > 1 ? ws : y, (long)F, none);
+  if (rc) return rc;
+  if (S > 1) {
+    const long mn = (long)N * F;
+    rc = iic_launch_lds<sup_fold_kernel>(dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                         (const float*)ws, S, bias, y, mn, F);
+    if (rc) return rc;
+  }
+  return iic_launch_status();
+}
+
+int iic_pair_linear_bwd_dx(const void* dyb, const void* wt, void* dx0_pt, void* dx1_pt, int N, int F, int C, int p,
+                           void* stream) {
+  if (!dyb || !wt || !dx0_pt || !dx1_pt) return IIC_ERR_ARG;
+  if (!pair_shape_ok(N, F, C, p)) return IIC_ERR_UNSUPPORTED;
+  const int K = p * p * C;
+  const sup_mat A = sup_flat(dyb, N, F);
+  dim3 grid((N + TM - 1) / TM, (K + TN - 1) / TN, 1);
+  for (int q = 0; q < 2; ++q) {
+    const sup_mat B = sup_flat((const bf16_t*)wt + (long)q * K * F, K, F), o = sup_pt(q ? dx1_pt : dx0_pt, N, p, p, C);
+    int rc = iic_launch_lds<sup_gemm_kernel<true>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, A, F / BK, B, F,
+                                                   (const float*)nullptr, (float*)nullptr, 0L, o);
+    if (rc) return rc;
+  }
+  return iic_launch_status();
+}
+
+int iic_pair_linear_wgrad(const void* dyt, const void* a0_pt, const void* a1_pt, float* dW, int N, int F, int C, int p,
+                          void* stream) {
+  if (!dyt || !a0_pt || !a1_pt || !dW) return IIC_ERR_ARG;
+  if (!pair_shape_ok(N, F, C, p)) return IIC_ERR_UNSUPPORTED;
+  const int Np = (N + 63) / 64 * 64, HW = p * p;
+  const long K = (long)HW * C;
+  if ((HW + 15) / 16 > 65535 || C / 8 > 65535) return IIC_ERR_UNSUPPORTED;
+  const sup_mat A = sup_flat(dyt, F, Np);
+  dim3 grid((F + TM - 1) / TM, C / 8, (HW + 15) / 16);
+  for (int q = 0; q < 2; ++q) {
+    int rc = iic_launch_lds<sup_wgrad_kernel>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A,
+                                              (const bf16_t*)(q ? a1_pt : a0_pt), (long)(p + 2) * (p + 2) * C, N, p, p, C,
+                                              dW + q * K, 2 * K);
+    if (rc) return rc;
+  }
   return iic_launch_status();
 }
 

@@ -980,6 +980,80 @@ long iic_triplets_workspace_bytes(long N, int k);
 int iic_triplets_loss(const float* a, const float* b, const float* c, long ld, long N, int k, float* loss, float* d_a,
                       float* d_b, float* d_c, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Isola and Doersch segmentation baselines: patch sampler (csrc/seg_patches.hip), joint Linear (csrc/sup_head.hip)
+ * and losses (csrc/seg_baseline_loss.hip).
+ * coords: int32 [8] on the device, {cy, cx, oy, ox, label, 0, 0, 0}: the centre patch's centre, the other patch's
+ * centre (row, column at resolution S) and the step's label (Isola: adjacent != 0; Doersch: position 0..8).  On the
+ * device so that a captured step can be replayed with new patches; the kernels clamp what they read, the host wrappers
+ * validate before they upload.
+ * ------------------------------------------------------------------------------- */
+/* code/archs/segmentation/baselines/net10a_isola.py:92-96, net10a_doersch.py:85-89 and
+ * code/utils/segmentation/baselines/general.py:4-18 (F.interpolate of all C channels to S x S, then two p x p slices)
+ * for the 2 p p sampled pixels per image only.  pt: the trunk's PT feature tensor [N][Hp][Wp][C], bf16 (pt_is_f32 == 0) or
+ * fp32, interior Hl x Wl at `off`.  p odd, d = p / 2; centres are clamped into [d, S - 1 - d].
+ * patches: one PT tensor [2 N][p + 2][p + 2][C] of the source's dtype, border 1: images 0 .. N - 1 hold the centre patch,
+ * N .. 2 N - 1 the other patch.  Interior (i, j, c) of image q N + n is the number iic_bilinear_fwd stores at
+ * (n, c, y_q - d + i, x_q - d + j) for the fp32-converted interior (align_corners=False, as F.interpolate), rounded to
+ * nearest even once when the output is bf16.  The border is written as zeros.
+ * Served: C even, p odd, p <= min(S, 127); otherwise IIC_ERR_UNSUPPORTED before a launch. */
+int iic_seg_patch_sample_fwd(const void* pt, int pt_is_f32, const int* coords, void* patches, int N, int Hl, int Wl, int Hp,
+                             int Wp, int off, int C, int S, int p, void* stream);
+/* The adjoint (the backward nodes of the same lines).  dcentre, dother: the two halves of dpatches
+ * [2 N][p + 2][p + 2][C] -- [N][p + 2][p + 2][C] each, images 0 .. N - 1 and N .. 2 N - 1; two pointers because the two
+ * siamese-stage calls hand back two tensors (dother = dcentre + N (p + 2)(p + 2) C for one tensor).  Their borders are
+ * not read.  dx_pt [N][Hp][Wp][C]: every element of the Hl x Wl interior is written exactly once -- zeros outside both
+ * footprints --, the border never.  A gather in a FIXED ORDER: per element one fp32 accumulator,
+ *     acc <- acc + g_q[n][i][j][c] * (wy(i) wx(j)),   product and sum rounded separately,
+ * centre patch (q = 0) before other patch (q = 1), inside a patch the pixels in ascending (i, j); wy(i) =
+ * [y0(i) == ys] (1 - ly(i)) + [y1(i) == ys] ly(i) with (y0, y1, ly) the source rows and weight of patch row i as
+ * iic_bilinear_fwd computes them, wx(j) likewise, wy wx rounded once.  Patch pixels whose taps miss the element are
+ * skipped.  Overlapping footprints both contribute.  One rounding to bf16 at the store.  No float atomics: two calls give
+ * the same bits. */
+int iic_seg_patch_sample_bwd(const void* dcentre, const void* dother, int pt_is_f32, const int* coords, void* dx_pt, int N,
+                             int Hl, int Wl, int Hp, int Wp, int off, int C, int S, int p, void* stream);
+/* The joint Linear(2 C p p -> F) of net10a_isola.py:29 / net10a_doersch.py:24 over torch.cat of the two flattened
+ * siamese activations (net10a_isola.py:52-58, net10a_doersch.py:46-52) and its backward nodes:
+ *     y[n][f] = sum_q sum_k a_q[n][k] w[f][q K + k] + b[f],   K = C p p in the parameter's (c, h, w) column order.
+ * a0_pt, a1_pt (and dx0_pt, dx1_pt): bf16 PT tensors [N][p + 2][p + 2][C], border 1 -- the siamese stage's output for
+ * the centre and for the other patch, read in place.  The kernels are those of iic_sup_* (bf16 MFMA, fp32 accumulation,
+ * fixed-order sums, no float atomics: two calls give identical bits).
+ * Served: N >= 1, any odd p, C % 64 == 0, F % 64 == 0; anything else returns IIC_ERR_UNSUPPORTED before a launch. */
+/* wb [F][2 K] = bf16(w), each column half permuted to the PT interior order (h, w, c); wt [2 K][F]: its transpose.
+ * Once per optimiser step. */
+int iic_pair_weight_prep(const float* w, void* wb, void* wt, int F, int C, int p, void* stream);
+/* K slices S of the forward for this shape (0: unsupported): S > 1 needs ws, S * N * F floats.  Host only. */
+int iic_pair_linear_fwd_nsplit(int N, int F, int C, int p);
+/* y fp32 [N][F]: the 2 K / 64 K-tiles -- those of q = 0, then those of q = 1 -- are cut into S consecutive slices, the
+ * slices' partial matrices are added in index order, then the bias (nullable). */
+int iic_pair_linear_fwd(const void* a0_pt, const void* a1_pt, const void* wb, const float* bias, float* y, float* ws, int N,
+                        int F, int C, int p, void* stream);
+/* dx_q[n][k] = sum_f dyb[n][f] wt[q K + k][f], bf16 (round to nearest even) into the interior of dx0_pt / dx1_pt; no
+ * ReLU mask (the siamese stage's BatchNorm backward applies its own).  dyb / dyt: iic_sup_dy_cast. */
+int iic_pair_linear_bwd_dx(const void* dyb, const void* wt, void* dx0_pt, void* dx1_pt, int N, int F, int C, int p,
+                           void* stream);
+/* dW[f][q K + c p p + hw] = sum_n dyt[f][n] a_q[n][hw][c]: fp32 [F][2 K], in the parameter's own column order. */
+int iic_pair_linear_wgrad(const void* dyt, const void* a0_pt, const void* a1_pt, float* dW, int N, int F, int C, int p,
+                          void* stream);
+/* code/utils/segmentation/baselines/isola_utils.py:27-72 (isola_loss) and its backward, one launch, nothing read back
+ * (the reference calls norm_factor.item() every step).  prob fp32 [N]: the net's output, sigmoid applied;
+ * mask_u8 [N][S][S].  m_n = (mask[n][cy][cx] + mask[n][oy][ox]) > 0, norm = sum m_n; t_n = p_n (label != 0) or
+ * fl32(1 - p_n); a row is dropped iff t_n < EPS = 2^-52 (sys.float_info.epsilon);
+ *     loss = -(1 / norm) sum_kept m_n log t_n      dprob_n = -+ m_n / (norm t_n), exactly 0 for dropped rows
+ * log and the sum in float64, rows in index order, one rounding to fp32 each.  The expression is evaluated as the
+ * reference writes it, so a non-finite p behaves as float64 torch does (0 * NaN is NaN).  norm == 0: the loss and every
+ * gradient are NaN (the reference dies of ZeroDivisionError there).  dprob nullable.  Two calls give the same bits. */
+int iic_isola_loss(const float* prob, const unsigned char* mask_u8, const int* coords, float* loss, float* dprob, int N,
+                   int S, void* stream);
+/* code/utils/segmentation/baselines/doersch_utils.py:55-66 (doersch_loss with nn.CrossEntropyLoss(reduction="none")) and
+ * its backward, one launch.  logits fp32 [N][k], k <= 32 (else IIC_ERR_UNSUPPORTED); the target of every row is the
+ * block's label (clamped into [0, k)).  ce_n = logsumexp(x_n) - x_n[label], max-subtracted float64;
+ *     loss = sum_n m_n ce_n / norm      dlogits = (m_n / norm) (softmax(x_n) - onehot)
+ * rows in index order, one rounding to fp32 each; norm == 0 makes all of them NaN, the value of the reference's
+ * expression.  dlogits nullable.  Two calls give the same bits. */
+int iic_doersch_loss(const float* logits, const unsigned char* mask_u8, const int* coords, float* loss, float* dlogits,
+                     int N, int k, int S, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif
