@@ -6,7 +6,9 @@ implemented on hand-written HIP kernels behind the C ABI of ``libiic_hip.so``
 (include/iic_hip.h).  ``iic_amd.install.install()`` registers them under the reference's
 module names so its training scripts import them unchanged.
 
-Submodules: losses, seg_losses, transforms, archs, optim, dist, install, geom, ops, branches, pool, augment, seg_augment, seg_ragged, seg_prescale, semisup, seg_baselines, _lib.
+Submodules: losses, seg_losses, transforms, archs, optim, dist, install, geom, ops, branches, pool, augment, seg_augment, seg_ragged, seg_prescale, linear, semisup, seg_baselines, _lib.
+``linear`` holds every fully-connected layer (exact fp32, and bf16 MFMA over one or two PT activations); the heads of
+archs, semisup and the baselines call it.
 """
 import importlib
 

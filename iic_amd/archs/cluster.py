@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from .. import geom as G
 from .. import ops
+from ..linear import linear_f32_backward, linear_f32_forward
 
 __all__ = ["ClusterNet5g", "ClusterNet5gTwoHead"]
 
@@ -91,11 +92,7 @@ class _Chain(object):
   def __init__(self):
     self.ctx = self.y2 = self.yd = self.blk = None
 
-_WEIGHTS_EPOCH = [0]   # bumped by iic_amd.optim.Adam (raw-pointer updates do not bump _version)
-
-
-def bump_weights_epoch():
-  _WEIGHTS_EPOCH[0] += 1
+_WEIGHTS_EPOCH, bump_weights_epoch = ops.WEIGHTS_EPOCH, ops.bump_weights_epoch      # the same objects, under their names here
 
 
 _HOLDERS = {}     # branch -> WeakSet of _ConvHolder with an operand set in that branch
@@ -554,14 +551,10 @@ class _HeadsFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, feats, Wcat, bcat, H, k):
-    N, F = feats.shape
+    N = feats.shape[0]
     feats = feats.contiguous()
     Wcat = Wcat.contiguous()
-    KT = H * k
-    logits = torch.empty((N, KT), dtype=torch.float32, device=feats.device)
-    # logits[n][j] = sum_c feats[n][c] * Wcat[j][c] + b[j]
-    ops.gemm_f32(feats, F, 1, Wcat, 1, F, logits, KT, N, KT, F, bias=bcat.contiguous())
-    probs = ops.softmax_fwd(logits, N * H, k)
+    probs = ops.softmax_fwd(linear_f32_forward(feats, Wcat, bcat), N * H, k)
     ctx.save_for_backward(feats, Wcat, probs)
     ctx.hk = (H, k)
     ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]   # (the K-split GEMM workspace is per branch)
@@ -571,17 +564,9 @@ class _HeadsFn(torch.autograd.Function):
   def backward(ctx, dprobs):
     feats, Wcat, probs = ctx.saved_tensors
     H, k = ctx.hk
-    N, F = feats.shape
-    KT = H * k
-    dlog = ops.softmax_bwd(probs, dprobs.contiguous().view(N, KT), N * H, k)
-    # dW[j][c] = sum_n dlog[n][j] feats[n][c]
-    dW = torch.empty((KT, F), dtype=torch.float32, device=feats.device)
-    ops.gemm_f32(dlog, 1, KT, feats, F, 1, dW, F, KT, F, N)
-    db = ops.colsum(dlog, N, KT)
-    # dfeats[n][c] = sum_j dlog[n][j] Wcat[j][c]
-    dfe = torch.empty((N, F), dtype=torch.float32, device=feats.device)
-    ops.gemm_f32(dlog, KT, 1, Wcat, F, 1, dfe, F, N, F, KT)
-    return dfe, dW, db, None, None
+    N = feats.shape[0]
+    dlog = ops.softmax_bwd(probs, dprobs.contiguous().view(N, H * k), N * H, k)
+    return linear_f32_backward(dlog, feats, Wcat) + (None, None)
 
 
 class ClusterNet5gHead(nn.Module):

@@ -6,7 +6,7 @@ The reference up-samples all 512 trunk channels to input_sz (fp32 [N, 512, S, S]
 again in backward) and slices the two patches out of the result.  Here only the 2 p p pixels per image that the patches
 hold are interpolated, straight into the siamese conv's operand layout (iic_seg_patch_sample_fwd, csrc/seg_patches.hip);
 their adjoint goes back into the trunk's gradient as a fixed-order gather.  The joint Linear(2 * 1024 * p * p -> 1024)
-reads both stage outputs in place on the bf16 MFMA pipe (iic_pair_*, csrc/sup_head.hip).
+reads both stage outputs in place on the bf16 MFMA pipe (linear.PTLinearFn over iic_pair_*, csrc/sup_head.hip).
 
   forward     trunk -> sampler -> siamese stage (conv 3x3 512 -> 1024 + BatchNorm + ReLU; the centre images, then the
               other images: two calls, each with its own batch statistics, the running statistics updated in that order,
@@ -15,7 +15,7 @@ reads both stage outputs in place on the bf16 MFMA pipe (iic_pair_*, csrc/sup_he
   state_dict  the reference's keys: features.*, {isola,doersch}_head.siamese_branch.{0,1}.*, {..}_head.joint.{0,3}.*
 
 Under ops.fp32_mode() the same modules run on the exact-fp32 kernels (the fp32 sampler flavour, _StageFn's fp32 branch,
-_FlattenFn per half + _LinearF32Fn): the parity tier.  ReLU, dropout, the sigmoid and the second Linear act on [N, 1024]
+_FlattenFn per half + linear.LinearF32Fn): the parity tier.  ReLU, dropout, the sigmoid and the second Linear act on [N, 1024]
 and are not the hot path (torch ops and iic_gemm_f32).
 
 Both classes subclass SegmentationNet10aFeatures: trunk_pt, load_trunk_state_dict and the k-means evaluation twins of
@@ -26,22 +26,14 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import IICLibraryError, check, lib, ptr, stream_ptr
-from . import cluster as _cl
+from .._lib import check, lib, ptr, stream_ptr
+from ..linear import LinearF32Fn, PTLinearFn, PTLinearOperands
 from .seg import SegmentationNet10a, SegmentationNet10aFeatures, SegmentationNet10aTrunk
 from .vgg import _FlattenFn, _Stage, _StageFn, _initialize_weights_vgg
 
 __all__ = ["SegmentationNet10aIsola", "SegmentationNet10aDoersch", "coords_block", "check_patches", "patch_sample",
-           "patch_sample_bwd", "pair_weight_prep", "pair_linear_forward", "pair_linear_bwd_dx", "pair_linear_wgrad",
-           "pair_fwd_nsplit"]
+           "patch_sample_bwd"]
 F32, BF16 = torch.float32, torch.bfloat16
-
-
-def _semisup():
-  """iic_amd.semisup (SUP_WS, dy_cast, _LinearF32Fn), imported at first use: that module imports this package."""
-  from .. import semisup
-  return semisup
-
 
 HEAD_C = 1024         # channels of the siamese stage (net10a_isola.py:19, net10a_doersch.py:19)
 MAX_PATCH = 127       # patch side the sampler serves
@@ -149,103 +141,6 @@ class _PatchSampleFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------
-# joint Linear over the two siamese activations
-# ------------------------------------------------------------------------------------
-def pair_fwd_nsplit(N, F, C, p):
-  """K slices of the pair forward (iic_pair_linear_fwd_nsplit); 0: unsupported shape.  Host only."""
-  return int(lib().iic_pair_linear_fwd_nsplit(int(N), int(F), int(C), int(p)))
-
-
-def pair_weight_prep(w, C, p, wb=None, wt=None):
-  """(wb [F, 2K], wt [2K, F]) bf16 operands of the fp32 parameter w [F, 2K], K = C p p (iic_pair_weight_prep)."""
-  Fo, K2 = w.shape
-  if K2 != 2 * C * p * p:
-    raise ValueError("joint Linear: weight has %d columns, 2 * %d * %d * %d expected" % (K2, C, p, p))
-  wb = torch.empty((Fo, K2), dtype=BF16, device=w.device) if wb is None else wb
-  wt = torch.empty((K2, Fo), dtype=BF16, device=w.device) if wt is None else wt
-  check(lib().iic_pair_weight_prep(ptr(w), ptr(wb), ptr(wt), Fo, C, p, stream_ptr()), "iic_pair_weight_prep")
-  return wb, wt
-
-
-def pair_linear_forward(a0, a1, wb, bias, F):
-  """y fp32 [N, F] = sum_q interior(a_q) . wb[:, q K:(q + 1) K]^T + bias (iic_pair_linear_fwd)."""
-  N, Hp, _, C = a0.shape
-  p = Hp - 2
-  S = pair_fwd_nsplit(N, F, C, p)
-  if S < 1:
-    raise IICLibraryError("iic_pair_linear_fwd: unsupported shape C = %d, F = %d, p = %d (C, F multiples of 64, p odd)"
-                          % (C, F, p))
-  y = torch.empty((N, F), dtype=F32, device=a0.device)
-  ws = _semisup().SUP_WS.get(a0.device, S * N * F) if S > 1 else None
-  check(lib().iic_pair_linear_fwd(ptr(a0), ptr(a1), ptr(wb), ptr(bias), ptr(y), ptr(ws), N, F, C, p, stream_ptr()),
-        "iic_pair_linear_fwd")
-  return y
-
-
-def pair_linear_bwd_dx(dyb, wt, dx0, dx1):
-  N, Hp, _, C = dx0.shape
-  check(lib().iic_pair_linear_bwd_dx(ptr(dyb), ptr(wt), ptr(dx0), ptr(dx1), N, dyb.shape[1], C, Hp - 2, stream_ptr()),
-        "iic_pair_linear_bwd_dx")
-  return dx0, dx1
-
-
-def pair_linear_wgrad(dyt, a0, a1):
-  N, Hp, _, C = a0.shape
-  p, F = Hp - 2, dyt.shape[0]
-  dW = torch.empty((F, 2 * C * p * p), dtype=F32, device=a0.device)
-  check(lib().iic_pair_linear_wgrad(ptr(dyt), ptr(a0), ptr(a1), ptr(dW), N, F, C, p, stream_ptr()),
-        "iic_pair_linear_wgrad")
-  return dW
-
-
-class _PairOperands(object):
-  """bf16 operands (wb [F][2K], wt [2K][F]) of the joint Linear, per branch; re-written in place when the parameter has
-  changed since they were made (data pointer, version counter, optimiser epoch) -- semisup._LinearOperands' rule."""
-
-  def __init__(self):
-    self._ent = {}      # branch -> [key, wb, wt]
-
-  def get(self, w, C, p):
-    b = ops.current_branch()
-    key = (w.data_ptr(), w._version, _cl._WEIGHTS_EPOCH[0], C, p)
-    ent = self._ent.get(b)
-    if ent is not None and ent[0] == key:
-      return ent[1], ent[2]
-    if ent is None or ent[1].device != w.device or ent[1].numel() != w.numel():
-      ent = self._ent[b] = [None, None, None]
-    ent[1], ent[2] = pair_weight_prep(w, C, p, ent[1], ent[2])
-    ent[0] = key
-    return ent[1], ent[2]
-
-
-class _PairLinearFn(torch.autograd.Function):
-  """Joint Linear over the siamese stage's two bf16 PT outputs [N, p+2, p+2, C] -> fp32 [N, F]."""
-
-  @staticmethod
-  def forward(ctx, a0, a1, w, b, operands):
-    assert a0.dtype is BF16 and a1.dtype is BF16 and a0.is_contiguous() and a1.is_contiguous() and a0.shape == a1.shape
-    N, Hp, Wp, C = a0.shape
-    wb, wt = operands.get(w.detach(), C, Hp - 2)
-    ctx.save_for_backward(a0, a1, wt)
-    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
-    return pair_linear_forward(a0, a1, wb, b.detach() if b is not None else None, w.shape[0])
-
-  @ops.branch_backward
-  def backward(ctx, dy):
-    a0, a1, wt = ctx.saved_tensors
-    N, Hp, Wp, C = a0.shape
-    dy = dy.contiguous()
-    dyb, dyt = _semisup().dy_cast(dy)
-    dx0 = dx1 = None
-    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-      dx0, dx1 = pair_linear_bwd_dx(dyb, wt, ops.pt_alloc(N, Hp - 2, Wp - 2, C, 1, dy.device),
-                                    ops.pt_alloc(N, Hp - 2, Wp - 2, C, 1, dy.device))
-    dW = pair_linear_wgrad(dyt, a0, a1)
-    db = ops.colsum(dy, N, dy.shape[1]) if ctx.needs_input_grad[3] else None
-    return dx0, dx1, dW, db, None
-
-
-# ------------------------------------------------------------------------------------
 # the nets
 # ------------------------------------------------------------------------------------
 class _BaselineHead(nn.Module):
@@ -279,7 +174,7 @@ class _BaselineNet(SegmentationNet10aFeatures):
     setattr(self, self.HEAD_ATTR, head)
     _initialize_weights_vgg(self)                                   # (VGGNet._initialize_weights, vgg.py:42-54)
     self._stage = _Stage(head.siamese_branch[0], head.siamese_branch[1], pool=False, first=False, P=1)
-    self._operands = _PairOperands()
+    self._operands = PTLinearOperands()
     # test hook: a [N, 1024] keep-mask (0 / 1) used instead of the one torch draws on the device in train() mode
     self.dropout_keep = None
 
@@ -308,18 +203,17 @@ class _BaselineNet(SegmentationNet10aFeatures):
     """The head path on the trunk's PT feature tensor: sampler -> siamese stage twice -> joint Linear -> ReLU ->
     dropout -> second Linear (pre-sigmoid).  forward() validates the coordinates before it gets here."""
     lin1, lin2 = self.head.joint[0], self.head.joint[3]
-    _LinearF32Fn = _semisup()._LinearF32Fn
     coords = coords_block((cy, cx), (oy, ox), 0, pt.device)
     p0, p1 = _PatchSampleFn.apply(pt, coords, self.input_sz, self.patch_side)
     a0 = self._siamese(p0)       # two calls: own batch statistics each, running statistics updated in this order
     a1 = self._siamese(p1)
     if a0.dtype == F32:          # ops.fp32_mode(): (c, h, w) flatten per half, torch.cat, exact fp32 GEMM
-      h = _LinearF32Fn.apply(torch.cat([_FlattenFn.apply(a0, 1), _FlattenFn.apply(a1, 1)], dim=1), ops.pv(lin1.weight),
-                             ops.pv(lin1.bias))
+      h = LinearF32Fn.apply(torch.cat([_FlattenFn.apply(a0, 1), _FlattenFn.apply(a1, 1)], dim=1), ops.pv(lin1.weight),
+                            ops.pv(lin1.bias))
     else:
-      h = _PairLinearFn.apply(a0, a1, ops.pv(lin1.weight), ops.pv(lin1.bias), self._operands)
+      h = PTLinearFn.apply(a0, a1, ops.pv(lin1.weight), ops.pv(lin1.bias), self._operands)
     h = self._dropout(torch.relu(h))
-    return _LinearF32Fn.apply(h, ops.pv(lin2.weight), ops.pv(lin2.bias))
+    return LinearF32Fn.apply(h, ops.pv(lin2.weight), ops.pv(lin2.bias))
 
   def forward(self, x, centre=None, other=None, penultimate=False):
     if penultimate:

@@ -17,44 +17,12 @@ import torch.nn as nn
 
 from .. import ops
 from ..branches import context, join
+from ..linear import LinearF32Fn
 from ..pool import POOL
 from .cluster import BasicBlock, ClusterNet5gTrunk, _ApplyCounter, _initialize_weights
 from .vgg import ClusterNet6c, ClusterNet6cTrunk, _initialize_weights_vgg
 
 __all__ = ["TripletsNet5g", "TripletsNet6c"]
-
-
-class _LinearFn(torch.autograd.Function):
-  """feats [N, F] fp32, W [k, F], b [k] -> logits [N, k] on the exact-fp32 GEMM: cluster._HeadsFn without its softmax."""
-
-  @staticmethod
-  def forward(ctx, feats, W, b):
-    assert feats.is_cuda, "TripletsNet (HIP): device tensors required -- no CPU fallback"
-    N, F = feats.shape
-    k = W.shape[0]
-    feats = feats.contiguous()
-    W = W.contiguous()
-    logits = torch.empty((N, k), dtype=torch.float32, device=feats.device)
-    # logits[n][j] = sum_c feats[n][c] * W[j][c] + b[j]
-    ops.gemm_f32(feats, F, 1, W, 1, F, logits, k, N, k, F, bias=b.contiguous())
-    ctx.save_for_backward(feats, W)
-    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]   # (the K-split GEMM workspace is per branch)
-    return logits
-
-  @ops.branch_backward
-  def backward(ctx, dlog):
-    feats, W = ctx.saved_tensors
-    N, F = feats.shape
-    k = W.shape[0]
-    dlog = dlog.contiguous()
-    # dW[j][c] = sum_n dlog[n][j] feats[n][c]
-    dW = torch.empty((k, F), dtype=torch.float32, device=feats.device)
-    ops.gemm_f32(dlog, 1, k, feats, F, 1, dW, F, k, F, N)
-    db = ops.colsum(dlog, N, k)
-    # dfeats[n][c] = sum_j dlog[n][j] W[j][c]
-    dfe = torch.empty((N, F), dtype=torch.float32, device=feats.device)
-    ops.gemm_f32(dlog, k, 1, W, F, 1, dfe, F, N, F, k)
-    return dfe, dW, db
 
 
 class _TripletsHead(nn.Module):
@@ -66,7 +34,7 @@ class _TripletsHead(nn.Module):
   def forward(self, x, kmeans_use_features=False):
     if kmeans_use_features:
       return x
-    return _LinearFn.apply(x, ops.pv(self.head.weight), ops.pv(self.head.bias))
+    return LinearF32Fn.apply(x, ops.pv(self.head.weight), ops.pv(self.head.bias))
 
 
 class TripletsNet5gHead(_TripletsHead):

@@ -1,4 +1,6 @@
-// Supervised head of the semi-supervised fine-tuning step for gfx950: Linear(C H W -> F) on layer 3's bf16 PT tensor,
+// The Linear over bf16 PT activations for gfx950, one family for one or two operands: Linear(C H W -> F) on layer 3's PT
+// tensor (the supervised head of the semi-supervised fine-tuning step, iic_sup_*) and the joint Linear(2 C p p -> F) over
+// the two patch activations of the Isola / Doersch baselines' heads (iic_pair_*); then the rest of the supervised head:
 // BatchNorm1d + ReLU, cross-entropy, and the ten-crop accuracy count.
 //
 // Replaces code/archs/semisup/sup_head5.py:12-19,33-37 (nn.Linear + nn.BatchNorm1d + nn.ReLU over
@@ -16,9 +18,9 @@
 // parameter's (c, h, w) order.  One block = 4 waves = a 128 x 128 output tile (2 x 2 MFMA tiles of 32 x 32 per wave), K-tiles
 // of 64 through double-buffered LDS at a 144-byte row pitch.  No float atomics anywhere: the forward's K split writes
 // partial matrices that sup_fold_kernel adds in index order, so two runs give equal bits.
-// The joint Linear of the Isola / Doersch baselines' heads (iic_pair_*, at the end of the file) runs on the same kernels:
-// its K axis covers two PT activations, one after the other, and each column half of its weight is a matrix whose rows
-// are 2 K apart.
+// With two operands the forward's K axis covers both PT activations, one after the other, and each column half of the
+// weight is a matrix whose rows are 2 K apart: the same kernels, driven by one set of host routines (lin_*, below the
+// kernels) that the iic_sup_* and iic_pair_* entries call with an operand count of 1 or 2.
 #include "common.h"
 #include "../../include/iic_hip.h"
 
@@ -504,51 +506,64 @@ sup_mat sup_flat(const void* p, int rows, int cols) {
   m.rows = rows;
   return m;
 }
-int sup_nsplit(int N, int F, int K) {
-  // K slices of the forward: enough workgroups for two per CU, at least 8 K-tiles each, at most 16
-  const long tiles = (long)((N + TM - 1) / TM) * ((F + TN - 1) / TN);
-  const int ktiles = K / BK;
-  long s = (2L * iic_num_cus() + tiles - 1) / tiles;
-  if (s > ktiles / 8) s = ktiles / 8;
-  if (s > 16) s = 16;
-  return s < 1 ? 1 : (int)s;
+
+// ---- host side of the Linear over Q = 1 or 2 PT operands -------------------------------------------------------------
+// y[n][f] = sum_q sum_k a_q[n][k] w[f][q K + k] + b[f], K = H W C per operand: iic_sup_* is Q = 1, iic_pair_* (the joint
+// Linear of the Isola / Doersch heads over the two p x p patch activations) Q = 2 with H = W = p.  The forward runs its K
+// axis over both activations (sup_gemm_kernel's A, A2); everywhere else the column halves of w are handled one after
+// the other by the same kernels: a half of w, wb or dW is a matrix whose rows are Q K apart.
+struct lin_shape {
+  int N, F, C, H, W, Q;
+};
+bool lin_shape_ok(const lin_shape& s) {
+  if (!sup_shape_ok(s.N, s.F, s.C, s.H, s.W)) return false;
+  return s.Q == 1 || (s.H == s.W && (s.H & 1) == 1 && 2L * s.H * s.W * s.C < (1L << 30));
+}
+// K slices of the forward: enough workgroups for two per CU (their LDS: 72 KB each) over the row x column tiles, at
+// least 8 K-tiles per slice, at most 16 slices for one operand and 64 for two.  The pair forward has a fraction of one
+// 128-row tile of images and reads every weight element once, so it is bound by streaming w and the slices are what
+// fills the chip -- at the Potsdam shape (N = 75, F = 1024, C = 1024, p = 11: 8 column tiles, 3872 K-tiles) 64 slices
+// of 60 or 61 K-tiles, whose partial matrices (64 x 75 x 1024 fp32, 20 MB) are 4 % of the 507 MB of weights read.
+int lin_nsplit(const lin_shape& s) {
+  const long tiles = (long)((s.N + TM - 1) / TM) * ((s.F + TN - 1) / TN);
+  const int ktiles = s.Q * s.H * s.W * s.C / BK, cap = s.Q == 1 ? 16 : 64;
+  long n = (2L * iic_num_cus() + tiles - 1) / tiles;
+  if (n > ktiles / 8) n = ktiles / 8;
+  if (n > cap) n = cap;
+  return n < 1 ? 1 : (int)n;
 }
 
-}  // namespace
-
-extern "C" {
-
-int iic_sup_weight_prep(const float* w, void* wb, void* wt, int F, int C, int H, int W, void* stream) {
-  if (!w || !wb || !wt) return IIC_ERR_ARG;
-  if (!sup_shape_ok(1, F, C, H, W)) return IIC_ERR_UNSUPPORTED;
-  const int HW = H * W;
+// wb, wt of w [F][Q K]; per half: the forward operand, then the backward one
+int lin_weight_prep(const float* w, void* wb, void* wt, const lin_shape& s, void* stream) {
+  if (!lin_shape_ok(s)) return IIC_ERR_UNSUPPORTED;
+  const int F = s.F, C = s.C, HW = s.H * s.W;
   const long K = (long)C * HW;
   if (F > 65535 || C / 64 > 65535) return IIC_ERR_UNSUPPORTED;
-  int rc = iic_launch_lds<sup_weight_prep_fwd_kernel>(dim3((HW + 63) / 64, C / 64, F), dim3(256), 0, (hipStream_t)stream, w,
-                                                      (bf16_t*)wb, C, HW, K);
-  if (rc) return rc;
-  rc = iic_launch_lds<sup_weight_prep_bwd_kernel>(dim3((unsigned)((K + 63) / 64), (F + 63) / 64), dim3(256), 0,
-                                                  (hipStream_t)stream, w, (bf16_t*)wt, F, C, HW, K);
-  if (rc) return rc;
+  for (int q = 0; q < s.Q; ++q) {
+    int rc = iic_launch_lds<sup_weight_prep_fwd_kernel>(dim3((HW + 63) / 64, C / 64, F), dim3(256), 0, (hipStream_t)stream,
+                                                        w + q * K, (bf16_t*)wb + q * K, C, HW, s.Q * K);
+    if (rc) return rc;
+    rc = iic_launch_lds<sup_weight_prep_bwd_kernel>(dim3((unsigned)((K + 63) / 64), (F + 63) / 64), dim3(256), 0,
+                                                    (hipStream_t)stream, w + q * K, (bf16_t*)wt + q * K * F, F, C, HW,
+                                                    s.Q * K);
+    if (rc) return rc;
+  }
   return iic_launch_status();
 }
 
-int iic_sup_fwd_nsplit(int N, int F, int C, int H, int W) {
-  if (!sup_shape_ok(N, F, C, H, W)) return 0;
-  return sup_nsplit(N, F, H * W * C);
-}
-
-int iic_sup_linear_fwd(const void* x_pt, const void* wb, const float* bias, float* y, float* ws, int N, int F, int C, int H,
-                       int W, void* stream) {
-  if (!x_pt || !wb || !y) return IIC_ERR_ARG;
-  if (!sup_shape_ok(N, F, C, H, W)) return IIC_ERR_UNSUPPORTED;
-  const int K = H * W * C;
-  const int S = sup_nsplit(N, F, K);
+// a1_pt is read at Q = 2 only
+int lin_fwd(const void* a0_pt, const void* a1_pt, const void* wb, const float* bias, float* y, float* ws,
+            const lin_shape& s, void* stream) {
+  if (!lin_shape_ok(s)) return IIC_ERR_UNSUPPORTED;
+  const int N = s.N, F = s.F, K = s.H * s.W * s.C;
+  const int S = lin_nsplit(s);
   if (S > 1 && !ws) return IIC_ERR_ARG;
-  const sup_mat A = sup_pt(x_pt, N, H, W, C), B = sup_flat(wb, F, K), none = sup_flat(nullptr, 0, 1);
+  const sup_mat A = sup_pt(a0_pt, N, s.H, s.W, s.C), A2 = s.Q == 2 ? sup_pt(a1_pt, N, s.H, s.W, s.C) : A,
+                B = sup_flat(wb, F, s.Q * K), none = sup_flat(nullptr, 0, 1);
   dim3 grid((N + TM - 1) / TM, (F + TN - 1) / TN, S);
-  int rc = iic_launch_lds<sup_gemm_kernel<false>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, A, K / BK, B, K,
-                                                  S > 1 ? (const float*)nullptr : bias, S > 1 ? ws : y, (long)F, none);
+  int rc = iic_launch_lds<sup_gemm_kernel<false>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, A2, K / BK, B,
+                                                  s.Q * K, S > 1 ? (const float*)nullptr : bias, S > 1 ? ws : y, (long)F,
+                                                  none);
   if (rc) return rc;
   if (S > 1) {
     const long mn = (long)N * F;
@@ -557,6 +572,59 @@ int iic_sup_linear_fwd(const void* x_pt, const void* wb, const float* bias, floa
     if (rc) return rc;
   }
   return iic_launch_status();
+}
+
+// dx1_pt is written at Q = 2 only
+int lin_bwd_dx(const void* dyb, const void* wt, void* dx0_pt, void* dx1_pt, const lin_shape& s, void* stream) {
+  if (!lin_shape_ok(s)) return IIC_ERR_UNSUPPORTED;
+  const int N = s.N, F = s.F, K = s.H * s.W * s.C;
+  const sup_mat A = sup_flat(dyb, N, F);
+  dim3 grid((N + TM - 1) / TM, (K + TN - 1) / TN, 1);
+  for (int q = 0; q < s.Q; ++q) {
+    const sup_mat B = sup_flat((const bf16_t*)wt + (long)q * K * F, K, F),
+                  o = sup_pt(q ? dx1_pt : dx0_pt, N, s.H, s.W, s.C);
+    int rc = iic_launch_lds<sup_gemm_kernel<true>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, A, F / BK, B, F,
+                                                   (const float*)nullptr, (float*)nullptr, 0L, o);
+    if (rc) return rc;
+  }
+  return iic_launch_status();
+}
+
+// a1_pt is read at Q = 2 only
+int lin_wgrad(const void* dyt, const void* a0_pt, const void* a1_pt, float* dW, const lin_shape& s, void* stream) {
+  if (!lin_shape_ok(s)) return IIC_ERR_UNSUPPORTED;
+  const int N = s.N, F = s.F, C = s.C, Np = (N + 63) / 64 * 64, HW = s.H * s.W;
+  const long K = (long)HW * C;
+  if ((HW + 15) / 16 > 65535 || C / 8 > 65535) return IIC_ERR_UNSUPPORTED;
+  const sup_mat A = sup_flat(dyt, F, Np);
+  dim3 grid((F + TM - 1) / TM, C / 8, (HW + 15) / 16);
+  for (int q = 0; q < s.Q; ++q) {
+    int rc = iic_launch_lds<sup_wgrad_kernel>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A,
+                                              (const bf16_t*)(q ? a1_pt : a0_pt), (long)(s.H + 2) * (s.W + 2) * C, N, s.H,
+                                              s.W, C, dW + q * K, s.Q * K);
+    if (rc) return rc;
+  }
+  return iic_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int iic_sup_weight_prep(const float* w, void* wb, void* wt, int F, int C, int H, int W, void* stream) {
+  if (!w || !wb || !wt) return IIC_ERR_ARG;
+  return lin_weight_prep(w, wb, wt, lin_shape{1, F, C, H, W, 1}, stream);
+}
+
+int iic_sup_fwd_nsplit(int N, int F, int C, int H, int W) {
+  const lin_shape s{N, F, C, H, W, 1};
+  return lin_shape_ok(s) ? lin_nsplit(s) : 0;
+}
+
+int iic_sup_linear_fwd(const void* x_pt, const void* wb, const float* bias, float* y, float* ws, int N, int F, int C, int H,
+                       int W, void* stream) {
+  if (!x_pt || !wb || !y) return IIC_ERR_ARG;
+  return lin_fwd(x_pt, nullptr, wb, bias, y, ws, lin_shape{N, F, C, H, W, 1}, stream);
 }
 
 int iic_sup_dy_cast(const float* dy, void* dyb, void* dyt, int N, int F, void* stream) {
@@ -570,27 +638,12 @@ int iic_sup_dy_cast(const float* dy, void* dyb, void* dyt, int N, int F, void* s
 
 int iic_sup_linear_bwd_dx(const void* dyb, const void* wt, void* dx_pt, int N, int F, int C, int H, int W, void* stream) {
   if (!dyb || !wt || !dx_pt) return IIC_ERR_ARG;
-  if (!sup_shape_ok(N, F, C, H, W)) return IIC_ERR_UNSUPPORTED;
-  const int K = H * W * C;
-  const sup_mat A = sup_flat(dyb, N, F), B = sup_flat(wt, K, F), o = sup_pt(dx_pt, N, H, W, C);
-  dim3 grid((N + TM - 1) / TM, (K + TN - 1) / TN, 1);
-  int rc = iic_launch_lds<sup_gemm_kernel<true>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, A, F / BK, B, F,
-                                                 (const float*)nullptr, (float*)nullptr, 0L, o);
-  if (rc) return rc;
-  return iic_launch_status();
+  return lin_bwd_dx(dyb, wt, dx_pt, nullptr, lin_shape{N, F, C, H, W, 1}, stream);
 }
 
 int iic_sup_linear_wgrad(const void* dyt, const void* x_pt, float* dW, int N, int F, int C, int H, int W, void* stream) {
   if (!dyt || !x_pt || !dW) return IIC_ERR_ARG;
-  if (!sup_shape_ok(N, F, C, H, W)) return IIC_ERR_UNSUPPORTED;
-  const int Np = (N + 63) / 64 * 64, HW = H * W;
-  if ((HW + 15) / 16 > 65535 || C / 8 > 65535) return IIC_ERR_UNSUPPORTED;
-  const sup_mat A = sup_flat(dyt, F, Np);
-  dim3 grid((F + TM - 1) / TM, C / 8, (HW + 15) / 16);
-  int rc = iic_launch_lds<sup_wgrad_kernel>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, (const bf16_t*)x_pt,
-                                            (long)(H + 2) * (W + 2) * C, N, H, W, C, dW, (long)HW * C);
-  if (rc) return rc;
-  return iic_launch_status();
+  return lin_wgrad(dyt, x_pt, nullptr, dW, lin_shape{N, F, C, H, W, 1}, stream);
 }
 
 int iic_sup_bn_relu_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
@@ -636,105 +689,34 @@ int iic_sup_tencrop_acc(const float* logits, const long long* targets, long long
   return iic_launch_status();
 }
 
-// ---- joint Linear of the Isola / Doersch heads over the two patch activations (iic_hip.h: iic_pair_*) ----------------
-// y[n][f] = sum_q sum_k a_q[n][k] w[f][q K + k] + b[f], K = C p p: the same three products with the K axis of the
-// forward running over both activations (sup_gemm_kernel's A, A2) and the two column halves of w handled one after the
-// other everywhere else.  The same kernels as iic_sup_*: a half of w is a matrix with row stride 2 K.
-
-static bool pair_shape_ok(int N, int F, int C, int p) {
-  return p >= 1 && (p & 1) == 1 && sup_shape_ok(N, F, C, p, p) && 2L * p * p * C < (1L << 30);
-}
-// K slices of the pair forward.  N is a fraction of one 128-row tile and every weight element is read once, so the
-// product is bound by streaming w: the slices are what fills the chip.  Two workgroups per CU (their LDS: 72 KB each)
-// over the row x column tiles, at least 8 K-tiles per slice, at most 64 slices -- at the Potsdam shape (N = 75,
-// F = 1024, C = 1024, p = 11: 8 column tiles, 3872 K-tiles) 64 slices of 60 or 61 K-tiles, whose partial matrices
-// (64 x 75 x 1024 fp32, 20 MB) are 4 % of the 507 MB of weights read.
-static int pair_nsplit(int N, int F, int K2) {
-  const long tiles = (long)((N + TM - 1) / TM) * ((F + TN - 1) / TN);
-  const int ktiles = K2 / BK;
-  long s = (2L * iic_num_cus() + tiles - 1) / tiles;
-  if (s > ktiles / 8) s = ktiles / 8;
-  if (s > 64) s = 64;
-  return s < 1 ? 1 : (int)s;
-}
+// ---- the joint Linear of the Isola / Doersch heads (iic_hip.h: iic_pair_*): the same routines at Q = 2, H = W = p ----
 
 int iic_pair_weight_prep(const float* w, void* wb, void* wt, int F, int C, int p, void* stream) {
   if (!w || !wb || !wt) return IIC_ERR_ARG;
-  if (!pair_shape_ok(1, F, C, p)) return IIC_ERR_UNSUPPORTED;
-  const int HW = p * p;
-  const long K = (long)C * HW;
-  if (F > 65535 || C / 64 > 65535) return IIC_ERR_UNSUPPORTED;
-  for (int q = 0; q < 2; ++q) {
-    int rc = iic_launch_lds<sup_weight_prep_fwd_kernel>(dim3((HW + 63) / 64, C / 64, F), dim3(256), 0, (hipStream_t)stream,
-                                                        w + q * K, (bf16_t*)wb + q * K, C, HW, 2 * K);
-    if (rc) return rc;
-    rc = iic_launch_lds<sup_weight_prep_bwd_kernel>(dim3((unsigned)((K + 63) / 64), (F + 63) / 64), dim3(256), 0,
-                                                    (hipStream_t)stream, w + q * K, (bf16_t*)wt + q * K * F, F, C, HW,
-                                                    2 * K);
-    if (rc) return rc;
-  }
-  return iic_launch_status();
+  return lin_weight_prep(w, wb, wt, lin_shape{1, F, C, p, p, 2}, stream);
 }
 
 int iic_pair_linear_fwd_nsplit(int N, int F, int C, int p) {
-  if (!pair_shape_ok(N, F, C, p)) return 0;
-  return pair_nsplit(N, F, 2 * p * p * C);
+  const lin_shape s{N, F, C, p, p, 2};
+  return lin_shape_ok(s) ? lin_nsplit(s) : 0;
 }
 
 int iic_pair_linear_fwd(const void* a0_pt, const void* a1_pt, const void* wb, const float* bias, float* y, float* ws, int N,
                         int F, int C, int p, void* stream) {
   if (!a0_pt || !a1_pt || !wb || !y) return IIC_ERR_ARG;
-  if (!pair_shape_ok(N, F, C, p)) return IIC_ERR_UNSUPPORTED;
-  const int K = p * p * C;
-  const int S = pair_nsplit(N, F, 2 * K);
-  if (S > 1 && !ws) return IIC_ERR_ARG;
-  const sup_mat A0 = sup_pt(a0_pt, N, p, p, C), A1 = sup_pt(a1_pt, N, p, p, C), B = sup_flat(wb, F, 2 * K),
-                none = sup_flat(nullptr, 0, 1);
-  dim3 grid((N + TM - 1) / TM, (F + TN - 1) / TN, S);
-  int rc = iic_launch_lds<sup_gemm_kernel<false>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A0, A1, K / BK, B, 2 * K,
-                                                  S > 1 ? (const float*)nullptr : bias, S > 1 ? ws : y, (long)F, none);
-  if (rc) return rc;
-  if (S > 1) {
-    const long mn = (long)N * F;
-    rc = iic_launch_lds<sup_fold_kernel>(dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                                         (const float*)ws, S, bias, y, mn, F);
-    if (rc) return rc;
-  }
-  return iic_launch_status();
+  return lin_fwd(a0_pt, a1_pt, wb, bias, y, ws, lin_shape{N, F, C, p, p, 2}, stream);
 }
 
 int iic_pair_linear_bwd_dx(const void* dyb, const void* wt, void* dx0_pt, void* dx1_pt, int N, int F, int C, int p,
                            void* stream) {
   if (!dyb || !wt || !dx0_pt || !dx1_pt) return IIC_ERR_ARG;
-  if (!pair_shape_ok(N, F, C, p)) return IIC_ERR_UNSUPPORTED;
-  const int K = p * p * C;
-  const sup_mat A = sup_flat(dyb, N, F);
-  dim3 grid((N + TM - 1) / TM, (K + TN - 1) / TN, 1);
-  for (int q = 0; q < 2; ++q) {
-    const sup_mat B = sup_flat((const bf16_t*)wt + (long)q * K * F, K, F), o = sup_pt(q ? dx1_pt : dx0_pt, N, p, p, C);
-    int rc = iic_launch_lds<sup_gemm_kernel<true>>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A, A, F / BK, B, F,
-                                                   (const float*)nullptr, (float*)nullptr, 0L, o);
-    if (rc) return rc;
-  }
-  return iic_launch_status();
+  return lin_bwd_dx(dyb, wt, dx0_pt, dx1_pt, lin_shape{N, F, C, p, p, 2}, stream);
 }
 
 int iic_pair_linear_wgrad(const void* dyt, const void* a0_pt, const void* a1_pt, float* dW, int N, int F, int C, int p,
                           void* stream) {
   if (!dyt || !a0_pt || !a1_pt || !dW) return IIC_ERR_ARG;
-  if (!pair_shape_ok(N, F, C, p)) return IIC_ERR_UNSUPPORTED;
-  const int Np = (N + 63) / 64 * 64, HW = p * p;
-  const long K = (long)HW * C;
-  if ((HW + 15) / 16 > 65535 || C / 8 > 65535) return IIC_ERR_UNSUPPORTED;
-  const sup_mat A = sup_flat(dyt, F, Np);
-  dim3 grid((F + TM - 1) / TM, C / 8, (HW + 15) / 16);
-  for (int q = 0; q < 2; ++q) {
-    int rc = iic_launch_lds<sup_wgrad_kernel>(grid, dim3(256), GEMM_LDS, (hipStream_t)stream, A,
-                                              (const bf16_t*)(q ? a1_pt : a0_pt), (long)(p + 2) * (p + 2) * C, N, p, p, C,
-                                              dW + q * K, 2 * K);
-    if (rc) return rc;
-  }
-  return iic_launch_status();
+  return lin_wgrad(dyt, a0_pt, a1_pt, dW, lin_shape{N, F, C, p, p, 2}, stream);
 }
 
 }  // extern "C"

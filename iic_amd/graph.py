@@ -22,7 +22,7 @@ import sys
 
 import torch
 
-from .archs.cluster import bump_weights_epoch
+from .ops import bump_weights_epoch
 
 
 def _no_gc(fn):

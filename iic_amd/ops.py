@@ -79,6 +79,14 @@ def weight_prep_frag(w, bwd):
 # IIC_CONV_FRAG=0 keeps every conv on the first-generation kernel (row-major weight operand).
 USE_FRAG = [os.environ.get("IIC_CONV_FRAG", "1") != "0"]
 
+# Optimiser epoch: part of the key of every bf16 operand cache (PreppedWeights through archs.cluster._ConvHolder,
+# linear.PTLinearOperands).  iic_amd.optim.Adam bumps it: its raw-pointer updates do not bump a parameter's _version.
+WEIGHTS_EPOCH = [0]
+
+
+def bump_weights_epoch():
+  WEIGHTS_EPOCH[0] += 1
+
 
 class PreppedWeights(object):
   """bf16 operands of one conv parameter, laid out lazily per consumer kernel.  `pw[0]` is the

@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from ._lib import check, lib, stream_ptr
-from .archs.cluster import bump_weights_epoch
+from .ops import bump_weights_epoch
 
 
 _CAPTURABLE = weakref.WeakSet()      # live capturable optimisers (their learning rates live on the device)

@@ -1,7 +1,7 @@
 """Semi-supervised fine-tuning on the device: the SupHead5 training step and the ten-crop evaluation.
 
-Host side of csrc/sup_head.hip.  What the reference's IID_semisup_STL10 script (examples/commands.txt §1.3, model 698)
-runs after the trunk:
+Host side of csrc/sup_head.hip, but for the Linear layers: those are iic_amd.linear's.  What the reference's
+IID_semisup_STL10 script (examples/commands.txt §1.3, model 698) runs after the trunk:
 
   SupHead5            code/archs/semisup/sup_head5.py: Linear(dlen, 2048) -> BatchNorm1d -> ReLU ->
                       Linear(2048, gt_k) on trunk(x, trunk_features=True, penultimate_features=...)
@@ -10,9 +10,9 @@ runs after the trunk:
                       TenCropAndFinish: TenCrop(input_sz) + custom_greyscale_to_tensor per crop, the ten logit rows of an
                       image summed in float64, arg-max, compared with the label
 
-With penultimate_features=True the first Linear reads layer 3's bf16 PT tensor in place on the bf16 MFMA pipe: no fp32
-NCHW copy of the activation, its bf16 operand refreshed once per optimiser step (the rule ops.PreppedWeights applies
-to the conv weights).  Under ops.fp32_mode() the whole head runs exact fp32 (pt_to_nchw + iic_gemm_f32): the parity tier.
+With penultimate_features=True the first Linear reads layer 3's bf16 PT tensor in place on the bf16 MFMA pipe
+(linear.PTLinearFn): no fp32 NCHW copy of the activation, its bf16 operand refreshed once per optimiser step (the rule
+ops.PreppedWeights applies to the conv weights).  Under ops.fp32_mode() the whole head runs exact fp32 (pt_to_nchw + iic_gemm_f32): the parity tier.
 
   train_loader        the script's shuffled training DataLoader over a resident PairedAugmenter: tf2 of
                       sobel_make_transforms with the script's --random_affine / --cutout flags (model 698:
@@ -27,13 +27,12 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import IICLibraryError, check, lib, ptr, stream_ptr
-from .archs import cluster as _cl
+from ._lib import check, lib, ptr, stream_ptr
 from .augment import FPARAMS, IPARAMS, PairedAugmenter
+from .linear import LinearF32Fn, PTLinearFn, PTLinearOperands
 from .transforms import sobel_process
 
-F32, BF16 = torch.float32, torch.bfloat16
-SUP_WS = ops.Scratch()      # partial matrices of the forward's K split
+F32 = torch.float32
 
 __all__ = ["SupHead5", "cross_entropy", "CrossEntropyLoss", "ten_crop_params", "TenCropAccumulator",
            "TenCropEvaluator", "permute_columns", "unpermute_columns", "train_loader"]
@@ -55,124 +54,6 @@ def unpermute_columns(C, H, W):
   i = np.arange(C * H * W, dtype=np.int64)
   c, p = i // (H * W), i % (H * W)
   return p * C + c
-
-
-class _LinearOperands(object):
-  """bf16 operands (wb [F][K], wt [K][F]) of one nn.Linear over a PT tensor, per branch; re-written in place when the
-  parameter has changed since they were made (data pointer, version counter, optimiser epoch)."""
-
-  def __init__(self):
-    self._ent = {}      # branch -> [key, wb, wt]
-
-  def get(self, w, C, H, W):
-    b = ops.current_branch()
-    key = (w.data_ptr(), w._version, _cl._WEIGHTS_EPOCH[0], C, H, W)
-    ent = self._ent.get(b)
-    if ent is not None and ent[0] == key:
-      return ent[1], ent[2]
-    Fo, K = w.shape
-    if ent is None or ent[1].device != w.device or ent[1].numel() != w.numel():
-      ent = self._ent[b] = [None, torch.empty((Fo, K), dtype=BF16, device=w.device),
-                            torch.empty((K, Fo), dtype=BF16, device=w.device)]
-    check(lib().iic_sup_weight_prep(ptr(w), ptr(ent[1]), ptr(ent[2]), Fo, C, H, W, stream_ptr()), "iic_sup_weight_prep")
-    ent[0] = key
-    return ent[1], ent[2]
-
-
-def linear_pt_forward(x_pt, wb, bias, F):
-  """y fp32 [N, F] = interior(x_pt) . wb^T + bias (iic_sup_linear_fwd)."""
-  N, Hp, Wp, C = x_pt.shape
-  H, W = Hp - 2, Wp - 2
-  S = lib().iic_sup_fwd_nsplit(N, F, C, H, W)
-  if S < 1:
-    raise IICLibraryError("iic_sup_linear_fwd: unsupported shape C = %d, F = %d (multiples of 64 only)" % (C, F))
-  y = torch.empty((N, F), dtype=F32, device=x_pt.device)
-  ws = SUP_WS.get(x_pt.device, S * N * F) if S > 1 else None
-  check(lib().iic_sup_linear_fwd(ptr(x_pt), ptr(wb), ptr(bias), ptr(y), ptr(ws), N, F, C, H, W, stream_ptr()),
-        "iic_sup_linear_fwd")
-  return y
-
-
-def dy_cast(dy):
-  """(dyb [N, F], dyt [F, Np]) bf16 of an fp32 [N, F] gradient (iic_sup_dy_cast)."""
-  N, F = dy.shape
-  Np = (N + 63) // 64 * 64
-  dyb = torch.empty((N, F), dtype=BF16, device=dy.device)
-  dyt = torch.empty((F, Np), dtype=BF16, device=dy.device)
-  check(lib().iic_sup_dy_cast(ptr(dy), ptr(dyb), ptr(dyt), N, F, stream_ptr()), "iic_sup_dy_cast")
-  return dyb, dyt
-
-
-def linear_pt_bwd_dx(dyb, wt, dx_pt):
-  N, Hp, Wp, C = dx_pt.shape
-  check(lib().iic_sup_linear_bwd_dx(ptr(dyb), ptr(wt), ptr(dx_pt), N, dyb.shape[1], C, Hp - 2, Wp - 2, stream_ptr()),
-        "iic_sup_linear_bwd_dx")
-  return dx_pt
-
-
-def linear_pt_wgrad(dyt, x_pt, N):
-  _, Hp, Wp, C = x_pt.shape
-  F = dyt.shape[0]
-  dW = torch.empty((F, C * (Hp - 2) * (Wp - 2)), dtype=F32, device=x_pt.device)
-  check(lib().iic_sup_linear_wgrad(ptr(dyt), ptr(x_pt), ptr(dW), N, F, C, Hp - 2, Wp - 2, stream_ptr()),
-        "iic_sup_linear_wgrad")
-  return dW
-
-
-class _LinearPTFn(torch.autograd.Function):
-  """Linear over layer 3's bf16 PT tensor [N, H+2, W+2, C] -> fp32 [N, F]."""
-
-  @staticmethod
-  def forward(ctx, x_pt, w, b, operands):
-    assert x_pt.dtype is BF16 and x_pt.is_contiguous() and x_pt.dim() == 4
-    N, Hp, Wp, C = x_pt.shape
-    wb, wt = operands.get(w.detach(), C, Hp - 2, Wp - 2)
-    ctx.save_for_backward(x_pt, wt)
-    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
-    return linear_pt_forward(x_pt, wb, b.detach() if b is not None else None, w.shape[0])
-
-  @ops.branch_backward
-  def backward(ctx, dy):
-    x_pt, wt = ctx.saved_tensors
-    N, Hp, Wp, C = x_pt.shape
-    dy = dy.contiguous()
-    dyb, dyt = dy_cast(dy)
-    dx = None
-    if ctx.needs_input_grad[0]:
-      dx = linear_pt_bwd_dx(dyb, wt, ops.pt_alloc(N, Hp - 2, Wp - 2, C, 1, dy.device))
-    dW = linear_pt_wgrad(dyt, x_pt, N)
-    db = ops.colsum(dy, N, dy.shape[1]) if ctx.needs_input_grad[2] else None
-    return dx, dW, db, None
-
-
-class _LinearF32Fn(torch.autograd.Function):
-  """nn.Linear on fp32 features, exact fp32 (iic_gemm_f32): feats [N, K], w [F, K], b [F] -> [N, F]."""
-
-  @staticmethod
-  def forward(ctx, feats, w, b):
-    feats, w = feats.contiguous(), w.contiguous()
-    N, K = feats.shape
-    Fo = w.shape[0]
-    y = torch.empty((N, Fo), dtype=F32, device=feats.device)
-    ops.gemm_f32(feats, K, 1, w, 1, K, y, Fo, N, Fo, K, bias=b.contiguous())
-    ctx.save_for_backward(feats, w)
-    ctx.branch, ctx.pt_dtype = ops.current_branch(), ops.PT_DTYPE[0]
-    return y
-
-  @ops.branch_backward
-  def backward(ctx, dy):
-    feats, w = ctx.saved_tensors
-    N, K = feats.shape
-    Fo = w.shape[0]
-    dy = dy.contiguous()
-    dW = torch.empty((Fo, K), dtype=F32, device=dy.device)
-    ops.gemm_f32(dy, 1, Fo, feats, K, 1, dW, K, Fo, K, N)
-    db = ops.colsum(dy, N, Fo)
-    dfe = None
-    if ctx.needs_input_grad[0]:
-      dfe = torch.empty((N, K), dtype=F32, device=dy.device)
-      ops.gemm_f32(dy, Fo, 1, w, K, 1, dfe, K, N, K, Fo)
-    return dfe, dW, db
 
 
 def bn_relu_forward(x, gamma, beta, running_mean, running_var, training, momentum, eps):
@@ -295,7 +176,7 @@ class SupHead5(nn.Module):
       elif isinstance(m, nn.Linear):
         m.weight.data.normal_(0, 0.01)
         m.bias.data.zero_()
-    self._operands = _LinearOperands()
+    self._operands = PTLinearOperands()
 
   def _features(self, x, penultimate_features):
     tr = self.trunk.trunk
@@ -314,11 +195,11 @@ class SupHead5(nn.Module):
       if f.shape[3] * (f.shape[1] - 2) * (f.shape[2] - 2) != lin1.in_features:
         raise ValueError("SupHead5: dlen = %d, the trunk gives %d features" % (
           lin1.in_features, f.shape[3] * (f.shape[1] - 2) * (f.shape[2] - 2)))
-      h = _LinearPTFn.apply(f, pv(lin1.weight), pv(lin1.bias), self._operands)
+      h = PTLinearFn.apply(f, pv(lin1.weight), pv(lin1.bias), self._operands)
     else:                  # fp32 features: the 512 pooled ones, or the exact tier (ops.fp32_mode())
-      h = _LinearF32Fn.apply(f, pv(lin1.weight), pv(lin1.bias))
+      h = LinearF32Fn.apply(f, pv(lin1.weight), pv(lin1.bias))
     h = _BNReLUFn.apply(h, pv(bn.weight), pv(bn.bias), bn)
-    return _LinearF32Fn.apply(h, pv(lin2.weight), pv(lin2.bias))     # no softmax (sup_head5.py:36)
+    return LinearF32Fn.apply(h, pv(lin2.weight), pv(lin2.bias))     # no softmax (sup_head5.py:36)
 
 
 # ------------------------------------------------------------------------------------

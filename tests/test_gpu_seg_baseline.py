@@ -197,7 +197,7 @@ def test_pair_linear_within_f64_brackets(case):
 
 
 def test_pair_linear_reproducible_and_unsupported():
-  from iic_amd.archs import seg_baselines as ab
+  from iic_amd import linear
   case = bc.PAIR_CASES[-2]      # N = 3, C = 1024, F = 1024: K split
   t = bc.pair_mantissa(case)
   _, y1, dW1, a1, b1, wb, wt = _pair_products(case, t)
@@ -205,23 +205,71 @@ def test_pair_linear_reproducible_and_unsupported():
   for _ in range(4):
     junk = junk @ junk * 1e-3      # other work queued in front of the second run, through the wrappers this time
   a0p, a1p = sc.to_pt(t["a0"]).to(dev()), sc.to_pt(t["a1"]).to(dev())
-  wb2, wt2 = ab.pair_weight_prep(t["w"].to(dev()), case.C, case.p)
-  y2 = ab.pair_linear_forward(a0p, a1p, wb2, t["b"].to(dev()), case.F)
-  from iic_amd.semisup import dy_cast
-  dyb, dyt = dy_cast(t["dy"].to(dev()))
-  a2, b2 = ab.pair_linear_bwd_dx(dyb, wt2, torch.zeros_like(a0p), torch.zeros_like(a1p))
-  dW2 = ab.pair_linear_wgrad(dyt, a0p, a1p)
+  wb2, wt2 = linear.pt_weight_prep(t["w"].to(dev()), case.C, case.p, case.p, 2)
+  y2 = linear.pt_linear_forward((a0p, a1p), wb2, t["b"].to(dev()), case.F)
+  dyb, dyt = linear.dy_cast(t["dy"].to(dev()))
+  a2, b2 = linear.pt_linear_bwd_dx(dyb, wt2, (torch.zeros_like(a0p), torch.zeros_like(a1p)))
+  dW2 = linear.pt_linear_wgrad(dyt, (a0p, a1p))
   torch.cuda.synchronize()
   for name, u, v in (("y", y1, y2), ("dW", dW1, dW2), ("dx0", a1, a2), ("dx1", b1, b2), ("wb", wb, wb2), ("wt", wt, wt2)):
     assert_bits(u, v, name + " second run")
-  assert ab.pair_fwd_nsplit(case.N, case.F, case.C, case.p) > 1
+  assert linear.pt_linear_nsplit(case.N, case.F, case.C, case.p, case.p, 2) > 1
   z = torch.zeros(16, device=dev())
   for F_, C_, p_ in ((100, 64, 3), (64, 96, 3), (64, 64, 2)):      # refused before a launch
-    assert ab.pair_fwd_nsplit(4, F_, C_, p_) == 0
+    assert linear.pt_linear_nsplit(4, F_, C_, p_, p_, 2) == 0
     assert parity.call("iic_pair_weight_prep", z, z, z, F_, C_, p_) == -3
     assert parity.call("iic_pair_linear_fwd", z, z, z, z, z, z, 4, F_, C_, p_) == -3
     assert parity.call("iic_pair_linear_bwd_dx", z, z, z, z, 4, F_, C_, p_) == -3
     assert parity.call("iic_pair_linear_wgrad", z, z, z, z, 4, F_, C_, p_) == -3
+
+
+def _sup_forward(a, wb_half, bias, case):
+  """iic_sup_linear_fwd of one activation against one [F, K] operand, H = W = p."""
+  from iic_amd import _lib
+  S = _lib.lib().iic_sup_fwd_nsplit(case.N, case.F, case.C, case.p, case.p)
+  assert S >= 1
+  y = torch.empty((case.N, case.F), dtype=F32, device=dev())
+  ws = torch.empty(max(1, S * case.N * case.F), dtype=F32, device=dev())
+  parity.ok("iic_sup_linear_fwd", a, wb_half, bias, y, ws, case.N, case.F, case.C, case.p, case.p)
+  return y
+
+
+@pytest.mark.parametrize("case", [c for c in bc.PAIR_CASES if c.name in ("N3_C64_p3_F128", "N130_C64_p3_F64",
+                                                                        "N3_C1024_p3_F1024")], ids=lambda c: c.name)
+def test_pair_entries_are_the_single_operand_entries_per_half(case):
+  """iic_pair_* is iic_sup_* (H = W = p) applied to each column half of the weight, bit for bit: the operands, dx and dW
+  on the full-mantissa draw; the forward on the lattice, where every partial sum is an integer below 2^24 and the sum of
+  the two halves' results is exact."""
+  K = bc.pair_K(case)
+  t = bc.pair_mantissa(case)
+  S, _, dW, g0, g1, wb, wt = _pair_products(case, t)
+  if case.C == 1024:
+    assert S > 1      # the K split is on
+  a = [sc.to_pt(t["a0"]).to(dev()), sc.to_pt(t["a1"]).to(dev())]
+  Np = (case.N + 63) // 64 * 64
+  dyb = torch.empty((case.N, case.F), dtype=BF16, device=dev())
+  dyt = torch.empty((case.F, Np), dtype=BF16, device=dev())
+  parity.ok("iic_sup_dy_cast", t["dy"].to(dev()), dyb, dyt, case.N, case.F)
+  for q in (0, 1):
+    wq = t["w"][:, q * K:(q + 1) * K].contiguous().to(dev())
+    wbq = torch.empty((case.F, K), dtype=BF16, device=dev())
+    wtq = torch.empty((K, case.F), dtype=BF16, device=dev())
+    parity.ok("iic_sup_weight_prep", wq, wbq, wtq, case.F, case.C, case.p, case.p)
+    assert_bits(wb[:, q * K:(q + 1) * K], wbq, "wb, half %d" % q)
+    assert_bits(wt[q * K:(q + 1) * K], wtq, "wt, half %d" % q)
+    dx = torch.zeros_like(a[q])
+    parity.ok("iic_sup_linear_bwd_dx", dyb, wt[q * K:(q + 1) * K].contiguous(), dx, case.N, case.F, case.C, case.p, case.p)
+    assert_bits((g0, g1)[q], dx, "dx, half %d" % q)
+    dWq = torch.full((case.F, K), parity.SENTINEL, dtype=F32, device=dev())
+    parity.ok("iic_sup_linear_wgrad", dyt, a[q], dWq, case.N, case.F, case.C, case.p, case.p)
+    assert_bits(dW[:, q * K:(q + 1) * K], dWq, "dW, half %d" % q)
+  # forward, on the lattice
+  t = bc.pair_lattice(case)
+  _, y, _, _, _, wb, _ = _pair_products(case, t)
+  a = [sc.to_pt(t["a0"]).to(dev()), sc.to_pt(t["a1"]).to(dev())]
+  bias = [t["b"].to(dev()), torch.zeros(case.F, dtype=F32, device=dev())]
+  halves = [_sup_forward(a[q], wb[:, q * K:(q + 1) * K].contiguous(), bias[q], case) for q in (0, 1)]
+  assert_bits(y, halves[0] + halves[1], "forward: the sum of the halves")
 
 
 # ======================================================================================================================

@@ -185,11 +185,11 @@ def test_backward_products_are_bit_reproducible():
     a = a @ a * 1e-3
   x_pt = sc.to_pt(t["x"]).to(dev())
   wb, wt = _prep(case, t["w"])
-  from iic_amd import semisup
-  dyb, dyt = semisup.dy_cast(t["dy"].to(dev()))
-  dx3 = semisup.linear_pt_bwd_dx(dyb, wt, torch.zeros_like(x_pt))
-  dW3 = semisup.linear_pt_wgrad(dyt, x_pt, case.N)
-  y3 = semisup.linear_pt_forward(x_pt, wb, t["b"].to(dev()), case.F)
+  from iic_amd import linear
+  dyb, dyt = linear.dy_cast(t["dy"].to(dev()))
+  dx3, = linear.pt_linear_bwd_dx(dyb, wt, (torch.zeros_like(x_pt),))
+  dW3 = linear.pt_linear_wgrad(dyt, (x_pt,))
+  y3 = linear.pt_linear_forward((x_pt,), wb, t["b"].to(dev()), case.F)
   torch.cuda.synchronize()
   for name, u, v, w_ in (("y", y1, y2, y3), ("dW", dW1, dW2, dW3), ("dx", dx1, dx2, dx3)):
     assert_bits(u, v, name + " run 2")
@@ -419,7 +419,7 @@ def test_ten_crop_evaluator_matches_manual_batches(module_setup):
 
 # ---- 8. unsupported shapes -------------------------------------------------------------------------------------------
 def test_unsupported_shapes_return_the_error_code():
-  from iic_amd import _lib, semisup
+  from iic_amd import _lib, linear
   u = sc.UNSUPPORTED
   K = sc.K_of(u)
   assert _lib.lib().iic_sup_fwd_nsplit(u.N, u.F, u.C, u.H, u.W) == 0
@@ -434,4 +434,4 @@ def test_unsupported_shapes_return_the_error_code():
     assert parity.call("iic_sup_linear_wgrad", dyt, x_pt, dW, u.N, F, C, u.H, u.W) == -3
   assert float(x_pt.float().abs().sum()) == 0.0 and float(dW.abs().sum()) == 0.0 and float(y.abs().sum()) == 0.0
   with pytest.raises(_lib.IICLibraryError):
-    semisup.linear_pt_forward(x_pt, wb, None, u.F)
+    linear.pt_linear_forward((x_pt,), wb, None, u.F)

@@ -158,12 +158,22 @@ def test_launch_plans_serve_the_siamese_stage(L, N, p):
 
 
 def test_pair_linear_host_queries():
-  from iic_amd.archs import seg_baselines as ab
-  assert ab.pair_fwd_nsplit(75, 1024, 1024, 11) == 64       # 8 column tiles, 3872 K-tiles: two workgroups per CU
-  assert ab.pair_fwd_nsplit(4, 1024, 1024, 3) > 1
-  assert ab.pair_fwd_nsplit(1, 64, 64, 3) >= 1
+  from iic_amd import linear
+  pair_fwd_nsplit = lambda N, F, C, p: linear.pt_linear_nsplit(N, F, C, p, p, 2)
+  assert pair_fwd_nsplit(75, 1024, 1024, 11) == 64       # 8 column tiles, 3872 K-tiles: two workgroups per CU
+  assert pair_fwd_nsplit(4, 1024, 1024, 3) > 1
+  assert pair_fwd_nsplit(1, 64, 64, 3) >= 1
   for bad in ((4, 100, 64, 3), (4, 64, 96, 3), (4, 64, 64, 4), (0, 64, 64, 3)):      # F, C, even p, N
-    assert ab.pair_fwd_nsplit(*bad) == 0
+    assert pair_fwd_nsplit(*bad) == 0
+
+
+def test_pair_forward_k_split_counts_are_pinned():
+  """iic_pair_linear_fwd_nsplit at 256 CUs (the count without a device, and the MI355X's): two workgroups per CU over the
+  row x column tiles, at least 8 K-tiles per slice, at most 64 slices."""
+  from iic_amd import _lib
+  L = _lib.lib()
+  assert L.iic_pair_linear_fwd_nsplit(75, 1024, 1024, 11) == 64      # 8 tiles -> 64 wanted; 3872 K-tiles; the cap
+  assert L.iic_pair_linear_fwd_nsplit(3, 1024, 1024, 3) == 36        # 8 tiles -> 64 wanted; 288 K-tiles / 8 = 36
 
 
 # ---- argument checks ---------------------------------------------------------------------------------------------------

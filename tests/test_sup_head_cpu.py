@@ -68,6 +68,22 @@ def test_lattice_preconditions():
       assert torch.equal(sc.bf16(v), v)
 
 
+# ---- the forward's K split ---------------------------------------------------------------------------------------------
+def test_forward_k_split_counts_are_pinned():
+  """iic_sup_fwd_nsplit at 256 CUs (the count without a device, and the MI355X's): two workgroups per CU over the
+  row x column tiles, at least 8 K-tiles per slice, at most 16 slices; 0 for a shape the kernels do not serve."""
+  from iic_amd import _lib
+  L = _lib.lib()
+  for (N, F, C, H, W), want in (((37, 192, 64, 3, 3), 1),           # 2 tiles; 9 K-tiles: no slice has 8
+                                ((12, 2048, 256, 5, 5), 12),        # 16 tiles -> 32 wanted; 100 K-tiles / 8 = 12
+                                ((150, 64, 64, 2, 3), 1),           # 6 K-tiles
+                                ((3, 64, 64, 9, 8), 9),             # 1 tile -> 512 wanted; 72 K-tiles / 8 = 9
+                                ((700, 2048, 256, 9, 9), 6)):       # 96 tiles -> 6 wanted; 324 K-tiles
+    assert L.iic_sup_fwd_nsplit(N, F, C, H, W) == want, (N, F, C, H, W)
+  u = sc.UNSUPPORTED
+  assert L.iic_sup_fwd_nsplit(u.N, u.F, u.C, u.H, u.W) == 0
+
+
 # ---- the three products: correct arithmetic passes, defects are rejected -------------------------------------------
 @pytest.mark.parametrize("draw", sc.DRAWS)
 @pytest.mark.parametrize("case", sc.CASES, ids=lambda c: c.name)

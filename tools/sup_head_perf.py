@@ -3,7 +3,7 @@ before it existed, both sides on the same device in one process, alternating aft
 
 (a) head forward + backward from layer 3's bf16 PT tensor to every gradient (head parameters and the PT tensor's):
       baseline  ops.pt_to_nchw(x, 1).reshape(N, -1) -> torch.nn Linear / BatchNorm1d / ReLU / Linear -> nn.CrossEntropyLoss
-      new       the autograd Functions of iic_amd.semisup over the iic_sup_* kernels + iic_amd.semisup.cross_entropy;
+      new       the autograd Functions of iic_amd.linear / iic_amd.semisup over the iic_sup_* kernels + cross_entropy;
                 `new` re-writes the bf16 weight operands every step (what a training step pays: once per optimiser step),
                 `new_no_prep` re-uses them (an evaluation forward's cost is not timed here; this isolates the products)
     Wall time of a step that starts and ends with a device synchronise; median, min, max over the repeats.  FLOP of the
@@ -33,8 +33,7 @@ import torch
 import torch.nn as nn
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
-from iic_amd import archs, ops, semisup                     # noqa: E402
-from iic_amd.archs import cluster as _cl                    # noqa: E402
+from iic_amd import archs, linear, ops, semisup             # noqa: E402
 from iic_amd.transforms import sobel_process                # noqa: E402
 
 BF16_PEAK = 2.5e15
@@ -69,7 +68,7 @@ def head_step_forms(N, C, HW, F, k, dev):
   with torch.no_grad():
     head[0].weight.normal_(0, 0.01)
   crit = nn.CrossEntropyLoss()
-  operands = semisup._LinearOperands()
+  operands = linear.PTLinearOperands()
 
   def clear():
     for p in head.parameters():
@@ -87,14 +86,14 @@ def head_step_forms(N, C, HW, F, k, dev):
   def new_no_prep():
     clear()
     lin1, bn, _, lin2 = head
-    h = semisup._LinearPTFn.apply(x_pt, lin1.weight, lin1.bias, operands)
+    h = linear.PTLinearFn.apply(x_pt, lin1.weight, lin1.bias, operands)
     h = semisup._BNReLUFn.apply(h, bn.weight, bn.bias, bn)
-    loss = semisup._CrossEntropyFn.apply(semisup._LinearF32Fn.apply(h, lin2.weight, lin2.bias), targets)
+    loss = semisup._CrossEntropyFn.apply(linear.LinearF32Fn.apply(h, lin2.weight, lin2.bias), targets)
     loss.backward()
     return loss
 
   def new():
-    _cl.bump_weights_epoch()          # as after an optimiser step: the operands are stale
+    ops.bump_weights_epoch()          # as after an optimiser step: the operands are stale
     return new_no_prep()
 
   return dict(baseline=baseline, new=new, new_no_prep=new_no_prep), head, x_pt
